@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: realisations/sec, 68 pulsars x 5000 TOAs, GWB + RN + WN (EFAC/EQUAD + ECORR), fp64.
 
-    python bench.py --gpus N --steps K --warmup W [--batch R]
+    python bench.py --gpus N --steps K --warmup W [--batch R] [--dump-outputs DIR] [--full]
 
 Workload = BASELINE.json config 3 as SURVEY.md §8d specifies it (headline_array): the 68 pulsars of ng15_dict.json with their
 per-backend EFAC / t2EQUAD / ECORR and red-noise values, HD GWB at the dictionary's gw_log10_A, 1024 realisations per step.
@@ -12,7 +12,12 @@ so rank g generates realisations [g*R*(K+W) .. ) of the same seeded stream (weak
 north_star's gather of the residual arrays to rank 0 is timed separately as a pipelined generate+gather
 (`gathered_to_rank0`), not folded into the step.  Rank 0 prints ONE JSON line.
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value, unit, ms_per_step, ...) only.
+--dump-outputs DIR writes what the last timed step returned (a seeded sample of realisations of out[R, n_toa], float64) as
+DIR/*.npy: with the same arguments the inputs are identical from run to run, so two builds can be compared output for output.
+--full adds every secondary measurement below (and, N > 1, the ranks seen, per-rank step times and the gather to rank 0).
+
+With --full, besides the contract fields the line carries
   roofline      the dominant kernel of the step against its bound: algorithmic units per launch / launch time measured
                 here with HIP events on the launch stream; HBM peak 8 TB/s (MI355X_MICROARCH.md); fp64 matrix peak
                 78.6 TFLOP/s = AMD's public MI355X figure, cross-checked by the in-library microbenchmark.  `traffic`
@@ -276,6 +281,44 @@ def compact_line(full):
     return line
 
 
+def headline_fields(world, R, K, W, elapsed, eng, args):
+    """the contract fields of the line: the same in a plain run and under --full"""
+    return {
+        "metric": "realizations/sec, 68 psr x 5000 TOAs GWB+RN+WN", "value": world * R * K / elapsed, "unit": "realizations/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"BASELINE.json config 3: the {args.psr} pulsars of ng15_dict.json x {args.toa} synthetic TOAs - HD GWB (gw_log10_A of the dict) + "
+                               f"per-pulsar power-law RN (dict values, 30 components) + per-backend EFAC / t2EQUAD / ECORR (dict values), on-chip Philox "
+                               f"draws, {R} realisations per step per GPU",
+                   "realisations_per_step_per_gpu": R, "n_toa_total": eng.n_toa, "Nf": eng.grid["Nf"], "npts": eng.plan.gw_npts,
+                   "parallelism": f"replica-shard x{world}"},
+    }
+
+
+DUMP_MAX_BYTES = 48_000_000    # the residual sample of --dump-outputs; the index arrays beside it stay far below the 64 MB of the whole dump
+
+
+def dump_outputs(out, r0, path, seed=20261016):
+    """--dump-outputs: what the last timed step returned, out[R, n_toa] (residuals in seconds, float64, realisations r0 .. r0+R-1).
+    All of it when it fits DUMP_MAX_BYTES, else a fixed seeded sample of whole realisations (and, only if one realisation alone is
+    too large, of TOAs): residuals.npy [rows, cols], realisation.npy = the realisation number of each row, toa_index.npy = the column
+    of out of each residual column (written only when the TOAs are sampled)."""
+    import torch
+    R, n = out.shape
+    budget = DUMP_MAX_BYTES // 8
+    rng = np.random.default_rng(seed)
+    rows = np.arange(R) if R * n <= budget else np.sort(rng.choice(R, max(1, min(R, budget // n)), replace=False))
+    cols = None if len(rows) * n <= budget else np.sort(rng.choice(n, budget // (2 * len(rows)), replace=False))
+    sub = out.index_select(0, torch.as_tensor(rows, device=out.device))
+    if cols is not None:
+        sub = sub.index_select(1, torch.as_tensor(cols, device=out.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "residuals.npy"), np.ascontiguousarray(sub.cpu().numpy(), dtype=np.float64))
+    np.save(os.path.join(path, "realisation.npy"), (r0 + rows).astype(np.float64))
+    if cols is not None:
+        np.save(os.path.join(path, "toa_index.npy"), cols.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -288,7 +331,12 @@ def main():
     ap.add_argument("--no-td", action="store_true", help="skip the TD-mode (dense covariance / Cholesky / L.z) measurement")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the timed generate+gather-to-rank-0 pipeline")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (config-4 shape, drop-in API timing): profiling runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (a seeded sample, float64) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement (variants, per-kernel times, roofline, microbenchmarks, "
+                                                        "TD mode, grid, API timing, CPU baseline; N > 1: ranks seen, per-rank times, gather)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -339,6 +387,14 @@ def main():
         return el
 
     elapsed = timed_steps()
+    if args.dump_outputs and rank == 0:     # `out` still holds the last timed step: nothing below may run before this
+        dump_outputs(out, base + (W + K - 1) * R, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_fields(world, R, K, W, elapsed, eng, args)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- secondary numbers, same K steps: (i) opt-in fp32 Gaussian transform; (ii) GWB drawn on the npts-sample grid through the
     # factor of its covariance (npts instead of 2 Nf normals per pulsar; same distribution, not replayable
     # through the reference's frequency-domain algebra).  `value` stays the default: fp64 transform, reference-order draws.
@@ -633,13 +689,7 @@ def main():
                   "note": "flops = 4 P^2 Nf + 5 n log2 n P + 2 K sum N_a + 10 sum N_a; deviates = 2 P Nf + P K + 2 sum N_a + sum E_a (SURVEY.md §8d)"}
 
     line = {
-        "metric": "realizations/sec, 68 psr x 5000 TOAs GWB+RN+WN", "value": world * R * K / elapsed, "unit": "realizations/s",
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"BASELINE.json config 3: the {args.psr} pulsars of ng15_dict.json x {args.toa} synthetic TOAs - HD GWB (gw_log10_A of the dict) + "
-                               f"per-pulsar power-law RN (dict values, 30 components) + per-backend EFAC / t2EQUAD / ECORR (dict values), on-chip Philox "
-                               f"draws, {R} realisations per step per GPU",
-                   "realisations_per_step_per_gpu": R, "n_toa_total": eng.n_toa, "Nf": Nf, "npts": npts, "parallelism": f"replica-shard x{world}"},
+        **headline_fields(world, R, K, W, elapsed, eng, args),
         "value_fast_rng_math": world * R * K / elapsed_fast,
         "value_gwb_grid_draws": world * R * K / elapsed_grid,
         "value_single_deviate_wn": world * R * K / elapsed_single,

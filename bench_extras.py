@@ -2,7 +2,7 @@
 """Secondary measurements of bench.py (kept out of the headline file): the dense TD path (covariance assembly, batched
 Cholesky, L.z) on the headline array, on an ng15-like ragged array and on BASELINE config 2's shape; one cell of the (N_psr, N_toa)
 grid with the CPU port timed beside it; engine clocks; the drop-in add_* API; the anisotropic ORF basis of config 5's geometry.
-bench.py calls these at N = 1 unless --no-td / --no-extras; scripts/gpu_*.py call them directly.  `bench.<name>` still resolves."""
+bench.py --full calls these at N = 1 unless --no-td / --no-extras; scripts/gpu_*.py call them directly.  `bench.<name>` still resolves."""
 import json
 import os
 import sys

@@ -2,7 +2,7 @@
 # (--pmc passes carry --kernel-trace only: gpurun refuses PMC combined with sys/runtime/hip/hsa tracing.)
 cd $GRAFT_REPO_ROOT && export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_r5; rm -rf $OUT; mkdir -p $OUT
-CMD="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o b -- $CMD > $OUT/trace.log 2>&1; echo "trace rc=$?" >> $OUT/trace.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o b -- $CMD > $OUT/pmc_fetch.log 2>&1; echo "rc=$?" >> $OUT/pmc_fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o b -- $CMD > $OUT/pmc_write.log 2>&1; echo "rc=$?" >> $OUT/pmc_write.log

@@ -6,7 +6,7 @@ tail -4 $O/pytest.log
 timeout 1500 bash scripts/gpu_profile_r4.sh > $O/profile.log 2>&1; echo "profile rc=$?"
 tail -12 $O/profile.log
 cp gpurun_out/prof_r4/r04_pmc.json profiles/r04_pmc.json
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 tail -c 300 $O/bench.err
 python - <<'PY'
 import json

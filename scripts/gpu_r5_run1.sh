@@ -6,7 +6,7 @@ timeout 300 python scripts/gpu_r5_nan_repro.py > $O/nan_repro.log 2>&1; echo "na
 T0=$(date +%s); timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$? in $(( $(date +%s) - T0 )) s" >> $O/pytest.log; tail -6 $O/pytest.log
 timeout 300 python scripts/gpu_r5_first_call.py > $O/first_call.log 2>&1; echo "rc=$?" >> $O/first_call.log; tail -22 $O/first_call.log
 timeout 300 python scripts/gpu_r5_cov_only.py --ragged > $O/cov_only.json 2> $O/cov_only.err; cat $O/cov_only.json
-T0=$(date +%s); timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"; tail -c 2500 $O/bench.json
+T0=$(date +%s); timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"; tail -c 2500 $O/bench.json
 P=$GRAFT_REPO_ROOT/$O/prof; rm -rf $P; mkdir -p $P
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o c -- python scripts/gpu_r5_cov_only.py > $P/trace.log 2>&1; echo "trace rc=$?" >> $P/trace.log
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $P/pmc_mfma -o c -- python scripts/gpu_r5_cov_only.py > $P/pmc_mfma.log 2>&1; echo "rc=$?" >> $P/pmc_mfma.log

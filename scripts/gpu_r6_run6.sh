@@ -4,7 +4,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r6f; rm -rf $O; mkdir -p $O
 T0=$(date +%s); timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$? in $(( $(date +%s) - T0 )) s" >> $O/pytest.log; tail -4 $O/pytest.log
 rocprofv3 --kernel-trace --output-format csv -d $O/trmm -o t -- python scripts/gpu_r6_trmm_trace.py > $O/trmm.log 2>&1; echo "trace rc=$?"
 python scripts/trace_timeline.py $O/trmm 8
-T0=$(date +%s); timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"; cp gpurun_out/bench_full.json $O/bench_full.json
+T0=$(date +%s); timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$? in $(( $(date +%s) - T0 )) s"; cp "${O%/*}/bench_full.json" $O/bench_full.json
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r6f/bench.json'))

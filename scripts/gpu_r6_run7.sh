@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT && export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r6g; rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_td.py tests/test_gpu_configs.py -m gpu -x -q > $O/pytest.log 2>&1; tail -4 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 1200 python bench.py --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 1200 python bench.py --full --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/r6g/bench.json'))

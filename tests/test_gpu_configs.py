@@ -306,3 +306,33 @@ def test_bench_helpers_small_shapes():
     assert r["n_toa_total"] == 600 + 1301 + 2050 + 130
     ck = bench.engine_clock_during(lambda: bench.grid_cell, 0.05)      # a no-op load: the probe alone
     assert ck is None or 0.05 < ck["GHz"] < 3.5
+
+
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """a plain bench run (no --full) on a small array: one JSON line of the contract fields only, `steps` timed steps, and with
+    --dump-outputs the residuals of the LAST timed step, bit-identical to the engine regenerating those realisations in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from pta_replicator_amd.engine import ReplicaEngine
+    R, K, W = 16, 3, 2
+    cmd = [sys.executable, os.path.join(bench.ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--batch", str(R),
+           "--psr", "5", "--toa", "300", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=bench.ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                      "dtype", "data", "config"}
+    assert d["steps"] == K and d["warmup"] == W and d["dtype"] == "f64" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] - R * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert sorted(os.listdir(tmp_path / "dump")) == ["realisation.npy", "residuals.npy"]
+    res = np.load(tmp_path / "dump" / "residuals.npy")
+    real = np.load(tmp_path / "dump" / "realisation.npy")
+    assert res.dtype == np.float64 and np.array_equal(real, np.arange((W + K - 1) * R, (W + K) * R, dtype=np.float64))
+    psrs, noise = bench.headline_array(5, 300)
+    eng = bench.configure_engine(ReplicaEngine(psrs, seed=20260921), noise).prepare()
+    assert np.array_equal(res, eng.generate(R, r0=(W + K - 1) * R).cpu().numpy())

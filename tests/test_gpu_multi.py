@@ -76,7 +76,7 @@ def test_bench_two_ranks_dry_run_on_one_device():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PTA_BENCH_SINGLE_DEVICE="1", PTA_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "32", "--no-td", "--no-cpu-baseline", "--no-extras"]
+           "--batch", "32", "--full", "--no-td", "--no-cpu-baseline", "--no-extras"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

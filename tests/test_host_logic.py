@@ -690,6 +690,34 @@ def test_bench_line_roofline_fits_the_driver_record():
     assert list(empty["roofline"])[:8] == list(roof)[:8] and len(empty["roofline"]) <= 24
 
 
+def test_bench_dump_outputs_is_a_bounded_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: a small batch is written whole; a large one as the same seeded sample of whole realisations on every
+    run, within 64 MB, float64, with the realisation number of each row; a realisation too long for the budget is sampled by TOA too."""
+    import os
+    import torch
+    import bench
+
+    def dump(out, name):
+        bench.dump_outputs(out, 40, str(tmp_path / name))
+        files = sorted(os.listdir(tmp_path / name))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64e6
+        return {f[:-4]: np.load(tmp_path / name / f) for f in files}
+
+    small = torch.arange(6 * 50, dtype=torch.float64).reshape(6, 50)
+    z = dump(small, "small")
+    assert set(z) == {"residuals", "realisation"} and np.array_equal(z["residuals"], small.numpy())
+    assert np.array_equal(z["realisation"], np.arange(40, 46, dtype=np.float64))
+    n = 340000                                       # the headline array's TOA count
+    big = torch.arange(64, dtype=torch.float64)[:, None] * 1e6 + torch.arange(n, dtype=torch.float64)[None, :]
+    a, b = dump(big, "big_a"), dump(big, "big_b")
+    rows = a["realisation"].astype(int) - 40
+    assert a["residuals"].dtype == np.float64 and len(rows) == bench.DUMP_MAX_BYTES // (8 * n) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["residuals"], big.numpy()[rows]) and all(np.array_equal(a[k], b[k]) for k in a)
+    long = torch.zeros((2, bench.DUMP_MAX_BYTES // 8 + 1), dtype=torch.float64)
+    c = dump(long, "long")
+    assert set(c) == {"residuals", "realisation", "toa_index"} and c["residuals"].shape == (1, len(c["toa_index"]))
+
+
 def test_from_enterprise_adapter_reads_enterprise_style_arrays():
     """VERDICT r4 #6 / SURVEY.md §7 step 2: an object with enterprise's array surface (toas [s], toaerrs [s], flags dict, backend_flags,
     _raj/_decj or theta/phi or pos) becomes an array-backed SimulatedPulsar that the add_* functions and the engine take; the numbers the
