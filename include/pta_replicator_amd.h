@@ -48,7 +48,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
 /* Throughput-mode draws. The reference consumes NumPy's global legacy stream
  * (red_noise.py:119,127,176,238-240; white_noise.py:80,105-109,155,182); on the device every
  * deviate is Philox-4x32-10(key = seed, counter = (pair, stream, realisation)) + Box-Muller.
- * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor). */
+ * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor),
+ * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -278,6 +279,22 @@ int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t ldw, int R,
                 const double *pre, const double *FB, const double *tw, const double *post, double *G0, int64_t ldg,
                 int variant, int rng_fast, void *stream);
 
+/* Per-realisation GWB spectrum (ABI 8, additive): the two on-chip-draw transforms above with every drawn pair of bin k of row
+ * (r, a) multiplied by scale[r * ld_scale + k] (k = 1 .. Nf-2) before the pre-chirp / twiddle product.  With scale =
+ * hcf(theta_r) / hcf0 (pta_gwb_spectrum_scale) the row is the one a table built for theta_r gives: the ORF mix is linear and the
+ * spectrum common to all pulsars, M (s o w) = s o (M w) per bin (red_noise.py:267-270).  pta_gwb_czt_scaled: w must be NULL,
+ * variant 0 or 1.                                                                                                       */
+int pta_gwb_czt_scaled(uint64_t seed, uint64_t r0, const double *w, int64_t ldw, int R, int P, int Nf, int npts, int i0,
+                       const double *pre, const double *FB, const double *tw, const double *post, double *G0, int64_t ldg,
+                       int variant, int rng_fast, const double *scale, int64_t ld_scale, void *stream);
+int pta_gwb_idft_rng_scaled(uint64_t seed, uint64_t r0, int R, int P, int Nf, const double *Tsym, const double *rot, int npts,
+                            double *G0, int64_t ldg, int variant, int rng_fast, const double *scale, int64_t ld_scale, void *stream);
+/* scale[r * ld_scale + k] = hcf(f[k]; 10^log10_A[r], gamma[r]) / hcf0[k], k < Nf, r < R (ld_scale >= Nf): hcf = A (f / f1yr)^((3 - gamma)/2),
+ * f1yr = 1 / 3.16e7, with turnover != 0 divided by (1 + (f / f0)^(power (alpha - beta)))^(1 / power) (red_noise.py:245-251).
+ * hcf0 = the configured spectrum's hcf on the grid f (red_noise.gwb_spectrum_hcf).                                      */
+int pta_gwb_spectrum_scale(const double *f, const double *hcf0, int Nf, int R, const double *log10_A, const double *gamma, int turnover,
+                           double f0, double beta, double power, double *scale, int64_t ld_scale, void *stream);
+
 /* G[r,a,:] = sum_b Mchol[a,b] G0[r,b,:]  (the M@w of red_noise.py:268, applied after the DFT). */
 /* variant 0 (default): LDS-resident Mchol kernel when P <= 80, generic batched MFMA GEMM otherwise; 1: always the generic
  * MFMA GEMM; 2: the generic VALU reference GEMM (cross-check)                                                       */
@@ -390,6 +407,43 @@ typedef struct {
 
 int pta_engine_generate(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, uint64_t seed, uint64_t r0, int R,
                         double *out, int64_t ld_out, void *stream);
+
+/* ---------------------------------------------------------------- per-realisation hyperparameters (ABI 8, additive) */
+/* out[r * n_par + j] = lo[j] + (hi[j] - lo[j]) u (one fma), u = uniform u2 of pair j of stream (HYPER, 0), realisation r0 + r:
+ * theta of a realisation is a pure function of (seed, realisation).  lo / hi: device [n_par].                            */
+int pta_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *lo, const double *hi, double *out, void *stream);
+
+/* pta_engine_rn_coef with sqrt(prior) computed per (r, a, c) (red_noise.py:126):
+ *   coef[(r*P + a)*K + c] = sqrt(A^2 (f / fyr)^-gamma / (12 pi^2 Tspan_a) yr^3) * z(seed, r0+r, (RN,a), c),
+ * f = rn_f[a * K/2 + c/2] [Hz], Tspan_a = rn_tspan[a] [s], A = 10^log10_A[r*P + a], gamma = gamma[r*P + a], yr = 365.25 d.
+ * log10_A = NaN takes amp_fixed[a*K + c] (the configured amplitude).  Same deviates as pta_engine_rn_coef.                */
+int pta_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P, int K, const double *rn_f, const double *rn_tspan,
+                             const double *log10_A, const double *gamma, const double *amp_fixed, double *coef, int rng_fast,
+                             void *stream);
+
+/* theta of a batch of pta_engine_generate_hyper; row r of every array belongs to realisation r0 + r.  A NULL member means "as
+ * configured", and the stage it feeds is then the kernel pta_engine_generate runs.                                        */
+typedef struct {
+  const double *gw_scale;     /* [R x ld_gw_scale] precomputed per-realisation spectrum scale; NULL = from gw_log10_A / gw_gamma */
+  int64_t ld_gw_scale;        /* >= gw_nf */
+  const double *gw_log10_A;   /* [R] (NULL with gw_scale NULL: configured spectrum) */
+  const double *gw_gamma;     /* [R] */
+  const double *gw_f;         /* [gw_nf] frequency grid of the GWB (red_noise.py:230-232) */
+  const double *gw_hcf0;      /* [gw_nf] hcf of the configured spectrum on that grid */
+  int32_t gw_turnover;        /* turnover arguments of the configured GWB (f0, beta, power stay fixed) */
+  double gw_f0, gw_beta, gw_power;
+  double *ws_scale;           /* [R x ld_gw_scale] workspace pta_gwb_spectrum_scale writes */
+  const double *rn_f;         /* [n_psr x rn_k/2] red-noise frequencies [Hz] */
+  const double *rn_tspan;     /* [n_psr] Tspan [s] */
+  const double *rn_log10_A;   /* [R x n_psr] (NULL: configured red noise); NaN = configured amplitude of that pulsar */
+  const double *rn_gamma;     /* [R x n_psr] */
+} pta_engine_hyper;
+
+/* pta_engine_generate with per-realisation theta: pta_gwb_spectrum_scale -> pta_gwb_czt_scaled (or pta_gwb_idft_rng_scaled) ->
+ * pta_gwb_mix -> pta_engine_rn_coef_hyper -> pta_engine_synth (unchanged).  White noise, ECORR and deterministic signals as
+ * configured in the plan.                                                                                                 */
+int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, const pta_engine_hyper *hyper_host,
+                              uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out, void *stream);
 
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,

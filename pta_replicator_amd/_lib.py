@@ -61,6 +61,15 @@ class TdPlan(ctypes.Structure):
     ]
 
 
+class EngineHyper(ctypes.Structure):
+    """pta_engine_hyper (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("gw_scale", _P), ("ld_gw_scale", c_int64), ("gw_log10_A", _P), ("gw_gamma", _P), ("gw_f", _P), ("gw_hcf0", _P),
+        ("gw_turnover", c_int32), ("gw_f0", c_double), ("gw_beta", c_double), ("gw_power", c_double), ("ws_scale", _P),
+        ("rn_f", _P), ("rn_tspan", _P), ("rn_log10_A", _P), ("rn_gamma", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -97,6 +106,10 @@ _SIGNATURES = {
     "pta_gwb_czt_fits": (c_int, [c_int, c_int, c_int]),
     "pta_gwb_czt_setup": (c_int, [_P, c_int, c_int, c_int, c_double, _P, _P, _P, _P, _P]),
     "pta_gwb_czt": (c_int, [c_uint64, c_uint64, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int64, c_int, c_int, _P]),
+    "pta_gwb_czt_scaled": (c_int, [c_uint64, c_uint64, _P, c_int64, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int64, c_int, c_int,
+                                   _P, c_int64, _P]),
+    "pta_gwb_idft_rng_scaled": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, c_int, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
+    "pta_gwb_spectrum_scale": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_double, c_double, c_double, _P, c_int64, _P]),
     "pta_gwb_mix": (c_int, [_P, c_int, _P, c_int, c_int, c_int64, _P, c_int, _P]),
     "pta_gwb_bracket": (c_int, [_P, c_int, _P, c_int, _P, _P]),
     "pta_gwb_weights": (c_int, [_P, c_int, _P, _P, c_int, _P, _P]),
@@ -106,6 +119,10 @@ _SIGNATURES = {
     "pta_cw_catalog": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_double, _P, _P, c_int, _P]),
     "pta_engine_rn_coef": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, c_int, _P]),
     "pta_engine_generate": (c_int, [POINTER(EnginePlan), POINTER(EngineTables), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
+    "pta_hyper_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P]),
+    "pta_engine_rn_coef_hyper": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "pta_engine_generate_hyper": (c_int, [POINTER(EnginePlan), POINTER(EngineTables), POINTER(EngineHyper), c_uint64, c_uint64, c_int, _P,
+                                          c_int64, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),

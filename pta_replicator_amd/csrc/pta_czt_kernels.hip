@@ -97,12 +97,17 @@ extern "C" int pta_gwb_czt_fits(int Nf, int npts, int i0) { return czt_fits(Nf, 
 // global twiddle loads per thread (the q-strided twiddle gathers, not LDS or the barriers, bounded the first version:
 // 3.2 -> 2.0 ms per 65 280 rows; rocprofv3 SQ_INSTS_VALU now accounts for ~95 % of the time).  FUSE = 0 (every stage through
 // LDS, table twiddles) is kept as the cross-check.
-template <bool RNG, bool FAST, int FUSE>
+// SCALED (per-realisation spectrum, pta_gwb_czt_scaled): the drawn pair of bin k of row `row` is multiplied by
+// scale[(row / P) * ld_scale + k] = hcf(f_k; theta_r) / hcf0(f_k) before the pre-chirp product, which carries sqrt(C0).  The ORF mix
+// that follows is linear and the spectrum is common to all pulsars, so M (s o w) = s o (M w) per bin (red_noise.py:267-270).
+// SCALED = false compiles to the kernel without the scale operands.
+template <bool RNG, bool FAST, int FUSE, bool SCALED>
 __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, uint64_t r0, const double *__restrict__ w, int64_t ldw,
                                                                   int M, int P, int Nf, int npts, int i0,
                                                                   const double *__restrict__ pre, const double *__restrict__ FB,
                                                                   const double *__restrict__ tw, const double *__restrict__ post,
-                                                                  double *__restrict__ G0, int64_t ldg) {
+                                                                  double *__restrict__ G0, int64_t ldg,
+                                                                  const double *__restrict__ scale, int64_t ld_scale) {
   __shared__ double re[PTA_FFT_PLANE], im[PTA_FFT_PLANE];
   const int tid = threadIdx.x;
   const int row = blockIdx.x;
@@ -136,6 +141,11 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
           wr = w[(int64_t)row * ldw + 2 * (t + 1)];
           wi = w[(int64_t)row * ldw + 2 * (t + 1) + 1];
         }
+        if (SCALED) {
+          const double sc = scale[(int64_t)(row / P) * ld_scale + t + 1];
+          wr *= sc;
+          wi *= sc;
+        }
         const pta_cplx pc = pre2[t];
         v[q] = {wr * pc.re - wi * pc.im, wr * pc.im + wi * pc.re};
       }
@@ -154,6 +164,11 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
         } else {
           wr = w[(int64_t)row * ldw + 2 * (t + 1)];
           wi = w[(int64_t)row * ldw + 2 * (t + 1) + 1];
+        }
+        if (SCALED) {
+          const double sc = scale[(int64_t)(row / P) * ld_scale + t + 1];
+          wr *= sc;
+          wi *= sc;
         }
         const pta_cplx pc = pre2[t];
         ar = wr * pc.re - wi * pc.im;
@@ -244,8 +259,8 @@ extern "C" int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t 
   const int fastm = rng_fast ? 1 : 0;
   const int fuse = variant == 0 ? 15 : (variant == 1 ? 0 : variant - 10);
 #define PTA_CZT_X(RNGV, FASTV, FUSEV)                                                                                                  \
-  hipLaunchKernelGGL((k_gwb_czt<RNGV, FASTV, FUSEV>), dim3(M), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), seed, r0, w, ldw, M, P, \
-                     Nf, npts, i0, pre, FB, tw, post, G0, ldg)
+  hipLaunchKernelGGL((k_gwb_czt<RNGV, FASTV, FUSEV, false>), dim3(M), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), seed, r0, w, ldw, \
+                     M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, nullptr, 0)
 #define PTA_CZT_XF(FUSEV)              \
   if (w)                               \
     PTA_CZT_X(false, false, FUSEV);    \
@@ -264,6 +279,41 @@ extern "C" int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t 
   }
 #undef PTA_CZT_XF
 #undef PTA_CZT_X
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+// The same transform with a per-realisation spectrum: on-chip draws only, variants 0 (default) and 1 (cross-check).
+extern "C" int pta_gwb_czt_scaled(uint64_t seed, uint64_t r0, const double *w, int64_t ldw, int R, int P, int Nf, int npts, int i0,
+                                  const double *pre, const double *FB, const double *tw, const double *post, double *G0, int64_t ldg,
+                                  int variant, int rng_fast, const double *scale, int64_t ld_scale, void *stream) {
+  PTA_REQUIRE(pre && FB && tw && post && G0 && scale, PTA_E_ARG, "pta_gwb_czt_scaled: NULL argument");
+  PTA_REQUIRE(!w, PTA_E_ARG, "pta_gwb_czt_scaled: draws are generated on chip (w must be NULL)");
+  (void)ldw;
+  PTA_REQUIRE(R > 0 && P > 0 && P < (1 << 24) && npts > 0 && ldg >= npts, PTA_E_ARG, "pta_gwb_czt_scaled: R=%d P=%d npts=%d", R, P,
+              npts);
+  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt_scaled: Nf=%d npts=%d does not fit one 4096-point convolution", Nf,
+              npts);
+  PTA_REQUIRE(ld_scale >= Nf - 1, PTA_E_ARG, "pta_gwb_czt_scaled: ld_scale=%lld < Nf - 1", (long long)ld_scale);
+  int64_t M64 = (int64_t)R * P;
+  PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_czt_scaled: R*P too large");
+  const int M = (int)M64;
+  PTA_REQUIRE(variant == 0 || variant == 1, PTA_E_ARG, "pta_gwb_czt_scaled: variant %d (0 or 1)", variant);
+#define PTA_CZT_S(FASTV, FUSEV)                                                                                                     \
+  hipLaunchKernelGGL((k_gwb_czt<true, FASTV, FUSEV, true>), dim3(M), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), seed, r0, nullptr, \
+                     0, M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, scale, ld_scale)
+  if (variant == 0) {
+    if (rng_fast)
+      PTA_CZT_S(true, 15);
+    else
+      PTA_CZT_S(false, 15);
+  } else {
+    if (rng_fast)
+      PTA_CZT_S(true, 0);
+    else
+      PTA_CZT_S(false, 0);
+  }
+#undef PTA_CZT_S
   PTA_LAUNCH_CHECK();
   return PTA_OK;
 }

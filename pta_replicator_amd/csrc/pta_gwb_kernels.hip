@@ -132,11 +132,14 @@ __global__ void k_gwb_twiddle_sym(const double *__restrict__ sqrtC, int Nf, int 
   }
 }
 
-template <int NT, int MINW>
+// SCALED (pta_gwb_idft_rng_scaled): the drawn pair of bin k is multiplied by scale[(m / P) * ld_scale + k] (per-realisation spectrum
+// over the configured one, whose sqrt(C0) the twiddles carry) before the rotation; SCALED = false is the kernel without it.
+template <int NT, int MINW, bool SCALED>
 __global__ __launch_bounds__(256, MINW) void k_gwb_idft_sym_rng(uint64_t seed, uint64_t r0, int M, int P, int Nf,
                                                                 const double *__restrict__ Tsym,
                                                                 const double *__restrict__ rot, int npts,
-                                                                double *__restrict__ G0, int64_t ldg, int fast) {
+                                                                double *__restrict__ G0, int64_t ldg, int fast,
+                                                                const double *__restrict__ scale, int64_t ld_scale) {
   using C = pta_sym_cfg<NT>;
   extern __shared__ __attribute__((aligned(16))) double lds[];  // 2 x SLAB_PAD
   const int t = threadIdx.x, l = t & 63, wv = t >> 6;
@@ -170,6 +173,11 @@ __global__ __launch_bounds__(256, MINW) void k_gwb_idft_sym_rng(uint64_t seed, u
     for (int q = 0; q < C::NLD; ++q) regs[q] = src[(int64_t)ksn * (C::SLAB_PAD / 2) + q * 256];
     double re, im;
     pta_normal_pair(seed, real, strm, (uint32_t)(ks * 4 + kk + 1), re, im, fast);  // pair k <-> w[a,k] (red_noise.py:240)
+    if (SCALED) {  // bins past Kf (zero twiddles) read the last bin's entry
+      const double sc = scale[(int64_t)(mr / P) * ld_scale + min(ks * 4 + kk + 1, Kf)];
+      re *= sc;
+      im *= sc;
+    }
     const double2 cs = reinterpret_cast<const double2 *>(rot)[ks * 4 + kk];
     const double ar = re * cs.x - im * cs.y;  // rotated draw
     const double br = re * cs.y + im * cs.x;
@@ -236,6 +244,42 @@ extern "C" int pta_gwb_twiddle_sym(const double *sqrtC, int Nf, int npts, int i0
   return PTA_OK;
 }
 
+static int idft_rng_launch(uint64_t seed, uint64_t r0, int R, int P, int Nf, const double *Tsym, const double *rot, int npts, double *G0,
+                           int64_t ldg, int variant, int rng_fast, const double *scale, int64_t ld_scale, void *stream) {
+  const int M = R * P;
+  const int nt = sym_nt(variant);
+  rng_fast = rng_fast ? 1 : 0;
+  const int half = (npts + 1) >> 1;
+  const int nchunk = (half + nt * 16 - 1) / (nt * 16);
+  const size_t shmem = 2 * (size_t)sym_slab_pad(nt) * sizeof(double);
+  dim3 g(pta_cdiv(M, 64), nchunk);
+#define PTA_IDFT_X(NTV, MINWV, SCV)                                                                                                     \
+  do {                                                                                                                                 \
+    auto kern = k_gwb_idft_sym_rng<NTV, MINWV, SCV>;                                                                                  \
+    PTA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                          \
+    hipLaunchKernelGGL(kern, g, dim3(256), shmem, pta_stream(stream), seed, r0, M, P, Nf, Tsym, rot, npts, G0, ldg, rng_fast, scale, \
+                       ld_scale);                                                                                                      \
+  } while (0)
+  if (scale) {
+    if (nt == 19)
+      PTA_IDFT_X(19, 1, true);
+    else if (nt == 10)
+      PTA_IDFT_X(10, 2, true);
+    else
+      PTA_IDFT_X(7, 2, true);
+  } else {
+    if (nt == 19)
+      PTA_IDFT_X(19, 1, false);
+    else if (nt == 10)
+      PTA_IDFT_X(10, 2, false);
+    else
+      PTA_IDFT_X(7, 2, false);
+  }
+#undef PTA_IDFT_X
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
 extern "C" int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf, const double *Tsym, const double *rot,
                                 int npts, double *G0, int64_t ldg, int variant, int rng_fast, void *stream) {
   PTA_REQUIRE(Tsym && rot && G0, PTA_E_ARG, "pta_gwb_idft_rng: NULL argument");
@@ -243,28 +287,19 @@ extern "C" int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf
               "pta_gwb_idft_rng: R=%d P=%d Nf=%d npts=%d", R, P, Nf, npts);
   int64_t M64 = (int64_t)R * P;
   PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_idft_rng: R*P too large");
-  const int M = (int)M64;
-  const int nt = sym_nt(variant);
-  rng_fast = rng_fast ? 1 : 0;
-  const int half = (npts + 1) >> 1;
-  const int nchunk = (half + nt * 16 - 1) / (nt * 16);
-  const size_t shmem = 2 * (size_t)sym_slab_pad(nt) * sizeof(double);
-  dim3 g(pta_cdiv(M, 64), nchunk);
-  if (nt == 19) {
-    auto kern = k_gwb_idft_sym_rng<19, 1>;
-    PTA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kern, g, dim3(256), shmem, pta_stream(stream), seed, r0, M, P, Nf, Tsym, rot, npts, G0, ldg, rng_fast);
-  } else if (nt == 10) {
-    auto kern = k_gwb_idft_sym_rng<10, 2>;
-    PTA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kern, g, dim3(256), shmem, pta_stream(stream), seed, r0, M, P, Nf, Tsym, rot, npts, G0, ldg, rng_fast);
-  } else {
-    auto kern = k_gwb_idft_sym_rng<7, 2>;
-    PTA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kern, g, dim3(256), shmem, pta_stream(stream), seed, r0, M, P, Nf, Tsym, rot, npts, G0, ldg, rng_fast);
-  }
-  PTA_LAUNCH_CHECK();
-  return PTA_OK;
+  return idft_rng_launch(seed, r0, R, P, Nf, Tsym, rot, npts, G0, ldg, variant, rng_fast, nullptr, 0, stream);
+}
+
+extern "C" int pta_gwb_idft_rng_scaled(uint64_t seed, uint64_t r0, int R, int P, int Nf, const double *Tsym, const double *rot,
+                                       int npts, double *G0, int64_t ldg, int variant, int rng_fast, const double *scale,
+                                       int64_t ld_scale, void *stream) {
+  PTA_REQUIRE(Tsym && rot && G0 && scale, PTA_E_ARG, "pta_gwb_idft_rng_scaled: NULL argument");
+  PTA_REQUIRE(R > 0 && P > 0 && P < (1 << 24) && Nf >= 3 && npts > 0 && ldg >= npts, PTA_E_ARG,
+              "pta_gwb_idft_rng_scaled: R=%d P=%d Nf=%d npts=%d", R, P, Nf, npts);
+  PTA_REQUIRE(ld_scale >= Nf - 1, PTA_E_ARG, "pta_gwb_idft_rng_scaled: ld_scale=%lld < Nf - 1", (long long)ld_scale);
+  int64_t M64 = (int64_t)R * P;
+  PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_idft_rng_scaled: R*P too large");
+  return idft_rng_launch(seed, r0, R, P, Nf, Tsym, rot, npts, G0, ldg, variant, rng_fast, scale, ld_scale, stream);
 }
 
 // ---- mix: G[r] = Mchol . G0[r]  (red_noise.py:268, moved behind the DFT) -------------------------

@@ -1,0 +1,148 @@
+// Per-realisation hyperparameters in throughput mode (ReplicaEngine.generate(theta=...), generate_sampled):
+//   pta_hyper_uniform          theta drawn on chip from uniform boxes, keyed by (seed, realisation) like the residuals
+//   pta_gwb_spectrum_scale     hcf(f_k; A_r, gamma_r) / hcf0(f_k) per (realisation, bin): the factor the scaled GWB transforms apply
+//   pta_engine_rn_coef_hyper   k_engine_rn_coef with sqrt(prior) evaluated per (realisation, pulsar, frequency)
+//   pta_engine_generate_hyper  pta_engine_generate with any of the two stages above switched in
+// The fused synthesis kernel is unchanged: only its inputs (RN coefficients, mixed GWB grid series) depend on theta.
+#include "pta_common.h"
+#include "pta_rng.h"
+#include "pta_hyper.h"
+
+__global__ void k_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *__restrict__ lo,
+                                const double *__restrict__ hi, double *__restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)R * n_par) return;
+  const int j = (int)(idx % n_par);
+  const int64_t r = idx / n_par;
+  out[idx] = pta_hyper_draw(seed, r0 + (uint64_t)r, (uint32_t)j, lo[j], hi[j]);
+}
+
+extern "C" int pta_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *lo, const double *hi, double *out,
+                                 void *stream) {
+  PTA_REQUIRE(lo && hi && out, PTA_E_ARG, "pta_hyper_uniform: NULL argument");
+  PTA_REQUIRE(R > 0 && n_par > 0, PTA_E_ARG, "pta_hyper_uniform: R=%d n_par=%d", R, n_par);
+  const int64_t total = (int64_t)R * n_par;
+  PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_hyper_uniform: problem too large");
+  hipLaunchKernelGGL(k_hyper_uniform, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, n_par, lo, hi, out);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+__global__ void k_gwb_spectrum_scale(const double *__restrict__ f, const double *__restrict__ hcf0, int Nf, int R,
+                                     const double *__restrict__ log10_A, const double *__restrict__ gamma, int turnover, double f0,
+                                     double beta, double power, double *__restrict__ scale, int64_t ld_scale) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)R * Nf) return;
+  const int k = (int)(idx % Nf);
+  const int64_t r = idx / Nf;
+  scale[r * ld_scale + k] = pta_gwb_hcf(f[k], log10_A[r], gamma[r], turnover, f0, beta, power) / hcf0[k];
+}
+
+extern "C" int pta_gwb_spectrum_scale(const double *f, const double *hcf0, int Nf, int R, const double *log10_A, const double *gamma,
+                                      int turnover, double f0, double beta, double power, double *scale, int64_t ld_scale,
+                                      void *stream) {
+  PTA_REQUIRE(f && hcf0 && log10_A && gamma && scale, PTA_E_ARG, "pta_gwb_spectrum_scale: NULL argument");
+  PTA_REQUIRE(Nf >= 3 && R > 0 && ld_scale >= Nf, PTA_E_ARG, "pta_gwb_spectrum_scale: Nf=%d R=%d ld_scale=%lld", Nf, R,
+              (long long)ld_scale);
+  const int64_t total = (int64_t)R * Nf;
+  PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_gwb_spectrum_scale: problem too large");
+  hipLaunchKernelGGL(k_gwb_spectrum_scale, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), f, hcf0, Nf, R, log10_A, gamma,
+                     turnover ? 1 : 0, f0, beta, power, scale, ld_scale);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+// coef[(r*P + a)*K + c] = sqrt(prior(f_a[c/2]; A_ra, gamma_ra)) * z, z = deviate c of stream (RN, a): the draws of k_engine_rn_coef;
+// log10_A[r*P + a] = NaN takes amp_fixed[a*K + c] (pulsar not sampled, or without red noise: amp_fixed row zero)
+__global__ void k_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P, int K, const double *__restrict__ rn_f,
+                                       const double *__restrict__ rn_tspan, const double *__restrict__ log10_A,
+                                       const double *__restrict__ gamma, const double *__restrict__ amp_fixed,
+                                       double *__restrict__ coef, int fast) {
+  pta_rng_stage_tables();  // Box-Muller tables -> LDS (pta_rng.h)
+  __syncthreads();
+  int idx = blockIdx.x * blockDim.x + threadIdx.x;  // (r, a, pair)
+  int hp = K / 2;
+  int total = R * P * hp;
+  if (idx >= total) return;
+  int p = idx % hp, ra = idx / hp;
+  int a = ra % P, r = ra / P;
+  double z0, z1;
+  pta_normal_pair(seed, r0 + (uint64_t)r, pta_stream_id(PTA_STREAM_RN, (uint32_t)a), (uint32_t)p, z0, z1, fast);
+  const double lA = log10_A[ra];
+  double a0, a1;
+  if (isnan(lA)) {
+    a0 = amp_fixed[(int64_t)a * K + 2 * p];
+    a1 = amp_fixed[(int64_t)a * K + 2 * p + 1];
+  } else {
+    a0 = a1 = pta_rn_amp(rn_f[(int64_t)a * hp + p], rn_tspan[a], lA, gamma[ra]);  // sin and cos column share f (np.repeat(f, 2))
+  }
+  int64_t o = (int64_t)ra * K + 2 * p;
+  coef[o] = a0 * z0;
+  coef[o + 1] = a1 * z1;
+}
+
+extern "C" int pta_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P, int K, const double *rn_f, const double *rn_tspan,
+                                        const double *log10_A, const double *gamma, const double *amp_fixed, double *coef, int rng_fast,
+                                        void *stream) {
+  PTA_REQUIRE(rn_f && rn_tspan && log10_A && gamma && amp_fixed && coef, PTA_E_ARG, "pta_engine_rn_coef_hyper: NULL argument");
+  PTA_REQUIRE(R > 0 && P > 0 && K > 0 && (K % 2) == 0, PTA_E_ARG, "pta_engine_rn_coef_hyper: R=%d P=%d K=%d (K must be even)", R, P,
+              K);
+  int64_t total = (int64_t)R * P * (K / 2);
+  PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_engine_rn_coef_hyper: problem too large");
+  hipLaunchKernelGGL(k_engine_rn_coef_hyper, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, P, K, rn_f,
+                     rn_tspan, log10_A, gamma, amp_fixed, coef, rng_fast ? 1 : 0);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+extern "C" int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host,
+                                         const pta_engine_hyper *hyper_host, uint64_t seed, uint64_t r0, int R, double *out,
+                                         int64_t ld_out, void *stream) {
+  PTA_REQUIRE(plan_host && tables_host && hyper_host && out, PTA_E_ARG, "pta_engine_generate_hyper: NULL argument");
+  pta_engine_plan p = *plan_host;
+  const pta_engine_tables &tb = *tables_host;
+  const pta_engine_hyper &h = *hyper_host;
+  int rc;
+  if (p.gw_npts > 0) {
+    PTA_REQUIRE(tb.Mchol && tb.ws_G0 && tb.ws_G, PTA_E_ARG, "pta_engine_generate_hyper: GWB factor / workspace missing");
+    const double *scale = h.gw_scale;
+    if (!scale && h.gw_log10_A) {
+      PTA_REQUIRE(h.gw_gamma && h.gw_f && h.gw_hcf0 && h.ws_scale, PTA_E_ARG,
+                  "pta_engine_generate_hyper: gw_gamma / gw_f / gw_hcf0 / ws_scale missing");
+      rc = pta_gwb_spectrum_scale(h.gw_f, h.gw_hcf0, tb.gw_nf, R, h.gw_log10_A, h.gw_gamma, h.gw_turnover, h.gw_f0, h.gw_beta,
+                                  h.gw_power, h.ws_scale, h.ld_gw_scale, stream);
+      if (rc != PTA_OK) return rc;
+      scale = h.ws_scale;
+    }
+    if (tb.use_czt) {
+      PTA_REQUIRE(tb.czt_pre && tb.czt_FB && tb.czt_tw && tb.czt_post, PTA_E_ARG, "pta_engine_generate_hyper: chirp-z tables missing");
+      rc = scale ? pta_gwb_czt_scaled(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
+                                      tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, scale, h.ld_gw_scale, stream)
+                 : pta_gwb_czt(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
+                               tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, stream);
+    } else {
+      PTA_REQUIRE(tb.Tsym && tb.rot, PTA_E_ARG, "pta_engine_generate_hyper: DFT-GEMM tables missing");
+      rc = scale ? pta_gwb_idft_rng_scaled(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
+                                           p.rng_fast, scale, h.ld_gw_scale, stream)
+                 : pta_gwb_idft_rng(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
+                                    p.rng_fast, stream);
+    }
+    if (rc != PTA_OK) return rc;
+    rc = pta_gwb_mix(tb.Mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream);
+    if (rc != PTA_OK) return rc;
+    p.gw_G = tb.ws_G;
+  }
+  if (p.rn_k > 0) {
+    PTA_REQUIRE(tb.rn_amp && tb.ws_coef, PTA_E_ARG, "pta_engine_generate_hyper: red-noise amplitudes / workspace missing");
+    if (h.rn_log10_A) {
+      PTA_REQUIRE(h.rn_gamma && h.rn_f && h.rn_tspan, PTA_E_ARG, "pta_engine_generate_hyper: rn_gamma / rn_f / rn_tspan missing");
+      rc = pta_engine_rn_coef_hyper(seed, r0, R, p.n_psr, p.rn_k, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma, tb.rn_amp, tb.ws_coef,
+                                    p.rng_fast, stream);
+    } else {
+      rc = pta_engine_rn_coef(seed, r0, R, p.n_psr, p.rn_k, tb.rn_amp, tb.ws_coef, p.rng_fast, stream);
+    }
+    if (rc != PTA_OK) return rc;
+    p.rn_coef = tb.ws_coef;
+  }
+  return pta_engine_synth(&p, seed, r0, R, out, ld_out, stream);
+}

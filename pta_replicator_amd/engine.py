@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, device as dv
+from . import _hyper, _lib, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import white_noise as wn
@@ -33,6 +33,7 @@ from .constants import DAY_IN_SEC, YEAR_IN_SEC
 from .engine_td import TimeDomainMixin
 
 STREAM_GWB, STREAM_RN, STREAM_WN, STREAM_ECORR, STREAM_TD, STREAM_TDGW = 1, 2, 3, 4, 5, 6
+STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_id(7, 0), pair = parameter column (_hyper.columns)
 
 
 def stream_id(kind, pulsar):
@@ -381,15 +382,24 @@ class ReplicaEngine(TimeDomainMixin):
         self.plan.rng_fast, self.plan.synth_variant = int(self.rng_fast), int(self.synth_variant)
         return ws
 
-    def max_batch(self):
+    def max_batch(self, hyper=False):
         """realisations per launch sequence: the launch-grid limit of the mix / fused kernels (65536) and the workspace byte
-        budget (coef + G0 + G per realisation: 0.68 MB at 68 pulsars, so 8 GiB hold 12 600 realisations)."""
+        budget (coef + G0 + G per realisation: 0.68 MB at 68 pulsars, so 8 GiB hold 12 600 realisations; with per-realisation
+        theta (hyper=True) also the GWB spectrum-scale row, 8 Nf bytes)."""
         per_real = 8 * self.P * ((self.K if self.plan.rn_k else 0) + 2 * self.plan.gw_npts)
+        if hyper and self.plan.gw_npts:
+            per_real += 8 * self.grid["Nf"]
         return int(max(16, min(65536, self.workspace_bytes // max(per_real, 1))))
 
-    def generate(self, R, r0=0, out=None):
+    def generate(self, R, r0=0, out=None, theta=None):
         """out[R, n_toa] (device tensor, seconds): realisations r0 .. r0+R-1, every deviate drawn on chip: one call of
-        pta_engine_generate (coefficients -> GWB transform -> mix -> fused synthesis, all queued on the current stream)."""
+        pta_engine_generate (coefficients -> GWB transform -> mix -> fused synthesis, all queued on the current stream).
+
+        theta: per-realisation GWB / red-noise parameters of realisations r0 .. r0+R-1, a dict with any subset of
+        gwb_log10_A [R], gwb_gamma [R], rn_log10_A [R, P], rn_gamma [R, P] (NumPy arrays or tensors; pta_replicator_amd._hyper).
+        Keys not given keep their configured values; NaN in rn_log10_A = that pulsar as configured."""
+        if theta is not None:
+            return self._generate_hyper(R, r0, out, theta)
         if not self._prepared:
             self.prepare()
         if out is None:
@@ -422,6 +432,155 @@ class ReplicaEngine(TimeDomainMixin):
         if self.plan.gw_npts:
             self.plan.gw_G = ws["G"].data_ptr()
         return out
+
+    def _generate_hyper(self, R, r0, out, theta, check_values=True):
+        """generate() with per-realisation theta: pta_engine_generate_hyper per batch (spectrum scale -> scaled GWB transform -> mix
+        -> red-noise coefficients with sqrt(prior) per realisation -> the unchanged fused synthesis)."""
+        th = _hyper.check_theta(theta, R, self.P, self._gw, self._rn, self.gwb_mode, check_values)
+        if not self._prepared:
+            self.prepare()
+        dev = self._theta_device(th, R, mask_unconfigured=check_values)
+        if out is None:
+            out = dv.empty((R, self.n_toa))
+        step = self.max_batch(hyper=True)
+        ws = self.workspace(min(R, step))
+        hy = self._hyper_tables()
+        gw_theta = dev["gwb_log10_A"] is not None
+        if gw_theta and ("scale" not in ws or ws["scale"].shape[0] < ws["R"]):
+            ws["scale"] = dv.empty((ws["R"], self.grid["Nf"]))
+        grid_mode = self.gwb_mode == "grid" and self.plan.gw_npts
+        if grid_mode:
+            self._prepare_gw_grid_factor()
+            self.tdgw_plan.rng_fast = int(self.rng_fast)
+            self.tdgw_plan.z, self.tdgw_plan.ld_z, self.tdgw_plan.blk_zoff = None, 0, None
+        s = dv.stream_ptr()
+        P = self.P
+
+        def at(t, lo, per_row):
+            return None if t is None else ctypes.c_void_p(t.data_ptr() + 8 * lo * per_row)
+        for lo in range(0, R, step):
+            n = min(step, R - lo)
+            optr = ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0))
+            h = _lib.EngineHyper()
+            if self.plan.rn_k:
+                h.rn_f, h.rn_tspan = hy["rn_f"].data_ptr(), hy["rn_tspan"].data_ptr()
+                h.rn_log10_A, h.rn_gamma = at(dev["rn_log10_A"], lo, P), at(dev["rn_gamma"], lo, P)
+            if gw_theta:
+                h.ld_gw_scale, h.ws_scale = self.grid["Nf"], ws["scale"].data_ptr()
+                h.gw_log10_A, h.gw_gamma = at(dev["gwb_log10_A"], lo, 1), at(dev["gwb_gamma"], lo, 1)
+                h.gw_f, h.gw_hcf0 = hy["gw_f"].data_ptr(), hy["gw_hcf0"].data_ptr()
+                c = self._gw
+                h.gw_turnover, h.gw_f0, h.gw_beta, h.gw_power = int(bool(c["turnover"])), float(c["f0"]), float(c["beta"]), float(c["power"])
+            if not grid_mode:
+                _lib.call("pta_engine_generate_hyper", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), ctypes.byref(h),
+                          self.seed, r0 + lo, n, optr, out.stride(0), s)
+                continue
+            pl = _lib.EnginePlan.from_buffer_copy(self._plan_for_mode())    # grid mode: RN theta only (check_config)
+            if pl.rn_k:
+                if h.rn_log10_A:
+                    _lib.call("pta_engine_rn_coef_hyper", self.seed, r0 + lo, n, P, self.K, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma,
+                              dv.ptr(self.d_amp), dv.ptr(ws["coef"]), int(self.rng_fast), s)
+                else:
+                    _lib.call("pta_engine_rn_coef", self.seed, r0 + lo, n, P, self.K, dv.ptr(self.d_amp), dv.ptr(ws["coef"]), int(self.rng_fast), s)
+                pl.rn_coef = ws["coef"].data_ptr()
+            _lib.call("pta_td_trmm_rng", ctypes.byref(self.tdgw_plan), self.seed, r0 + lo, n * P, dv.ptr(ws["G0"]), pl.gw_npts, s)
+            _lib.call("pta_gwb_mix", dv.ptr(self.d_M), P, dv.ptr(ws["G0"]), n, pl.gw_npts, pl.gw_npts, dv.ptr(ws["G"]), int(self.mix_variant), s)
+            pl.gw_G = ws["G"].data_ptr()
+            _lib.call("pta_engine_synth", ctypes.byref(pl), self.seed, r0 + lo, n, optr, out.stride(0), s)
+        if self.plan.rn_k:
+            self.plan.rn_coef = ws["coef"].data_ptr()
+        if self.plan.gw_npts:
+            self.plan.gw_G = ws["G"].data_ptr()
+        self._theta_keep = dev   # the launches above read these buffers asynchronously
+        return out
+
+    def _theta_device(self, th, R, mask_unconfigured=True):
+        """validated theta -> contiguous float64 device tensors, keys not given filled with the configured values:
+        {gwb_log10_A, gwb_gamma: [R] or None, rn_log10_A, rn_gamma: [R, P] or None}.  Pulsars without red noise get NaN amplitudes
+        (mask_unconfigured=False: theta of sample_theta, which has them already)."""
+        def f64(x):
+            if hasattr(x, "data_ptr"):
+                return x.to(device=dv.require_gpu(), dtype=torch.float64).contiguous()
+            return dv.f64(np.ascontiguousarray(x, dtype=np.float64))
+        dev = dict.fromkeys(_hyper.KEYS)
+        if any(k in th for k in _hyper.GWB_KEYS):
+            for k, conf in (("gwb_log10_A", self._gw["A"]), ("gwb_gamma", self._gw["g"])):
+                dev[k] = f64(th[k]) if k in th else torch.full((R,), float(conf), dtype=torch.float64, device=dv.require_gpu())
+        if any(k in th for k in _hyper.RN_KEYS) and self.plan.rn_k:
+            conf = _hyper.configured_rn(self._rn)
+            for k, c in zip(_hyper.RN_KEYS, conf):
+                dev[k] = f64(th[k]) if k in th else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
+            none = self._hyper_tables()["rn_none"]
+            if mask_unconfigured and len(none):   # configured without red noise: keeps none (amp_fixed row is zero)
+                dev["rn_log10_A"] = dev["rn_log10_A"].clone()
+                dev["rn_log10_A"][:, none] = float("nan")
+        return dev
+
+    def _hyper_tables(self):
+        """theta-independent device tables of the hyper path, built once per prepare(): GWB frequency grid and configured hcf,
+        red-noise frequencies [P, K/2] and Tspan [P] (the values prepare() built the configured amplitudes from)."""
+        hy = getattr(self, "_hy", None)
+        if hy is not None and hy["plan"] is self.plan:
+            return hy
+        hy = {"plan": self.plan}
+        if self.plan.gw_npts:
+            c = self._gw
+            hy["gw_f"] = dv.f64(self.grid["f"])
+            if c["userSpec"] is None:
+                hy["gw_hcf0"] = dv.f64(rn.gwb_spectrum_hcf(self.grid["f"], c["A"], c["g"], c["turnover"], c["f0"], c["beta"], c["power"]))
+        if self.plan.rn_k:
+            hy["rn_f"] = dv.f64(np.stack(self.rn_freqs))
+            hy["rn_tspan"] = dv.f64(np.array([t.max() - t.min() for t in self.tdb_s]))
+            hy["rn_none"] = dv.i64(np.flatnonzero(np.isnan(_hyper.configured_rn(self._rn)[0])))
+        self._hy = hy
+        return hy
+
+    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None):
+        """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array.
+        Parameters left out keep their configured values.  No prepare() needed after a change."""
+        self._prior = _hyper.make_prior(self.P, gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma, rn_log10_A=rn_log10_A, rn_gamma=rn_gamma)
+        self._prior_dev = None   # device copy of the boxes, uploaded by the next sample_theta()
+        return self
+
+    def generate_sampled(self, R, r0=0, out=None):
+        """(out[R, n_toa], theta): realisations r0 .. r0+R-1 with theta drawn on chip from the set_hyper_prior() boxes
+        (pta_hyper_uniform: uniform u2 of stream (7, 0), pair = parameter column, so theta of realisation r is a pure function of
+        (seed, r) like its residuals).  theta: {key: device tensor} of the sampled keys, gwb_* [R], rn_* [R, P] (NaN for pulsars
+        without red noise) - the labels of the realisations."""
+        prior = getattr(self, "_prior", None)
+        if prior is None:
+            raise ValueError("generate_sampled: no prior (set_hyper_prior first)")
+        _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
+        if not self._prepared:
+            self.prepare()
+        theta = self.sample_theta(R, r0)
+        out = self._generate_hyper(R, r0, out, theta, check_values=False)
+        return out, theta
+
+    def sample_theta(self, R, r0=0):
+        """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses)."""
+        prior = getattr(self, "_prior", None)
+        if prior is None:
+            raise ValueError("sample_theta: no prior (set_hyper_prior first)")
+        if not self._prepared:
+            self.prepare()
+        if getattr(self, "_prior_dev", None) is None:
+            self._prior_dev = [dv.f64(x) for x in _hyper.prior_bounds(prior, self.P)]
+        d_lo, d_hi = self._prior_dev
+        table = dv.empty((R, _hyper.n_columns(self.P)))
+        _lib.call("pta_hyper_uniform", self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+        cols = _hyper.columns(self.P)
+        theta = {}
+        for k in _hyper.KEYS:
+            if k in prior:
+                c0, c1 = cols[k]
+                theta[k] = table[:, c0].contiguous() if k in _hyper.GWB_KEYS else table[:, c0:c1].contiguous()
+        if self.plan.rn_k:
+            none = self._hyper_tables()["rn_none"]
+            for k in _hyper.RN_KEYS:
+                if k in theta and len(none):   # pulsars configured without red noise keep none: their labels are NaN
+                    theta[k][:, none] = float("nan")
+        return theta
 
     def _plan_for_mode(self):
         """the plan generate() launches with: the shared one, or - wn_mode "single" - a private copy whose white-noise operands are
@@ -456,16 +615,19 @@ class ReplicaEngine(TimeDomainMixin):
             out.append(np.where((idx >> 4) & 1, z1[idx & ~16], z0[idx & ~16]))
         return out
 
-    def generate_per_signal(self, R, r0=0):
+    def generate_per_signal(self, R, r0=0, theta=None):
         """{'rn', 'gwb', 'wn', 'ecorr', 'det', 'total'}: the same realisations as generate(R, r0), one [R, n_toa] array per
         signal (the batched counterpart of the reference's per-signal ``added_signals_time`` entries).  Every deviate is a pure
         function of (seed, realisation, stream, index), so running the fused kernel once per signal with the other inputs
-        switched off reproduces exactly the deviates of the combined pass."""
+        switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate()."""
+        if theta is not None:
+            _hyper.check_theta(theta, R, self.P, self._gw, self._rn, self.gwb_mode)
         if not self._prepared:
             self.prepare()
-        if R > self.max_batch():
-            raise ValueError(f"generate_per_signal: at most {self.max_batch()} realisations per call (one workspace batch)")
-        total = self.generate(R, r0=r0)                      # also fills the workspace (coefficients, mixed GWB grid series)
+        step = self.max_batch(hyper=theta is not None)
+        if R > step:
+            raise ValueError(f"generate_per_signal: at most {step} realisations per call (one workspace batch)")
+        total = self.generate(R, r0=r0, theta=theta)         # also fills the workspace (coefficients, mixed GWB grid series)
         s = dv.stream_ptr()
         base = self._plan_for_mode()                         # wn_mode "single": the white-noise term is the one-deviate form, as in generate()
         keep = (self.plan.rn_k, self.plan.gw_npts, base.wn_a, base.wn_b, self.plan.ecorr_toa, self.plan.epoch_of, self.plan.det, base.wn_c)

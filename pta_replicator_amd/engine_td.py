@@ -335,7 +335,7 @@ class TimeDomainMixin:
         self._gw_grid_ready = True
 
     # ---------------------------------------------------------------- generate ------------------
-    def generate_td(self, R, r0=0, out=None, chunk=4096):
+    def generate_td(self, R, r0=0, out=None, chunk=4096, theta=None):
         """out[R, n_toa] (device, seconds): realisations r0 .. r0+R-1 of the dense path, deviates drawn on chip.
 
         The batch runs in chunks.  ``td_overlap = True`` (opt-in, "memory" draws only) prepares chunk c + 1 - its deviates
@@ -344,6 +344,9 @@ class TimeDomainMixin:
         and NOT the default (profiles/r04_bench_mid_round.json): 32.8 ms per 1024 realisations of the 68 x 5000 array in four pipelined
         chunks of 256 against 31.2 ms as one chunk - every chunk streams the 13.6 GB of factors again, and the preparation kernels are
         VALU work on the ALUs the matrix pipe shares, not idle time to fill."""
+        if theta is not None:
+            raise ValueError("generate_td: per-realisation theta is not supported in TD mode (the dense factors are built for one "
+                             "covariance); use generate(theta=...) or generate_sampled()")
         if not getattr(self, "_td_prepared", False) or not self._prepared:
             self.prepare_td()
         if out is None:

@@ -167,9 +167,9 @@ def gwb_time_grid(psrs, npts=600, howml=10):
     return dict(start=start, stop=stop, dur=dur, npts=npts, ut=ut, dt=dt, f=f, Nf=len(f), howml=howml)
 
 
-def gwb_spectrum(f, dur, howml, log10_amplitude, spectral_index, turnover=False, f0=1e-9, beta=1, power=1,
-                 userSpec=None):
-    """C(f) = hc(f)^2 / (96 pi^2 f^3) * dur * howml (red_noise.py:243-265)."""
+def gwb_spectrum_hcf(f, log10_amplitude, spectral_index, turnover=False, f0=1e-9, beta=1, power=1, userSpec=None):
+    """characteristic strain hc(f) of the GWB spectrum (red_noise.py:243-263); pta_hyper.h pta_gwb_hcf is the device twin of the
+    power-law branch."""
     if userSpec is None:
         Amp = 10 ** log10_amplitude
         gam = spectral_index
@@ -189,6 +189,13 @@ def gwb_spectrum(f, dur, howml, log10_amplitude, spectral_index, turnover=False,
         # silently return garbage for an unsorted spectrum - so do the same
         order = np.argsort(freqs, kind="mergesort")
         hcf = 10.0 ** np.interp(np.log10(f), np.log10(freqs[order]), np.log10(userSpec[order, 1]))
+    return hcf
+
+
+def gwb_spectrum(f, dur, howml, log10_amplitude, spectral_index, turnover=False, f0=1e-9, beta=1, power=1,
+                 userSpec=None):
+    """C(f) = hc(f)^2 / (96 pi^2 f^3) * dur * howml (red_noise.py:243-265)."""
+    hcf = gwb_spectrum_hcf(f, log10_amplitude, spectral_index, turnover, f0, beta, power, userSpec)
     return 1 / 96 / np.pi ** 2 * hcf ** 2 / f ** 3 * dur * howml
 
 
