@@ -564,6 +564,22 @@ int pta_td_trmm_rng(const pta_td_plan *plan_host, uint64_t seed, uint64_t r0, in
 int pta_tm_project(const double *Qt, const double *Mt, int64_t ld, int m, const int32_t *psr_off, int P, double *rows, int64_t ld_rows, int R,
                    void *stream);
 
+/* ---------------------------------------------------------------- optimal statistic (ABI 8, additive) ---- */
+/* Per-realisation half of the Hellings-Downs cross-correlation optimal statistic (the realisation-independent half - W_a, Z_a, den_ab
+ * and the ORF weights - is host NumPy: pta_replicator_amd/optimal_statistic.py).  The reference has no counterpart: its realisations
+ * leave as par/tim files for a CPU analysis code.
+ * Projection:  Y[r * ld_y + a * C + c] = sum_i Wt[c * ldw + psr_off[a] + i] * rows[r * ld_rows + psr_off[a] + i]  for r < R, a < P, c < C,
+ * i < psr_off[a + 1] - psr_off[a] (ragged pulsars; psr_off [P + 1] device int32); C = 2 n_f in 1..64, ld_y >= P * C.  fp64 MFMA, one
+ * workgroup per pulsar x 64 or 128 realisations; every residual is read once.  A realisation's Y is bit-identical whatever R, its
+ * row in the batch or the launch geometry (fixed reduction order over TOAs, no split across workgroups).                          */
+int pta_os_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R, double *Y,
+                   int64_t ld_y, void *stream);
+/* Pair reduction:  num_p = Y[r, pair_a[p], :] . Y[r, pair_b[p], :]  (p < n_pairs, pairs a < b), A2[r * ld_a2 + o] = sum_p wt[o * n_pairs + p] num_p
+ * for o < n_orf <= 8 (wt = Gamma_o / sum Gamma_o^2 den).  pair_out (optional, NULL = none): pair_out[r * ld_pair + p] = num_p / den[p], or
+ * num_p when den is NULL.  One workgroup per realisation with its Y row in LDS (P * C <= 8192 doubles); fixed summation order. */
+int pta_os_pairs(const double *Y, int64_t ld_y, int P, int C, int R, const int32_t *pair_a, const int32_t *pair_b, int n_pairs, const double *wt,
+                 int n_orf, double *A2, int64_t ld_a2, const double *den, double *pair_out, int64_t ld_pair, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays
  * back to rank 0"): realisations are sharded by contiguous row ranges - rank r owns rows [a_r, b_r) of the [total_rows x n_cols]

@@ -131,7 +131,9 @@ _SIGNATURES = {
     "pta_td_trmm": (c_int, [_P, c_int64, c_int, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P]),
     "pta_td_trmm_rng": (c_int, [POINTER(TdPlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_tm_project": (c_int, [_P, _P, c_int64, c_int, _P, c_int, _P, c_int64, c_int, _P]),
-    "pta_gather_rank0": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
+    "pta_os_project": (c_int, [_P, c_int64, c_int, _P, c_int, _P, c_int64, c_int, _P, c_int64, _P]),
+    "pta_os_pairs": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int64, _P, _P, c_int64, _P]),
+    "pta_gather_rank0":(c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
     "pta_dgemm": (c_int, [c_int, c_int, c_int, c_int, c_double, _P, c_int64, c_int64, _P, c_int64, c_double, _P, c_int64,
                           c_int, c_int, c_int64, c_int64, c_int64, c_int, _P]),
     "pta_microbench": (c_int, [c_int, c_int64, c_int, c_int, POINTER(c_double)]),

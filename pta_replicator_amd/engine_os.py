@@ -1,0 +1,168 @@
+"""Cross-correlation optimal statistic (OS) of the ReplicaEngine's realisations, per realisation, on the device.
+
+``prepare_optimal_statistic()`` builds the realisation-independent operands on the host from the noise model ``prepare()`` holds
+(pta_replicator_amd/optimal_statistic.py: W_a = S^1/2 F^T P_a^-1, Z_a, den_ab, the ORF weights) and uploads them once;
+``optimal_statistic(rows)`` then costs two launches per batch:
+
+    pta_os_project   Y[r, a, :] = W_a r_a             every residual read once (fp64 MFMA)
+    pta_os_pairs     A2[r, o] = sum_{a<b} G_o,ab Y_ra . Y_rb / sum G_o^2 den      one workgroup per realisation
+
+and ``generate_os(R)`` runs generate / generate_td / generate(theta=...) chunk by chunk into one reused buffer with the OS behind
+each chunk, keeping only the statistics.  A realisation's statistic is bit-identical whatever chunk or row it is computed in.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, device as dv
+from . import optimal_statistic as ost
+from ._position import ra_dec
+
+
+class OptimalStatisticMixin:
+    def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None):
+        """W, Z, den and ORF weights of the array under the configured noise model (white noise + ECORR + red noise, optionally the
+        GWB auto-term), uploaded once.
+
+        components: n_f = 1 .. 32 frequencies k / T (T = span of the whole array); gamma: spectral index of the unit spectrum;
+        orfs: names "hd", "monopole", "dipole" or [P, P] arrays (at most 8); timing_model: "spin", "astrometric" or None;
+        gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False = off."""
+        if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
+            raise ValueError(f"components={components!r}: an integer 1 .. 32 (2 n_f <= 64 columns)")
+        if timing_model not in ("spin", "astrometric", None):
+            raise ValueError(f"timing_model={timing_model!r} must be 'spin', 'astrometric' or None")
+        orfs = tuple(orfs) if not isinstance(orfs, str) else (orfs,)
+        if not 1 <= len(orfs) <= 8:
+            raise ValueError(f"{len(orfs)} ORFs: one call evaluates 1 .. 8")
+        for o in orfs:
+            if isinstance(o, str) and o not in ost.ORF_NAMES:
+                raise ValueError(f"unknown ORF {o!r}: expected one of {ost.ORF_NAMES} or a [P, P] array")
+            if not isinstance(o, str) and np.shape(o) != (self.P, self.P):
+                raise ValueError(f"a user ORF must be a finite [{self.P}, {self.P}] array, got shape {np.shape(o)}")
+        if self.P < 2:
+            raise ValueError("the cross-correlation OS needs at least two pulsars")
+        if self._wn is None:
+            raise ValueError("the OS needs measurement noise (set_white_noise): without it the noise covariance is singular")
+        if gwb_auto is None:
+            amp2 = 10.0 ** (2 * float(self._gw["A"])) if self._gw is not None else 0.0
+        elif gwb_auto is False:
+            amp2 = 0.0
+        elif isinstance(gwb_auto, (bool, np.bool_)):
+            raise ValueError("gwb_auto: None, a log10 amplitude, or False")
+        else:
+            amp2 = 10.0 ** (2 * float(gwb_auto))
+        if not self._prepared:
+            self.prepare()
+        from .simulate import timing_design_matrix
+        P = self.P
+        toas = [m * 86400.0 for m in self.mjd]
+        wa, wb = self.d_wn_a.cpu().numpy(), self.d_wn_b.cpu().numpy()
+        sigma2 = [wa[self.off[a]:self.off[a + 1]] ** 2 + wb[self.off[a]:self.off[a + 1]] ** 2 for a in range(P)]
+        epoch_of = ecorr = F_rn = phi_rn = None
+        if self._ec is not None:
+            epoch_of, ecorr = self.epoch_of, self.ecorrvec
+        if self.plan.rn_k:
+            F_rn = [self._rn_basis_host(a) for a in range(P)]
+            phi_rn = [self.rn_amp[a] ** 2 for a in range(P)]
+        M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
+        pos = []
+        for p in self.psrs:
+            ra, dec = ra_dec(p, default=(0.0, 0.0))
+            pos.append([np.cos(dec) * np.cos(ra), np.cos(dec) * np.sin(ra), np.sin(dec)])
+        plan = ost.prepare(toas, sigma2, np.array(pos), components=int(components), gamma=float(gamma), orfs=orfs, epoch_of=epoch_of,
+                           ecorr=ecorr, F_rn=F_rn, phi_rn=phi_rn, gw_amp2=amp2, M=M)
+        self._os = dict(plan=plan, engine_plan=self.plan, C=plan.C, n_orf=len(plan.names), names=plan.names,
+                        Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), pa=dv.i32(plan.pair_a), pb=dv.i32(plan.pair_b),
+                        wt=dv.f64(plan.weights), den=dv.f64(plan.den), sigma=dv.f64(plan.sigma), sigma_pair=dv.f64(plan.sigma_pair),
+                        zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None)
+        return self
+
+    def _rn_basis_host(self, a):
+        """the red-noise basis [N_a, K] prepare() put on the device (pta_rn_basis: sin / cos of 2 pi f t per mode, t = TDB seconds;
+        libstempo convention: cos / sin of t - t[0])."""
+        t = self.tdb_s[a]
+        f = self.rn_freqs[a]
+        lib_conv = self._rn["libstempo"]
+        arg = 2 * np.pi * ((t - t[0]) if lib_conv else t)[:, None] * f[None, :]
+        F = np.empty((len(t), 2 * len(f)))
+        F[:, 0::2], F[:, 1::2] = (np.cos(arg), np.sin(arg)) if lib_conv else (np.sin(arg), np.cos(arg))
+        return F
+
+    def _os_state(self, what):
+        st = getattr(self, "_os", None)
+        if st is None:
+            raise ValueError(f"{what}: the optimal statistic is not prepared (prepare_optimal_statistic first)")
+        if not self._prepared or st["engine_plan"] is not self.plan:
+            raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_optimal_statistic(): call it again")
+        return st
+
+    def optimal_statistic(self, rows, pairs=False):
+        """OS of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
+        generate_td, generate_sampled, or the caller's own residuals).  Returns a dict of device tensors: A2 [R, n_orf], snr [R, n_orf],
+        sigma [n_orf], names (list); with pairs=True also rho [R, n_pairs] (= num / den), sigma_pair [n_pairs], zeta [n_pairs] and
+        pairs [n_pairs, 2] (a < b, row-major upper triangle)."""
+        st = self._os_state("optimal_statistic")
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
+            raise ValueError("rows must be a float64 device tensor")
+        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
+        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
+            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
+        R = int(rows.shape[0])
+        out = {"A2": dv.empty((R, st["n_orf"])), "rho": dv.empty((R, len(st["plan"].den))) if pairs else None}
+        self._os_launch(rows, R, out["A2"], out["rho"])
+        return self._os_result(st, out["A2"], out["rho"])
+
+    def _os_result(self, st, A2, rho):
+        res = {"A2": A2, "snr": A2 / st["sigma"], "sigma": st["sigma"], "names": list(st["names"])}
+        if rho is not None:
+            res.update(rho=rho, sigma_pair=st["sigma_pair"], zeta=st["zeta"], pairs=st["pairs"])
+        return res
+
+    def _os_launch(self, rows, R, A2, rho):
+        """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream"""
+        st = self._os
+        P, C = self.P, st["C"]
+        if st["Y"] is None or st["Y"].shape[0] < R:
+            st["Y"] = dv.empty((R, P * C))
+        Y = st["Y"]
+        s = dv.stream_ptr()
+        _lib.call("pta_os_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), R,
+                  dv.ptr(Y), P * C, s)
+        npairs = len(st["plan"].den)
+        _lib.call("pta_os_pairs", dv.ptr(Y), P * C, P, C, R, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(st["wt"]), st["n_orf"],
+                  ctypes.c_void_p(A2.data_ptr()), A2.stride(0), dv.ptr(st["den"]) if rho is not None else None,
+                  ctypes.c_void_p(rho.data_ptr()) if rho is not None else None, rho.stride(0) if rho is not None else 0, s)
+
+    def generate_os(self, R, r0=0, theta=None, td=False, chunk=1024, pairs=False):
+        """OS of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
+        td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations, e.g. sample_theta(R, r0)); only
+        the statistics are kept.  Same results as optimal_statistic(generate(R, r0, ...)), bit for bit, whatever the chunk.  The chunk
+        is cut so that the buffer stays within workspace_bytes."""
+        st = self._os_state("generate_os")
+        R, r0, chunk = int(R), int(r0), int(chunk)
+        if R < 1 or chunk < 1 or r0 < 0:
+            raise ValueError(f"generate_os: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
+        if td and theta is not None:
+            raise ValueError("generate_os: per-realisation theta is not supported in TD mode (see generate_td)")
+        per_real = 8 * (self.n_toa + self.P * st["C"])
+        chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
+        buf = getattr(self, "_os_rows", None)
+        if buf is None or buf.shape[0] < chunk:
+            self._os_rows = None
+            buf = self._os_rows = dv.empty((chunk, self.n_toa))
+        A2 = dv.empty((R, st["n_orf"]))
+        rho = dv.empty((R, len(st["plan"].den))) if pairs else None
+        for lo in range(0, R, chunk):
+            n = min(chunk, R - lo)
+            rows = buf[:n]
+            if td:
+                self.generate_td(n, r0=r0 + lo, out=rows)
+            elif theta is not None:
+                self.generate(n, r0=r0 + lo, out=rows, theta={k: v[lo:lo + n] for k, v in theta.items()})
+            else:
+                self.generate(n, r0=r0 + lo, out=rows)
+            self._os_state("generate_os")     # generate_td / generate may have (re)prepared the engine
+            self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
+        return self._os_result(st, A2, rho)
