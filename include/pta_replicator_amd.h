@@ -49,7 +49,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * (red_noise.py:119,127,176,238-240; white_noise.py:80,105-109,155,182); on the device every
  * deviate is Philox-4x32-10(key = seed, counter = (pair, stream, realisation)) + Box-Muller.
  * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor),
- * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform). */
+ * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform),
+ * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -444,6 +445,41 @@ typedef struct {
  * configured in the plan.                                                                                                 */
 int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, const pta_engine_hyper *hyper_host,
                               uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out, void *stream);
+
+/* ---------------------------------------------------------------- one CW source per realisation (ABI 8, additive) */
+/* out[r * n_par + j] = lo[j] + (hi[j] - lo[j]) u (one fma), u = uniform u2 of pair j of stream (CW, 0), realisation r0 + r.  Columns
+ * j: 0 cos_gwtheta, 1 gwphi, 2 log10_mc [Msun], 3 log10_fgw [Hz], 4 log10 h or log10 dist [Mpc], 5 phase0, 6 psi, 7 cos_inc,
+ * 8 + a pdist of pulsar a [kpc].  lo / hi: device [n_par].                                                               */
+int pta_cw_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *lo, const double *hi, double *out, void *stream);
+
+/* The source of every realisation of a batch (deterministic.py:13-185 with one source per realisation).  Device pointers.     */
+#define PTA_CW_ENGINE_NPAR 16
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t mode;               /* 0 evolve, 1 phase_approx, 2 monochromatic (add_cgw's evolve / phase_approx flags) */
+  int32_t psr_term;           /* 0 / 1 */
+  int32_t amp_is_h;           /* 1: column 4 of src is log10 h (strain); 0: log10 dist [Mpc] */
+  int32_t has_pdist;          /* 1: columns 8 .. 8 + P - 1 of src hold pdist [kpc] per realisation; 0: pdist[] below */
+  double tref;                /* [s] */
+  const double *phat;         /* [n_psr x 3] pulsar unit vectors (ptheta = pi/2 - dec, pphi = ra) */
+  const double *pdist;        /* [n_psr] pulsar distances [kpc] (has_pdist = 0) */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *src;          /* [R x ld_src] source columns of realisation r0 + r (the layout of pta_cw_uniform) */
+  int64_t ld_src;             /* >= 8 (+ n_psr with has_pdist) */
+  double *par;                /* [R x n_psr x PTA_CW_ENGINE_NPAR] scalar table written by pta_engine_cw_params */
+} pta_cw_engine;
+
+/* par[(r * P + a) * PTA_CW_ENGINE_NPAR + k] from src row r and pulsar a: w0, orbital phase0, Phi = 1 / (32 (mc w0)^(5/3)), fac1,
+ * fac3 w0^(-1/3), incfac1, incfac2, cos 2psi, sin 2psi, F+, Fx, pd (1 - cos mu) [s], and for phase_approx omega_p, its phase offset
+ * and fac3 omega_p^(-1/3).  One thread per (r, a).                                                                       */
+int pta_engine_cw_params(const pta_cw_engine *cw_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= CW residual of realisation r at TOA i for r < R (accumulate = 1 adds, 0 writes), over the plan's TOA
+ * tiles (tile_psr / tile_start / tile_count, n_tiles, n_psr, n_toa; nothing else of the plan is read).  The evolving phase uses
+ * phase0 - Phi d (5 + d (10 + d (10 + d (5 + d)))), d = expm1(log1p(-fac1 t) / 8): the reference's expression without its
+ * cancellation.  A TOA whose contribution is not finite (after the merger) gets 0 (deterministic.py:435,556).  No atomics.  */
+int pta_engine_cw_add(const pta_engine_plan *plan_host, const pta_cw_engine *cw_host, int R, double *out, int64_t ld_out, int accumulate,
+                      void *stream);
 
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,

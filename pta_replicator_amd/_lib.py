@@ -70,6 +70,14 @@ class EngineHyper(ctypes.Structure):
     ]
 
 
+class CwEngine(ctypes.Structure):
+    """pta_cw_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("mode", c_int32), ("psr_term", c_int32), ("amp_is_h", c_int32), ("has_pdist", c_int32), ("tref", c_double),
+        ("phat", _P), ("pdist", _P), ("toa_s", _P), ("src", _P), ("ld_src", c_int64), ("par", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -123,6 +131,9 @@ _SIGNATURES = {
     "pta_engine_rn_coef_hyper": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "pta_engine_generate_hyper": (c_int, [POINTER(EnginePlan), POINTER(EngineTables), POINTER(EngineHyper), c_uint64, c_uint64, c_int, _P,
                                           c_int64, _P]),
+    "pta_cw_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P]),
+    "pta_engine_cw_params": (c_int, [POINTER(CwEngine), c_int, _P]),
+    "pta_engine_cw_add": (c_int, [POINTER(EnginePlan), POINTER(CwEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
@@ -143,6 +154,7 @@ _SIGNATURES = {
 
 ENGINE_TILE = 256   # PTA_ENGINE_TILE
 ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX
+CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 TD_STRIP = 256      # PTA_TD_STRIP
 POTRF_ZERO_UPPER, POTRF_NO_LOOKAHEAD, POTRF_SUBSTITUTION, POTRF_VALU, POTRF_REG_STAGING, POTRF_LOCKSTEP, POTRF_DIAG_AHEAD, POTRF_DIAG64 = 1, 2, 4, 8, 32, 64, 128, 16
 POTRF_EPI1 = 0x100000

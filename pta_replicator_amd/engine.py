@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _hyper, _lib, device as dv
+from . import _cw, _hyper, _lib, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import white_noise as wn
@@ -35,6 +35,7 @@ from .engine_td import TimeDomainMixin
 
 STREAM_GWB, STREAM_RN, STREAM_WN, STREAM_ECORR, STREAM_TD, STREAM_TDGW = 1, 2, 3, 4, 5, 6
 STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_id(7, 0), pair = parameter column (_hyper.columns)
+STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream_id(8, 0), pair = label column (_cw.COLUMNS)
 
 
 def stream_id(kind, pulsar):
@@ -64,6 +65,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         self._gw = None
         self._det = None
         self._delays = None
+        self._cw = None      # one CW source per realisation (set_cw), parameters from theta / set_cw_prior
         self._prepared = False
         # frequency -> time transform of the GWB in throughput mode: "auto" = chirp-z FFT when it fits, else the MFMA DFT-GEMM
         self.gwb_transform = "auto"
@@ -115,6 +117,14 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         """a continuous-wave source shared by all pulsars (deterministic.py:13-185); same keyword arguments."""
         self._det = (self._det or []) + [kw]
         self._prepared = False
+
+    def set_cw(self, psrTerm=True, evolve=True, phase_approx=False, tref=0.0, pdist=1.0):
+        """one continuous-wave source PER REALISATION, its parameters given by the cw_* keys of theta (generate, generate_per_signal,
+        generate_td, generate_os) or drawn from set_cw_prior() (generate_sampled).  The flags have add_cgw's meaning
+        (deterministic.py:13-48); tref [s]; pdist [kpc], a scalar or one value per pulsar (theta's cw_pdist [R, P] overrides it).
+        Adds nothing by itself; fixed sources of add_cgw / add_delays stay as they are, on top of it.  No prepare() needed."""
+        self._cw = _cw.make_config(self.P, psrTerm, evolve, phase_approx, tref, pdist)
+        return self
 
     def add_delays(self, delays):
         """any precomputed deterministic delay (seconds; one array per pulsar or one concatenated array), e.g. the
@@ -383,13 +393,16 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         self.plan.rng_fast, self.plan.synth_variant = int(self.rng_fast), int(self.synth_variant)
         return ws
 
-    def max_batch(self, hyper=False):
+    def max_batch(self, hyper=False, cw=False):
         """realisations per launch sequence: the launch-grid limit of the mix / fused kernels (65536) and the workspace byte
         budget (coef + G0 + G per realisation: 0.68 MB at 68 pulsars, so 8 GiB hold 12 600 realisations; with per-realisation
-        theta (hyper=True) also the GWB spectrum-scale row, 8 Nf bytes)."""
+        theta (hyper=True) also the GWB spectrum-scale row, 8 Nf bytes; with CW theta (cw=True) also the CW source row and the
+        [P, 16] scalar table of pta_engine_cw_params)."""
         per_real = 8 * self.P * ((self.K if self.plan.rn_k else 0) + 2 * self.plan.gw_npts)
         if hyper and self.plan.gw_npts:
             per_real += 8 * self.grid["Nf"]
+        if cw:
+            per_real += 8 * (self.P * _lib.CW_ENGINE_NPAR + _cw.N_SRC + self.P)
         return int(max(16, min(65536, self.workspace_bytes // max(per_real, 1))))
 
     def generate(self, R, r0=0, out=None, theta=None):
@@ -398,9 +411,18 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
 
         theta: per-realisation GWB / red-noise parameters of realisations r0 .. r0+R-1, a dict with any subset of
         gwb_log10_A [R], gwb_gamma [R], rn_log10_A [R, P], rn_gamma [R, P] (NumPy arrays or tensors; pta_replicator_amd._hyper).
-        Keys not given keep their configured values; NaN in rn_log10_A = that pulsar as configured."""
+        Keys not given keep their configured values; NaN in rn_log10_A = that pulsar as configured.  With set_cw(), theta may also
+        hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch."""
         if theta is not None:
-            return self._generate_hyper(R, r0, out, theta)
+            rest, cw = _cw.split(theta)
+            if not cw:
+                return self._generate_hyper(R, r0, out, theta)
+            cw = _cw.check_theta(cw, R, self.P, self._cw)
+            if rest:
+                out = self._generate_hyper(R, r0, out, rest, cw=True)
+            else:
+                out = self.generate(R, r0, out)
+            return self._cw_apply(cw, R, out)
         if not self._prepared:
             self.prepare()
         if out is None:
@@ -434,7 +456,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
             self.plan.gw_G = ws["G"].data_ptr()
         return out
 
-    def _generate_hyper(self, R, r0, out, theta, check_values=True):
+    def _generate_hyper(self, R, r0, out, theta, check_values=True, cw=False):
         """generate() with per-realisation theta: pta_engine_generate_hyper per batch (spectrum scale -> scaled GWB transform -> mix
         -> red-noise coefficients with sqrt(prior) per realisation -> the unchanged fused synthesis)."""
         th = _hyper.check_theta(theta, R, self.P, self._gw, self._rn, self.gwb_mode, check_values)
@@ -443,7 +465,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         dev = self._theta_device(th, R, mask_unconfigured=check_values)
         if out is None:
             out = dv.empty((R, self.n_toa))
-        step = self.max_batch(hyper=True)
+        step = self.max_batch(hyper=True, cw=cw)
         ws = self.workspace(min(R, step))
         hy = self._hyper_tables()
         gw_theta = dev["gwb_log10_A"] is not None
@@ -536,6 +558,65 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         self._hy = hy
         return hy
 
+    def _cw_tables(self):
+        """theta-independent device tables of the CW path, built once per prepare() / set_cw(): pulsar unit vectors [P, 3] (the
+        reference's expression, deterministic.py:88) and the configured pulsar distances [P] (kpc)."""
+        tb = getattr(self, "_cwt", None)
+        if tb is not None and tb["plan"] is self.plan and tb["conf"] is self._cw:
+            return tb
+        phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
+        tb = {"plan": self.plan, "conf": self._cw, "phat": dv.f64(phat), "pdist": dv.f64(self._cw["pdist"])}
+        self._cwt = tb
+        return tb
+
+    def _cw_apply(self, cw, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the CW term of every row for validated CW theta `cw` (row r = the source of realisation r0 + r): the
+        source table -> pta_engine_cw_params -> pta_engine_cw_add, in batches of max_batch(hyper=True, cw=True)."""
+        if not self._prepared:
+            self.prepare()
+        dev = dv.require_gpu()
+        P = self.P
+
+        def col(x, shape):
+            t = x.to(device=dev, dtype=torch.float64) if hasattr(x, "data_ptr") else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev)
+            return t.reshape(shape)
+        amp = _cw.amp_key(cw)
+        cols = [col(cw[amp if c == "amp" else "cw_" + c], (R, 1)) for c in _cw.COLUMNS]
+        has_pd = _cw.PDIST_KEY in cw
+        if has_pd:
+            cols.append(col(cw[_cw.PDIST_KEY], (R, P)))
+        src = torch.cat(cols, dim=1).contiguous()
+        conf, tb = self._cw, self._cw_tables()
+        step = min(R, self.max_batch(hyper=True, cw=True))
+        par = getattr(self, "_cw_par", None)
+        if par is None or par.shape[0] < step:
+            self._cw_par = None
+            par = self._cw_par = dv.empty((step, P, _lib.CW_ENGINE_NPAR))
+        c = _lib.CwEngine()
+        c.n_psr, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = P, _cw.mode(conf), int(conf["psrTerm"]), int(amp == "cw_log10_h"), int(has_pd)
+        c.tref, c.phat, c.pdist, c.toa_s = conf["tref"], tb["phat"].data_ptr(), tb["pdist"].data_ptr(), self.d_toa_s.data_ptr()
+        c.ld_src, c.par = src.stride(0), par.data_ptr()
+        s = dv.stream_ptr()
+        for lo in range(0, R, step):
+            n = min(step, R - lo)
+            c.src = src.data_ptr() + 8 * lo * src.stride(0)
+            _lib.call("pta_engine_cw_params", ctypes.byref(c), n, s)
+            _lib.call("pta_engine_cw_add", ctypes.byref(self.plan), ctypes.byref(c), n, ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0)),
+                      out.stride(0), 1 if accumulate else 0, s)
+        self._cw_keep = src   # the launches above read it asynchronously
+        return out
+
+    def set_cw_prior(self, log10_mc=None, log10_fgw=None, log10_h=None, log10_dist=None, cos_gwtheta=None, gwphi=None, phase0=None,
+                     psi=None, cos_inc=None, pdist=None):
+        """uniform boxes (lo, hi) of the per-realisation CW source of generate_sampled() (set_cw configures it).  Required: log10_mc
+        [Msun], log10_fgw [Hz] and exactly one of log10_h / log10_dist [Mpc].  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), phase0
+        (0, 2 pi), psi (0, pi), cos_inc (-1, 1) (isotropic sky and orientation).  pdist [kpc]: (lo, hi) or [P, 2]; left out = set_cw's
+        pdist.  Drawn from stream (8, 0), pair = label column (_cw.COLUMNS), independently of set_hyper_prior's parameters."""
+        self._cw_prior = _cw.make_prior(self.P, log10_mc=log10_mc, log10_fgw=log10_fgw, log10_h=log10_h, log10_dist=log10_dist,
+                                        cos_gwtheta=cos_gwtheta, gwphi=gwphi, phase0=phase0, psi=psi, cos_inc=cos_inc, pdist=pdist)
+        self._cw_prior_dev = None
+        return self
+
     def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None):
         """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array.
         Parameters left out keep their configured values.  No prepare() needed after a change."""
@@ -548,30 +629,48 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         (pta_hyper_uniform: uniform u2 of stream (7, 0), pair = parameter column, so theta of realisation r is a pure function of
         (seed, r) like its residuals).  theta: {key: device tensor} of the sampled keys, gwb_* [R], rn_* [R, P] (NaN for pulsars
         without red noise) - the labels of the realisations."""
-        prior = getattr(self, "_prior", None)
-        if prior is None:
-            raise ValueError("generate_sampled: no prior (set_hyper_prior first)")
-        _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
+        prior, cw_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None)
+        if prior is None and cw_prior is None:
+            raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior first)")
+        if prior is not None:
+            _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
+        if cw_prior is not None and self._cw is None:
+            raise ValueError("generate_sampled: no per-realisation CW configured (set_cw)")
         if not self._prepared:
             self.prepare()
         theta = self.sample_theta(R, r0)
-        out = self._generate_hyper(R, r0, out, theta, check_values=False)
+        rest, cw = _cw.split(theta)
+        if rest:
+            out = self._generate_hyper(R, r0, out, rest, check_values=False, cw=bool(cw))
+        else:
+            out = self.generate(R, r0, out)
+        if cw:
+            out = self._cw_apply(_cw.check_theta(cw, R, self.P, self._cw, check_values=False), R, out)
         return out, theta
 
     def sample_theta(self, R, r0=0):
         """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses)."""
-        prior = getattr(self, "_prior", None)
-        if prior is None:
-            raise ValueError("sample_theta: no prior (set_hyper_prior first)")
+        prior, cw_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None)
+        if prior is None and cw_prior is None:
+            raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior first)")
         if not self._prepared:
             self.prepare()
+        theta = {}
+        if cw_prior is not None:   # stream (8, 0): pair j = label column j, whatever else is sampled
+            if getattr(self, "_cw_prior_dev", None) is None:
+                self._cw_prior_dev = [dv.f64(x) for x in _cw.prior_bounds(cw_prior, self.P)]
+            d_lo, d_hi = self._cw_prior_dev
+            table = dv.empty((R, d_lo.shape[0]))
+            _lib.call("pta_cw_uniform", self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+            theta.update(_cw.labels(table, cw_prior, self.P))
+        if prior is None:
+            return theta
         if getattr(self, "_prior_dev", None) is None:
             self._prior_dev = [dv.f64(x) for x in _hyper.prior_bounds(prior, self.P)]
         d_lo, d_hi = self._prior_dev
         table = dv.empty((R, _hyper.n_columns(self.P)))
         _lib.call("pta_hyper_uniform", self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
         cols = _hyper.columns(self.P)
-        theta = {}
         for k in _hyper.KEYS:
             if k in prior:
                 c0, c1 = cols[k]
@@ -620,12 +719,17 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         """{'rn', 'gwb', 'wn', 'ecorr', 'det', 'total'}: the same realisations as generate(R, r0), one [R, n_toa] array per
         signal (the batched counterpart of the reference's per-signal ``added_signals_time`` entries).  Every deviate is a pure
         function of (seed, realisation, stream, index), so running the fused kernel once per signal with the other inputs
-        switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate()."""
+        switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate(); with
+        CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer)."""
+        cw = {}
         if theta is not None:
-            _hyper.check_theta(theta, R, self.P, self._gw, self._rn, self.gwb_mode)
+            rest, cw = _cw.split(theta)
+            if cw:
+                cw = _cw.check_theta(cw, R, self.P, self._cw)
+            _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode)
         if not self._prepared:
             self.prepare()
-        step = self.max_batch(hyper=theta is not None)
+        step = self.max_batch(hyper=theta is not None, cw=bool(cw))
         if R > step:
             raise ValueError(f"generate_per_signal: at most {step} realisations per call (one workspace batch)")
         total = self.generate(R, r0=r0, theta=theta)         # also fills the workspace (coefficients, mixed GWB grid series)
@@ -652,6 +756,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
             one("ecorr", ecorr_toa=keep[4], epoch_of=keep[5])
         if keep[6]:
             out["det"] = self.d_det.unsqueeze(0).expand(R, self.n_toa)
+        if cw:
+            out["cw"] = self._cw_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         return out
 
     def stream_to_host(self, total, chunk=480, r0=0):

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, device as dv
+from . import _cw, _lib, device as dv
 from . import optimal_statistic as ost
 from ._position import ra_dec
 
@@ -145,7 +145,9 @@ class OptimalStatisticMixin:
         if R < 1 or chunk < 1 or r0 < 0:
             raise ValueError(f"generate_os: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
         if td and theta is not None:
-            raise ValueError("generate_os: per-realisation theta is not supported in TD mode (see generate_td)")
+            rest, cw = _cw.split(theta)
+            if rest or not cw:
+                raise ValueError("generate_os: per-realisation theta is not supported in TD mode (see generate_td; only cw_* keys are)")
         per_real = 8 * (self.n_toa + self.P * st["C"])
         chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
         buf = getattr(self, "_os_rows", None)
@@ -158,7 +160,7 @@ class OptimalStatisticMixin:
             n = min(chunk, R - lo)
             rows = buf[:n]
             if td:
-                self.generate_td(n, r0=r0 + lo, out=rows)
+                self.generate_td(n, r0=r0 + lo, out=rows, theta=None if theta is None else {k: v[lo:lo + n] for k, v in theta.items()})
             elif theta is not None:
                 self.generate(n, r0=r0 + lo, out=rows, theta={k: v[lo:lo + n] for k, v in theta.items()})
             else:
