@@ -440,8 +440,8 @@ typedef struct {
   const double *rn_gamma;     /* [R x n_psr] */
 } pta_engine_hyper;
 
-/* pta_engine_generate with per-realisation theta: pta_gwb_spectrum_scale -> pta_gwb_czt_scaled (or pta_gwb_idft_rng_scaled) ->
- * pta_gwb_mix -> pta_engine_rn_coef_hyper -> pta_engine_synth (unchanged).  White noise, ECORR and deterministic signals as
+/* pta_engine_generate with per-realisation theta: pta_engine_rn_coef_hyper -> pta_gwb_spectrum_scale -> pta_gwb_czt_scaled (or
+ * pta_gwb_idft_rng_scaled) -> pta_gwb_mix -> pta_engine_synth (unchanged).  White noise, ECORR and deterministic signals as
  * configured in the plan.                                                                                                 */
 int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, const pta_engine_hyper *hyper_host,
                               uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out, void *stream);

@@ -393,15 +393,26 @@ extern "C" int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf
 extern "C" int pta_gwb_mix(const double *Mchol, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant,
                            void *stream);
 
-extern "C" int pta_engine_generate(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, uint64_t seed, uint64_t r0,
-                                   int R, double *out, int64_t ld_out, void *stream) {
-  PTA_REQUIRE(plan_host && tables_host && out, PTA_E_ARG, "pta_engine_generate: NULL argument");
+// The stage chain of pta_engine_generate and pta_engine_generate_hyper, queued on `stream`: RN coefficients -> (spectrum scale) ->
+// GWB transform -> ORF mix -> fused synthesis.  hyper == NULL stands for a pta_engine_hyper whose members are all NULL; a NULL
+// member runs that stage's fixed-parameter kernel.  `fn` names the entry point in error messages.
+static int engine_generate(const char *fn, const pta_engine_plan *plan_host, const pta_engine_tables *tables_host,
+                           const pta_engine_hyper *hyper, uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out, void *stream) {
+  PTA_REQUIRE(plan_host && tables_host && out, PTA_E_ARG, "%s: NULL argument", fn);
+  const pta_engine_hyper fixed{};
+  const pta_engine_hyper &h = hyper ? *hyper : fixed;
   pta_engine_plan p = *plan_host;
   const pta_engine_tables &tb = *tables_host;
   int rc;
   if (p.rn_k > 0) {
-    PTA_REQUIRE(tb.rn_amp && tb.ws_coef, PTA_E_ARG, "pta_engine_generate: red-noise amplitudes / workspace missing");
-    rc = pta_engine_rn_coef(seed, r0, R, p.n_psr, p.rn_k, tb.rn_amp, tb.ws_coef, p.rng_fast, stream);
+    PTA_REQUIRE(tb.rn_amp && tb.ws_coef, PTA_E_ARG, "%s: red-noise amplitudes / workspace missing", fn);
+    if (h.rn_log10_A) {
+      PTA_REQUIRE(h.rn_gamma && h.rn_f && h.rn_tspan, PTA_E_ARG, "%s: rn_gamma / rn_f / rn_tspan missing", fn);
+      rc = pta_engine_rn_coef_hyper(seed, r0, R, p.n_psr, p.rn_k, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma, tb.rn_amp, tb.ws_coef,
+                                    p.rng_fast, stream);
+    } else {
+      rc = pta_engine_rn_coef(seed, r0, R, p.n_psr, p.rn_k, tb.rn_amp, tb.ws_coef, p.rng_fast, stream);
+    }
     if (rc != PTA_OK) return rc;
     p.rn_coef = tb.ws_coef;
   }
@@ -409,14 +420,27 @@ extern "C" int pta_engine_generate(const pta_engine_plan *plan_host, const pta_e
   // VALU-bound transform / synthesis of the other: 4.806 against 4.814 ms per step - the mix's workgroups only get the slots the
   // other kernel's retiring workgroups free, and the halves run at slightly lower efficiency.  pta_engine_rn_coef is 0.016 ms.)
   if (p.gw_npts > 0) {
-    PTA_REQUIRE(tb.Mchol && tb.ws_G0 && tb.ws_G, PTA_E_ARG, "pta_engine_generate: GWB factor / workspace missing");
+    PTA_REQUIRE(tb.Mchol && tb.ws_G0 && tb.ws_G, PTA_E_ARG, "%s: GWB factor / workspace missing", fn);
+    const double *scale = h.gw_scale;
+    if (!scale && h.gw_log10_A) {
+      PTA_REQUIRE(h.gw_gamma && h.gw_f && h.gw_hcf0 && h.ws_scale, PTA_E_ARG, "%s: gw_gamma / gw_f / gw_hcf0 / ws_scale missing", fn);
+      rc = pta_gwb_spectrum_scale(h.gw_f, h.gw_hcf0, tb.gw_nf, R, h.gw_log10_A, h.gw_gamma, h.gw_turnover, h.gw_f0, h.gw_beta,
+                                  h.gw_power, h.ws_scale, h.ld_gw_scale, stream);
+      if (rc != PTA_OK) return rc;
+      scale = h.ws_scale;
+    }
     if (tb.use_czt) {
-      PTA_REQUIRE(tb.czt_pre && tb.czt_FB && tb.czt_tw && tb.czt_post, PTA_E_ARG, "pta_engine_generate: chirp-z tables missing");
-      rc = pta_gwb_czt(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw, tb.czt_post,
-                       tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, stream);
+      PTA_REQUIRE(tb.czt_pre && tb.czt_FB && tb.czt_tw && tb.czt_post, PTA_E_ARG, "%s: chirp-z tables missing", fn);
+      rc = scale ? pta_gwb_czt_scaled(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
+                                      tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, scale, h.ld_gw_scale, stream)
+                 : pta_gwb_czt(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
+                               tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, stream);
     } else {
-      PTA_REQUIRE(tb.Tsym && tb.rot, PTA_E_ARG, "pta_engine_generate: DFT-GEMM tables missing");
-      rc = pta_gwb_idft_rng(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant, p.rng_fast, stream);
+      PTA_REQUIRE(tb.Tsym && tb.rot, PTA_E_ARG, "%s: DFT-GEMM tables missing", fn);
+      rc = scale ? pta_gwb_idft_rng_scaled(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
+                                           p.rng_fast, scale, h.ld_gw_scale, stream)
+                 : pta_gwb_idft_rng(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
+                                    p.rng_fast, stream);
     }
     if (rc != PTA_OK) return rc;
     rc = pta_gwb_mix(tb.Mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream);
@@ -424,4 +448,16 @@ extern "C" int pta_engine_generate(const pta_engine_plan *plan_host, const pta_e
     p.gw_G = tb.ws_G;
   }
   return pta_engine_synth(&p, seed, r0, R, out, ld_out, stream);
+}
+
+extern "C" int pta_engine_generate(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, uint64_t seed, uint64_t r0,
+                                   int R, double *out, int64_t ld_out, void *stream) {
+  return engine_generate("pta_engine_generate", plan_host, tables_host, nullptr, seed, r0, R, out, ld_out, stream);
+}
+
+extern "C" int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host,
+                                         const pta_engine_hyper *hyper_host, uint64_t seed, uint64_t r0, int R, double *out,
+                                         int64_t ld_out, void *stream) {
+  PTA_REQUIRE(hyper_host, PTA_E_ARG, "pta_engine_generate_hyper: NULL argument");
+  return engine_generate("pta_engine_generate_hyper", plan_host, tables_host, hyper_host, seed, r0, R, out, ld_out, stream);
 }

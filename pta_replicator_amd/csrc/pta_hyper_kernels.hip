@@ -2,7 +2,8 @@
 //   pta_hyper_uniform          theta drawn on chip from uniform boxes, keyed by (seed, realisation) like the residuals
 //   pta_gwb_spectrum_scale     hcf(f_k; A_r, gamma_r) / hcf0(f_k) per (realisation, bin): the factor the scaled GWB transforms apply
 //   pta_engine_rn_coef_hyper   k_engine_rn_coef with sqrt(prior) evaluated per (realisation, pulsar, frequency)
-//   pta_engine_generate_hyper  pta_engine_generate with any of the two stages above switched in
+// pta_engine_generate_hyper (pta_engine_kernels.hip) is pta_engine_generate with the last two stages above switched in, in the stage
+// order of pta_engine_generate: pta_engine_rn_coef_hyper -> pta_gwb_spectrum_scale -> scaled GWB transform -> ORF mix -> synthesis.
 // The fused synthesis kernel is unchanged: only its inputs (RN coefficients, mixed GWB grid series) depend on theta.
 #include "pta_common.h"
 #include "pta_rng.h"
@@ -93,56 +94,4 @@ extern "C" int pta_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P
                      rn_tspan, log10_A, gamma, amp_fixed, coef, rng_fast ? 1 : 0);
   PTA_LAUNCH_CHECK();
   return PTA_OK;
-}
-
-extern "C" int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host,
-                                         const pta_engine_hyper *hyper_host, uint64_t seed, uint64_t r0, int R, double *out,
-                                         int64_t ld_out, void *stream) {
-  PTA_REQUIRE(plan_host && tables_host && hyper_host && out, PTA_E_ARG, "pta_engine_generate_hyper: NULL argument");
-  pta_engine_plan p = *plan_host;
-  const pta_engine_tables &tb = *tables_host;
-  const pta_engine_hyper &h = *hyper_host;
-  int rc;
-  if (p.gw_npts > 0) {
-    PTA_REQUIRE(tb.Mchol && tb.ws_G0 && tb.ws_G, PTA_E_ARG, "pta_engine_generate_hyper: GWB factor / workspace missing");
-    const double *scale = h.gw_scale;
-    if (!scale && h.gw_log10_A) {
-      PTA_REQUIRE(h.gw_gamma && h.gw_f && h.gw_hcf0 && h.ws_scale, PTA_E_ARG,
-                  "pta_engine_generate_hyper: gw_gamma / gw_f / gw_hcf0 / ws_scale missing");
-      rc = pta_gwb_spectrum_scale(h.gw_f, h.gw_hcf0, tb.gw_nf, R, h.gw_log10_A, h.gw_gamma, h.gw_turnover, h.gw_f0, h.gw_beta,
-                                  h.gw_power, h.ws_scale, h.ld_gw_scale, stream);
-      if (rc != PTA_OK) return rc;
-      scale = h.ws_scale;
-    }
-    if (tb.use_czt) {
-      PTA_REQUIRE(tb.czt_pre && tb.czt_FB && tb.czt_tw && tb.czt_post, PTA_E_ARG, "pta_engine_generate_hyper: chirp-z tables missing");
-      rc = scale ? pta_gwb_czt_scaled(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
-                                      tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, scale, h.ld_gw_scale, stream)
-                 : pta_gwb_czt(seed, r0, nullptr, 0, R, p.n_psr, tb.gw_nf, p.gw_npts, tb.gw_i0, tb.czt_pre, tb.czt_FB, tb.czt_tw,
-                               tb.czt_post, tb.ws_G0, p.gw_npts, tb.czt_variant, p.rng_fast, stream);
-    } else {
-      PTA_REQUIRE(tb.Tsym && tb.rot, PTA_E_ARG, "pta_engine_generate_hyper: DFT-GEMM tables missing");
-      rc = scale ? pta_gwb_idft_rng_scaled(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
-                                           p.rng_fast, scale, h.ld_gw_scale, stream)
-                 : pta_gwb_idft_rng(seed, r0, R, p.n_psr, tb.gw_nf, tb.Tsym, tb.rot, p.gw_npts, tb.ws_G0, p.gw_npts, tb.idft_variant,
-                                    p.rng_fast, stream);
-    }
-    if (rc != PTA_OK) return rc;
-    rc = pta_gwb_mix(tb.Mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream);
-    if (rc != PTA_OK) return rc;
-    p.gw_G = tb.ws_G;
-  }
-  if (p.rn_k > 0) {
-    PTA_REQUIRE(tb.rn_amp && tb.ws_coef, PTA_E_ARG, "pta_engine_generate_hyper: red-noise amplitudes / workspace missing");
-    if (h.rn_log10_A) {
-      PTA_REQUIRE(h.rn_gamma && h.rn_f && h.rn_tspan, PTA_E_ARG, "pta_engine_generate_hyper: rn_gamma / rn_f / rn_tspan missing");
-      rc = pta_engine_rn_coef_hyper(seed, r0, R, p.n_psr, p.rn_k, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma, tb.rn_amp, tb.ws_coef,
-                                    p.rng_fast, stream);
-    } else {
-      rc = pta_engine_rn_coef(seed, r0, R, p.n_psr, p.rn_k, tb.rn_amp, tb.ws_coef, p.rng_fast, stream);
-    }
-    if (rc != PTA_OK) return rc;
-    p.rn_coef = tb.ws_coef;
-  }
-  return pta_engine_synth(&p, seed, r0, R, out, ld_out, stream);
 }

@@ -124,6 +124,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         (deterministic.py:13-48); tref [s]; pdist [kpc], a scalar or one value per pulsar (theta's cw_pdist [R, P] overrides it).
         Adds nothing by itself; fixed sources of add_cgw / add_delays stay as they are, on top of it.  No prepare() needed."""
         self._cw = _cw.make_config(self.P, psrTerm, evolve, phase_approx, tref, pdist)
+        self._cwt = None   # device tables of the previous configuration (_cw_tables)
         return self
 
     def add_delays(self, delays):
@@ -144,6 +145,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
     def prepare(self):
         dev = dv.require_gpu()
         self._ws = None  # tables of a previous prepare() point at replaced buffers
+        self._hy = None  # and the hyper path's tables describe the previous configuration
         self._td_prepared = False  # and so do the dense factors of TD mode
         self._gw_grid_ready = False
         s = dv.stream_ptr()
@@ -413,69 +415,45 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         gwb_log10_A [R], gwb_gamma [R], rn_log10_A [R, P], rn_gamma [R, P] (NumPy arrays or tensors; pta_replicator_amd._hyper).
         Keys not given keep their configured values; NaN in rn_log10_A = that pulsar as configured.  With set_cw(), theta may also
         hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch."""
-        if theta is not None:
-            rest, cw = _cw.split(theta)
-            if not cw:
-                return self._generate_hyper(R, r0, out, theta)
-            cw = _cw.check_theta(cw, R, self.P, self._cw)
-            if rest:
-                out = self._generate_hyper(R, r0, out, rest, cw=True)
-            else:
-                out = self.generate(R, r0, out)
-            return self._cw_apply(cw, R, out)
-        if not self._prepared:
-            self.prepare()
-        if out is None:
-            out = dv.empty((R, self.n_toa))
-        step = self.max_batch()
-        ws = self.workspace(min(R, step))
-        grid_mode = self.gwb_mode == "grid" and self.plan.gw_npts
-        if grid_mode:
-            self._prepare_gw_grid_factor()
-            self.tdgw_plan.rng_fast = int(self.rng_fast)
-            self.tdgw_plan.z, self.tdgw_plan.ld_z, self.tdgw_plan.blk_zoff = None, 0, None   # (generate_td may have pointed it at a deviate buffer)
-        s = dv.stream_ptr()
-        for lo in range(0, R, step):
-            n = min(step, R - lo)
-            optr = ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0))
-            if not grid_mode:
-                _lib.call("pta_engine_generate", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), self.seed, r0 + lo, n, optr, out.stride(0), s)
-                continue
-            pl = _lib.EnginePlan.from_buffer_copy(self._plan_for_mode())
-            if pl.rn_k:
-                _lib.call("pta_engine_rn_coef", self.seed, r0 + lo, n, self.P, self.K, dv.ptr(self.d_amp), dv.ptr(ws["coef"]), int(self.rng_fast), s)
-                pl.rn_coef = ws["coef"].data_ptr()
-            _lib.call("pta_td_trmm_rng", ctypes.byref(self.tdgw_plan), self.seed, r0 + lo, n * self.P, dv.ptr(ws["G0"]), pl.gw_npts, s)
-            _lib.call("pta_gwb_mix", dv.ptr(self.d_M), self.P, dv.ptr(ws["G0"]), n, pl.gw_npts, pl.gw_npts, dv.ptr(ws["G"]), int(self.mix_variant), s)
-            pl.gw_G = ws["G"].data_ptr()
-            _lib.call("pta_engine_synth", ctypes.byref(pl), self.seed, r0 + lo, n, optr, out.stride(0), s)
-        # per-kernel callers (bench.py, replay) read the workspace pointers from the plan
-        if self.plan.rn_k:
-            self.plan.rn_coef = ws["coef"].data_ptr()
-        if self.plan.gw_npts:
-            self.plan.gw_G = ws["G"].data_ptr()
-        return out
+        hyper, cw = self._theta_parts(theta, R)
+        return self._generate(R, r0, out, hyper, cw)
 
-    def _generate_hyper(self, R, r0, out, theta, check_values=True, cw=False):
-        """generate() with per-realisation theta: pta_engine_generate_hyper per batch (spectrum scale -> scaled GWB transform -> mix
-        -> red-noise coefficients with sqrt(prior) per realisation -> the unchanged fused synthesis)."""
-        th = _hyper.check_theta(theta, R, self.P, self._gw, self._rn, self.gwb_mode, check_values)
+    def _theta_parts(self, theta, R, td=False, check_values=True):
+        """(hyper, cw): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
+        (_hyper.check_theta), None for the fixed-parameter path (no theta, or CW keys alone); cw: its CW keys (_cw.check_theta), {} if
+        none.  td=True: TD mode, which takes CW keys only.  check_values=False skips the value checks (theta drawn by sample_theta)."""
+        if theta is None:
+            return None, {}
+        rest, cw = _cw.split(theta)
+        if td and (rest or not cw):   # a deterministic term leaves the factored covariance as it is
+            raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
+                             "cw_* keys are): use generate(theta=...) or generate_sampled()")
+        cw = _cw.check_theta(cw, R, self.P, self._cw, check_values)
+        if cw and not rest:
+            return None, cw
+        return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), cw
+
+    def _generate(self, R, r0, out, hyper, cw, mask_unconfigured=True):
+        """generate() for theta resolved by _theta_parts, one launch sequence per batch: pta_engine_generate (hyper None) or
+        pta_engine_generate_hyper (red-noise coefficients with sqrt(prior) per realisation -> spectrum scale -> scaled GWB transform ->
+        mix -> the unchanged fused synthesis); gwb_mode "grid" queues the same stages one by one, the grid factor's product as the GWB
+        transform.  Then the CW term of cw.  mask_unconfigured: as in _theta_device."""
         if not self._prepared:
             self.prepare()
-        dev = self._theta_device(th, R, mask_unconfigured=check_values)
+        dev = None if hyper is None else self._theta_device(hyper, R, mask_unconfigured)
         if out is None:
             out = dv.empty((R, self.n_toa))
-        step = self.max_batch(hyper=True, cw=cw)
+        step = self.max_batch(hyper=hyper is not None, cw=bool(cw))
         ws = self.workspace(min(R, step))
-        hy = self._hyper_tables()
-        gw_theta = dev["gwb_log10_A"] is not None
+        hy = None if dev is None else self._hyper_tables()
+        gw_theta = dev is not None and dev["gwb_log10_A"] is not None
         if gw_theta and ("scale" not in ws or ws["scale"].shape[0] < ws["R"]):
             ws["scale"] = dv.empty((ws["R"], self.grid["Nf"]))
         grid_mode = self.gwb_mode == "grid" and self.plan.gw_npts
         if grid_mode:
             self._prepare_gw_grid_factor()
             self.tdgw_plan.rng_fast = int(self.rng_fast)
-            self.tdgw_plan.z, self.tdgw_plan.ld_z, self.tdgw_plan.blk_zoff = None, 0, None
+            self.tdgw_plan.z, self.tdgw_plan.ld_z, self.tdgw_plan.blk_zoff = None, 0, None   # (generate_td may have pointed it at a deviate buffer)
         s = dv.stream_ptr()
         P = self.P
 
@@ -484,23 +462,28 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         for lo in range(0, R, step):
             n = min(step, R - lo)
             optr = ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0))
-            h = _lib.EngineHyper()
-            if self.plan.rn_k:
-                h.rn_f, h.rn_tspan = hy["rn_f"].data_ptr(), hy["rn_tspan"].data_ptr()
-                h.rn_log10_A, h.rn_gamma = at(dev["rn_log10_A"], lo, P), at(dev["rn_gamma"], lo, P)
-            if gw_theta:
-                h.ld_gw_scale, h.ws_scale = self.grid["Nf"], ws["scale"].data_ptr()
-                h.gw_log10_A, h.gw_gamma = at(dev["gwb_log10_A"], lo, 1), at(dev["gwb_gamma"], lo, 1)
-                h.gw_f, h.gw_hcf0 = hy["gw_f"].data_ptr(), hy["gw_hcf0"].data_ptr()
-                c = self._gw
-                h.gw_turnover, h.gw_f0, h.gw_beta, h.gw_power = int(bool(c["turnover"])), float(c["f0"]), float(c["beta"]), float(c["power"])
+            h = None
+            if dev is not None:
+                h = _lib.EngineHyper()
+                if self.plan.rn_k:
+                    h.rn_f, h.rn_tspan = hy["rn_f"].data_ptr(), hy["rn_tspan"].data_ptr()
+                    h.rn_log10_A, h.rn_gamma = at(dev["rn_log10_A"], lo, P), at(dev["rn_gamma"], lo, P)
+                if gw_theta:
+                    h.ld_gw_scale, h.ws_scale = self.grid["Nf"], ws["scale"].data_ptr()
+                    h.gw_log10_A, h.gw_gamma = at(dev["gwb_log10_A"], lo, 1), at(dev["gwb_gamma"], lo, 1)
+                    h.gw_f, h.gw_hcf0 = hy["gw_f"].data_ptr(), hy["gw_hcf0"].data_ptr()
+                    c = self._gw
+                    h.gw_turnover, h.gw_f0, h.gw_beta, h.gw_power = int(bool(c["turnover"])), float(c["f0"]), float(c["beta"]), float(c["power"])
             if not grid_mode:
-                _lib.call("pta_engine_generate_hyper", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), ctypes.byref(h),
-                          self.seed, r0 + lo, n, optr, out.stride(0), s)
+                args = (self.seed, r0 + lo, n, optr, out.stride(0), s)
+                if h is None:
+                    _lib.call("pta_engine_generate", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), *args)
+                else:
+                    _lib.call("pta_engine_generate_hyper", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), ctypes.byref(h), *args)
                 continue
             pl = _lib.EnginePlan.from_buffer_copy(self._plan_for_mode())    # grid mode: RN theta only (check_config)
             if pl.rn_k:
-                if h.rn_log10_A:
+                if h is not None and h.rn_log10_A:
                     _lib.call("pta_engine_rn_coef_hyper", self.seed, r0 + lo, n, P, self.K, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma,
                               dv.ptr(self.d_amp), dv.ptr(ws["coef"]), int(self.rng_fast), s)
                 else:
@@ -510,12 +493,14 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
             _lib.call("pta_gwb_mix", dv.ptr(self.d_M), P, dv.ptr(ws["G0"]), n, pl.gw_npts, pl.gw_npts, dv.ptr(ws["G"]), int(self.mix_variant), s)
             pl.gw_G = ws["G"].data_ptr()
             _lib.call("pta_engine_synth", ctypes.byref(pl), self.seed, r0 + lo, n, optr, out.stride(0), s)
+        # per-kernel callers (bench.py, replay) read the workspace pointers from the plan
         if self.plan.rn_k:
             self.plan.rn_coef = ws["coef"].data_ptr()
         if self.plan.gw_npts:
             self.plan.gw_G = ws["G"].data_ptr()
-        self._theta_keep = dev   # the launches above read these buffers asynchronously
-        return out
+        if dev is not None:
+            self._theta_keep = dev   # the launches above read these buffers asynchronously
+        return self._cw_apply(cw, R, out) if cw else out
 
     def _theta_device(self, th, R, mask_unconfigured=True):
         """validated theta -> contiguous float64 device tensors, keys not given filled with the configured values:
@@ -542,10 +527,9 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
     def _hyper_tables(self):
         """theta-independent device tables of the hyper path, built once per prepare(): GWB frequency grid and configured hcf,
         red-noise frequencies [P, K/2] and Tspan [P] (the values prepare() built the configured amplitudes from)."""
-        hy = getattr(self, "_hy", None)
-        if hy is not None and hy["plan"] is self.plan:
-            return hy
-        hy = {"plan": self.plan}
+        if self._hy is not None:
+            return self._hy
+        hy = {}
         if self.plan.gw_npts:
             c = self._gw
             hy["gw_f"] = dv.f64(self.grid["f"])
@@ -559,15 +543,12 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         return hy
 
     def _cw_tables(self):
-        """theta-independent device tables of the CW path, built once per prepare() / set_cw(): pulsar unit vectors [P, 3] (the
-        reference's expression, deterministic.py:88) and the configured pulsar distances [P] (kpc)."""
-        tb = getattr(self, "_cwt", None)
-        if tb is not None and tb["plan"] is self.plan and tb["conf"] is self._cw:
-            return tb
-        phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
-        tb = {"plan": self.plan, "conf": self._cw, "phat": dv.f64(phat), "pdist": dv.f64(self._cw["pdist"])}
-        self._cwt = tb
-        return tb
+        """theta-independent device tables of the CW path, built once per set_cw(): pulsar unit vectors [P, 3] (the reference's
+        expression, deterministic.py:88) and the configured pulsar distances [P] (kpc)."""
+        if self._cwt is None:
+            phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
+            self._cwt = {"phat": dv.f64(phat), "pdist": dv.f64(self._cw["pdist"])}
+        return self._cwt
 
     def _cw_apply(self, cw, R, out, accumulate=True):
         """out[R, n_toa] (+)= the CW term of every row for validated CW theta `cw` (row r = the source of realisation r0 + r): the
@@ -639,14 +620,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         if not self._prepared:
             self.prepare()
         theta = self.sample_theta(R, r0)
-        rest, cw = _cw.split(theta)
-        if rest:
-            out = self._generate_hyper(R, r0, out, rest, check_values=False, cw=bool(cw))
-        else:
-            out = self.generate(R, r0, out)
-        if cw:
-            out = self._cw_apply(_cw.check_theta(cw, R, self.P, self._cw, check_values=False), R, out)
-        return out, theta
+        hyper, cw = self._theta_parts(theta, R, check_values=False)
+        return self._generate(R, r0, out, hyper, cw, mask_unconfigured=False), theta
 
     def sample_theta(self, R, r0=0):
         """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses)."""
@@ -657,19 +632,14 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
             self.prepare()
         theta = {}
         if cw_prior is not None:   # stream (8, 0): pair j = label column j, whatever else is sampled
-            if getattr(self, "_cw_prior_dev", None) is None:
+            if self._cw_prior_dev is None:
                 self._cw_prior_dev = [dv.f64(x) for x in _cw.prior_bounds(cw_prior, self.P)]
-            d_lo, d_hi = self._cw_prior_dev
-            table = dv.empty((R, d_lo.shape[0]))
-            _lib.call("pta_cw_uniform", self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
-            theta.update(_cw.labels(table, cw_prior, self.P))
+            theta.update(_cw.labels(self._uniform_table("pta_cw_uniform", self._cw_prior_dev, R, r0), cw_prior, self.P))
         if prior is None:
             return theta
-        if getattr(self, "_prior_dev", None) is None:
+        if self._prior_dev is None:
             self._prior_dev = [dv.f64(x) for x in _hyper.prior_bounds(prior, self.P)]
-        d_lo, d_hi = self._prior_dev
-        table = dv.empty((R, _hyper.n_columns(self.P)))
-        _lib.call("pta_hyper_uniform", self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+        table = self._uniform_table("pta_hyper_uniform", self._prior_dev, R, r0)
         cols = _hyper.columns(self.P)
         for k in _hyper.KEYS:
             if k in prior:
@@ -681,6 +651,14 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
                 if k in theta and len(none):   # pulsars configured without red noise keep none: their labels are NaN
                     theta[k][:, none] = float("nan")
         return theta
+
+    def _uniform_table(self, kernel, bounds, R, r0):
+        """[R, n] table of `kernel` (pta_hyper_uniform or pta_cw_uniform) for realisations r0 .. r0+R-1: column j uniform in the box
+        (lo[j], hi[j]) of the device bounds (lo, hi)."""
+        d_lo, d_hi = bounds
+        table = dv.empty((R, d_lo.shape[0]))
+        _lib.call(kernel, self.seed, r0, R, table.shape[1], dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+        return table
 
     def _plan_for_mode(self):
         """the plan generate() launches with: the shared one, or - wn_mode "single" - a private copy whose white-noise operands are
@@ -721,18 +699,13 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin):
         function of (seed, realisation, stream, index), so running the fused kernel once per signal with the other inputs
         switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate(); with
         CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer)."""
-        cw = {}
-        if theta is not None:
-            rest, cw = _cw.split(theta)
-            if cw:
-                cw = _cw.check_theta(cw, R, self.P, self._cw)
-            _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode)
+        hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
         step = self.max_batch(hyper=theta is not None, cw=bool(cw))
         if R > step:
             raise ValueError(f"generate_per_signal: at most {step} realisations per call (one workspace batch)")
-        total = self.generate(R, r0=r0, theta=theta)         # also fills the workspace (coefficients, mixed GWB grid series)
+        total = self._generate(R, r0, None, hyper, cw)       # also fills the workspace (coefficients, mixed GWB grid series)
         s = dv.stream_ptr()
         base = self._plan_for_mode()                         # wn_mode "single": the white-noise term is the one-deviate form, as in generate()
         keep = (self.plan.rn_k, self.plan.gw_npts, base.wn_a, base.wn_b, self.plan.ecorr_toa, self.plan.epoch_of, self.plan.det, base.wn_c)

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _cw, _lib, device as dv
+from . import _lib, device as dv
 from . import optimal_statistic as ost
 from ._position import ra_dec
 
@@ -144,10 +144,7 @@ class OptimalStatisticMixin:
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:
             raise ValueError(f"generate_os: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
-        if td and theta is not None:
-            rest, cw = _cw.split(theta)
-            if rest or not cw:
-                raise ValueError("generate_os: per-realisation theta is not supported in TD mode (see generate_td; only cw_* keys are)")
+        hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
         per_real = 8 * (self.n_toa + self.P * st["C"])
         chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
         buf = getattr(self, "_os_rows", None)
@@ -156,15 +153,18 @@ class OptimalStatisticMixin:
             buf = self._os_rows = dv.empty((chunk, self.n_toa))
         A2 = dv.empty((R, st["n_orf"]))
         rho = dv.empty((R, len(st["plan"].den))) if pairs else None
+
+        def rows_of(part, lo, n):
+            return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
         for lo in range(0, R, chunk):
             n = min(chunk, R - lo)
             rows = buf[:n]
             if td:
-                self.generate_td(n, r0=r0 + lo, out=rows, theta=None if theta is None else {k: v[lo:lo + n] for k, v in theta.items()})
-            elif theta is not None:
-                self.generate(n, r0=r0 + lo, out=rows, theta={k: v[lo:lo + n] for k, v in theta.items()})
+                self.generate_td(n, r0=r0 + lo, out=rows)
+                if cw:
+                    self._cw_apply(rows_of(cw, lo, n), n, rows)
             else:
-                self.generate(n, r0=r0 + lo, out=rows)
+                self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
             self._os_state("generate_os")     # generate_td / generate may have (re)prepared the engine
             self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
         return self._os_result(st, A2, rho)

@@ -30,7 +30,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _cw, _lib, device as dv
+from . import _lib, device as dv
 
 STREAM_TD, STREAM_TDGW = 5, 6
 
@@ -344,13 +344,7 @@ class TimeDomainMixin:
         and NOT the default (profiles/r04_bench_mid_round.json): 32.8 ms per 1024 realisations of the 68 x 5000 array in four pipelined
         chunks of 256 against 31.2 ms as one chunk - every chunk streams the 13.6 GB of factors again, and the preparation kernels are
         VALU work on the ALUs the matrix pipe shares, not idle time to fill."""
-        if theta is not None:   # only the CW keys: a deterministic term leaves the factored covariance as it is
-            rest, cw = _cw.split(theta)
-            if rest or not cw:
-                raise ValueError("generate_td: per-realisation theta is not supported in TD mode (the dense factors are built for one "
-                                 "covariance); use generate(theta=...) or generate_sampled()")
-            cw = _cw.check_theta(cw, R, self.P, self._cw)
-            return self._cw_apply(cw, R, self.generate_td(R, r0, out, chunk))
+        _, cw = self._theta_parts(theta, R, td=True)   # only CW keys, added after the batch
         if not getattr(self, "_td_prepared", False) or not self._prepared:
             self.prepare_td()
         if out is None:
@@ -461,7 +455,7 @@ class TimeDomainMixin:
                       out.stride(0), s)
             if overlap:
                 ev_done[c & 1].record(main)
-        return out
+        return self._cw_apply(cw, R, out) if cw else out
 
     # ---------------------------------------------------------------- draws / replay ------------
     def dump_draws_td(self, r):
