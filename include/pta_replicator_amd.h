@@ -616,6 +616,37 @@ int pta_os_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off,
 int pta_os_pairs(const double *Y, int64_t ld_y, int P, int C, int R, const int32_t *pair_a, const int32_t *pair_b, int n_pairs, const double *wt,
                  int n_orf, double *A2, int64_t ld_a2, const double *den, double *pair_out, int64_t ld_pair, void *stream);
 
+/* ---- optimal statistic under per-realisation noise parameters (ABI 8, additive) ----
+ * The noise model of the statistic follows theta per realisation (red noise and the GWB auto-term; white noise, ECORR and the timing
+ * model stay fixed).  Host NumPy (optimal_statistic.py: matched_operator) builds per pulsar V = U^T P0' [K, N_a] and A = U^T P0' U
+ * [K, K], U = [F_rn | F], K = K_rn + C <= 128; pta_os_project gives q = V r_a (in blocks of <= 64 rows of V).  Per (realisation,
+ * pulsar), with prior variances b [K] over the pulsar's mean white-noise variance s and D = diag(sqrt b):
+ *     Mc = I + D A D = L L^T,   H = L^-1 D [q | A[:, F]],   X = S^1/2 (q_F - H_F^T h_q) / s,   Z = S^1/2 (A_FF - H_F^T H_F) S^1/2 / s
+ * (F = the last C columns; S [C] the unit spectrum), then num_ab = X_a . X_b, den_ab = tr(Z_a Z_b) per realisation.
+ *
+ * pta_os_matched_prior: b[(r * P + a) * K + k], K = K_rn + C.  Columns k < K_rn: pta_rn_amp(rn_f[a * K_rn / 2 + k / 2], rn_tspan[a],
+ * rn_log10_A[r * P + a], rn_gamma[r * P + a])^2 / s[a], or rn_phi[a * K_rn + k] / s[a] where rn_log10_A is NaN or the pointer NULL.
+ * Columns K_rn + c: 10^(2 gw_log10_A[r]) S(f = (c / 2 + 1) / T; gw_gamma[r]) / s[a] with the unit spectrum
+ * S = fyr^(gamma - 3) f^-gamma / (12 pi^2 T), or 0 when gw_log10_A is NULL (no GW auto-term).                                       */
+int pta_os_matched_prior(int R, int P, int K_rn, int C, const double *rn_f, const double *rn_tspan, const double *rn_phi, const double *rn_log10_A,
+                         const double *rn_gamma, double T, const double *gw_log10_A, const double *gw_gamma, const double *s, double *b,
+                         void *stream);
+/* pta_os_matched_solve: X[(r * P + a) * C + c] and the packed lower triangle Z[(r * P + a) * C (C + 1) / 2 + c (c + 1) / 2 + c2] (c2 <= c)
+ * from A [P, K, K] (symmetric), b [R, P, K] (>= 0, zeros allowed), S [C], s [P] and q: element (r, a, k) at
+ * q[r * ld_q + P * k0 + a * cb + (k - k0)], k0 = (k / q_block) * q_block, cb = min(q_block, K - k0) - what pta_os_project writes when it
+ * is called once per block of q_block rows of V with Y = q + P * k0 (q_block >= K: plain [R, P, K]).  1 <= C <= 64, C <= K <= 128
+ * (PTA_E_ARG beyond).  One workgroup per (r, a), factor and right-hand sides in LDS (up to 131 KiB); Mc has eigenvalues >= 1 for any
+ * finite b, so the factorisation cannot fail.  Bit-identical per (r, a) whatever R.                                                    */
+int pta_os_matched_solve(const double *A, int P, int K, int C, int R, const double *b, const double *q, int64_t ld_q, int q_block, const double *S,
+                         const double *s, double *X, double *Z, void *stream);
+/* pta_os_matched_pairs: num_p = X[r, pair_a[p]] . X[r, pair_b[p]], den_p = tr(Z[r, pair_a[p]] Z[r, pair_b[p]]) (packed triangles),
+ * A2[r * ld_a2 + o] = sum_p G[o * n_pairs + p] num_p / sum_p G2[o * n_pairs + p] den_p, sigma[r * ld_sigma + o] = (sum_p G2 den_p)^-1/2 for
+ * o < n_orf <= 8 (G2 = G * G); optionally (both or neither) rho[r * ld_pair + p] = num_p / den_p and sigma_pair[r * ld_pair + p] =
+ * den_p^-1/2.  One workgroup per realisation, one wave per pair; fixed summation order.                                               */
+int pta_os_matched_pairs(const double *X, const double *Z, int P, int C, int R, const int32_t *pair_a, const int32_t *pair_b, int n_pairs,
+                         const double *G, const double *G2, int n_orf, double *A2, int64_t ld_a2, double *sigma, int64_t ld_sigma, double *rho,
+                         double *sigma_pair, int64_t ld_pair, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays
  * back to rank 0"): realisations are sharded by contiguous row ranges - rank r owns rows [a_r, b_r) of the [total_rows x n_cols]

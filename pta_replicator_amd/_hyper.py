@@ -64,6 +64,28 @@ def check_theta(theta, R, P, gw, rn, gwb_mode, check_values=True):
     if not isinstance(theta, dict):
         raise ValueError("theta must be a dict of per-realisation parameters")
     check_config(theta.keys(), gw, rn, gwb_mode)
+    return _check_arrays(theta, R, P, rn, check_values)
+
+
+def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True):
+    """validate theta as the noise model of the optimal statistic (optimal_statistic(theta=...), generate_os(matched=True)): keys,
+    shapes and NaN rules of check_theta, without its gwb_mode restriction (the OS does not care how the GWB was generated).  GWB
+    keys are refused when the OS was prepared without the GWB auto-term (gwb_auto false); cw_* keys are ignored (a deterministic
+    source is not part of the noise model).  Returns {key: array} of the GWB / red-noise keys."""
+    from . import _cw
+    theta, _ = _cw.split(theta)
+    unknown = set(theta) - set(KEYS)
+    if unknown:
+        raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(KEYS)})")
+    if set(theta) & set(GWB_KEYS) and not gwb_auto:
+        raise ValueError("theta: GWB parameters given but the optimal statistic was prepared without the GWB auto-term (gwb_auto)")
+    if set(theta) & set(RN_KEYS) and rn is None:
+        raise ValueError("theta: red-noise parameters given but no red noise is configured (set_red_noise)")
+    return _check_arrays(theta, R, P, rn, check_values)
+
+
+def _check_arrays(theta, R, P, rn, check_values):
+    """shapes and values of theta's GWB / red-noise arrays (keys already checked against the configuration)."""
     out = {}
     for k, v in theta.items():
         v = _as_array(k, v)

@@ -9,25 +9,38 @@
 
 and ``generate_os(R)`` runs generate / generate_td / generate(theta=...) chunk by chunk into one reused buffer with the OS behind
 each chunk, keeping only the statistics.  A realisation's statistic is bit-identical whatever chunk or row it is computed in.
+
+``prepare_optimal_statistic(matched=True)`` also prepares the OS whose noise model follows theta per realisation (red noise and the
+GWB auto-term; white noise, ECORR and the timing model stay fixed): V = U^T P0' and A = U^T P0' U per pulsar, U = [F_rn | F].
+``optimal_statistic(rows, theta=...)`` and ``generate_os(R, theta=..., matched=True)`` then run
+
+    pta_os_project         q[r, a, :] = V_a r_a            once per block of <= 64 rows of V
+    pta_os_matched_prior   b[r, a, :] = prior variances of theta over the mean white-noise variance
+    pta_os_matched_solve   X_ra = W_a(theta_r) r_a, Z_ra = Z_a(theta_r)      one workgroup per (realisation, pulsar)
+    pta_os_matched_pairs   A2, sigma (and rho, sigma_pair) per realisation
+
+with sigma (and sigma_pair) per realisation.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib, device as dv
+from . import _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from ._position import ra_dec
 
 
 class OptimalStatisticMixin:
-    def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None):
+    def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None, matched=False):
         """W, Z, den and ORF weights of the array under the configured noise model (white noise + ECORR + red noise, optionally the
         GWB auto-term), uploaded once.
 
         components: n_f = 1 .. 32 frequencies k / T (T = span of the whole array); gamma: spectral index of the unit spectrum;
         orfs: names "hd", "monopole", "dipole" or [P, P] arrays (at most 8); timing_model: "spin", "astrometric" or None;
-        gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False = off."""
+        gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False = off.
+        matched: also prepare the OS under per-realisation noise parameters (optimal_statistic(theta=...), generate_os(matched=True)):
+        K = red-noise columns + 2 n_f <= 128."""
         if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
             raise ValueError(f"components={components!r}: an integer 1 .. 32 (2 n_f <= 64 columns)")
         if timing_model not in ("spin", "astrometric", None):
@@ -44,14 +57,20 @@ class OptimalStatisticMixin:
             raise ValueError("the cross-correlation OS needs at least two pulsars")
         if self._wn is None:
             raise ValueError("the OS needs measurement noise (set_white_noise): without it the noise covariance is singular")
+        gw_lA = None                       # log10 amplitude of the GWB auto-term, None = no auto-term
         if gwb_auto is None:
-            amp2 = 10.0 ** (2 * float(self._gw["A"])) if self._gw is not None else 0.0
+            gw_lA = float(self._gw["A"]) if self._gw is not None else None
         elif gwb_auto is False:
-            amp2 = 0.0
+            pass
         elif isinstance(gwb_auto, (bool, np.bool_)):
             raise ValueError("gwb_auto: None, a log10 amplitude, or False")
         else:
-            amp2 = 10.0 ** (2 * float(gwb_auto))
+            gw_lA = float(gwb_auto)
+        amp2 = 0.0 if gw_lA is None else 10.0 ** (2 * gw_lA)
+        K_rn = 2 * self._rn["components"] if self._rn is not None else 0
+        if matched and K_rn + 2 * int(components) > _lib.OSM_KMAX:
+            raise ValueError(f"matched=True: K = {K_rn} red-noise columns + {2 * int(components)} OS columns exceeds the kernel limit of "
+                             f"{_lib.OSM_KMAX}")
         if not self._prepared:
             self.prepare()
         from .simulate import timing_design_matrix
@@ -75,7 +94,16 @@ class OptimalStatisticMixin:
         self._os = dict(plan=plan, engine_plan=self.plan, C=plan.C, n_orf=len(plan.names), names=plan.names,
                         Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), pa=dv.i32(plan.pair_a), pb=dv.i32(plan.pair_b),
                         wt=dv.f64(plan.weights), den=dv.f64(plan.den), sigma=dv.f64(plan.sigma), sigma_pair=dv.f64(plan.sigma_pair),
-                        zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None)
+                        zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None, matched=None)
+        if matched:
+            mp = ost.prepare_matched(toas, sigma2, np.array(pos), components=int(components), gamma=float(gamma), orfs=orfs,
+                                     epoch_of=epoch_of, ecorr=ecorr, F_rn=[self._rn_basis_host(a) for a in range(P)] if self.plan.rn_k else None,
+                                     M=M)
+            m = dict(plan=mp, K=mp.K, K_rn=mp.K_rn, nz=mp.C * (mp.C + 1) // 2, Vt=dv.f64(mp.Vt()), A=dv.f64(mp.A), s=dv.f64(mp.s), S=dv.f64(mp.S),
+                     G=dv.f64(mp.G), G2=dv.f64(mp.G ** 2), T=mp.T, gw=None if gw_lA is None else (gw_lA, float(gamma)), ws=None, rn_phi=None)
+            if mp.K_rn:
+                m["rn_phi"] = dv.f64(self.rn_amp ** 2)
+            self._os["matched"] = m
         return self
 
     def _rn_basis_host(self, a):
@@ -97,11 +125,15 @@ class OptimalStatisticMixin:
             raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_optimal_statistic(): call it again")
         return st
 
-    def optimal_statistic(self, rows, pairs=False):
+    def optimal_statistic(self, rows, pairs=False, theta=None):
         """OS of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
         generate_td, generate_sampled, or the caller's own residuals).  Returns a dict of device tensors: A2 [R, n_orf], snr [R, n_orf],
         sigma [n_orf], names (list); with pairs=True also rho [R, n_pairs] (= num / den), sigma_pair [n_pairs], zeta [n_pairs] and
-        pairs [n_pairs, 2] (a < b, row-major upper triangle)."""
+        pairs [n_pairs, 2] (a < b, row-major upper triangle).
+
+        theta (needs prepare_optimal_statistic(matched=True)): per-realisation noise parameters as generate(theta=...) takes them;
+        row r is then weighted with the noise model of theta[r] (keys not given and NaN red-noise amplitudes: as configured / as
+        prepared; cw_* keys are ignored).  sigma is then [R, n_orf] and sigma_pair [R, n_pairs]."""
         st = self._os_state("optimal_statistic")
         if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
             raise ValueError("rows must be a float64 device tensor")
@@ -110,6 +142,13 @@ class OptimalStatisticMixin:
         if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
             raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
         R = int(rows.shape[0])
+        if theta is not None:
+            dev = self._os_matched_theta(st, theta, R, "optimal_statistic")
+            out = self._os_matched_out(st, R, pairs)
+            step = self._os_matched_chunk(st, R, with_rows=False)
+            for lo in range(0, R, step):
+                self._os_matched_launch(rows[lo:lo + step], min(step, R - lo), dev, lo, out)
+            return self._os_matched_result(st, out)
         out = {"A2": dv.empty((R, st["n_orf"])), "rho": dv.empty((R, len(st["plan"].den))) if pairs else None}
         self._os_launch(rows, R, out["A2"], out["rho"])
         return self._os_result(st, out["A2"], out["rho"])
@@ -135,24 +174,38 @@ class OptimalStatisticMixin:
                   ctypes.c_void_p(A2.data_ptr()), A2.stride(0), dv.ptr(st["den"]) if rho is not None else None,
                   ctypes.c_void_p(rho.data_ptr()) if rho is not None else None, rho.stride(0) if rho is not None else 0, s)
 
-    def generate_os(self, R, r0=0, theta=None, td=False, chunk=1024, pairs=False):
+    def generate_os(self, R, r0=0, theta=None, td=False, chunk=1024, pairs=False, matched=False):
         """OS of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
         td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations, e.g. sample_theta(R, r0)); only
         the statistics are kept.  Same results as optimal_statistic(generate(R, r0, ...)), bit for bit, whatever the chunk.  The chunk
-        is cut so that the buffer stays within workspace_bytes."""
+        is cut so that the buffer stays within workspace_bytes.
+
+        matched=True (needs theta and prepare_optimal_statistic(matched=True)): every chunk's statistic is evaluated under the theta
+        it was generated with - optimal_statistic(generate(R, r0, theta=theta), theta=theta), bit for bit; rows, q, b, X and Z of a
+        chunk stay within workspace_bytes."""
         st = self._os_state("generate_os")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:
             raise ValueError(f"generate_os: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
         hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
+        mdev = None
+        if matched:
+            if theta is None:
+                raise ValueError("generate_os: matched=True needs theta (the noise parameters every realisation is evaluated under)")
+            mdev = self._os_matched_theta(st, theta, R, "generate_os")
+            chunk = min(chunk, self._os_matched_chunk(st, R, with_rows=True))
         per_real = 8 * (self.n_toa + self.P * st["C"])
         chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
         buf = getattr(self, "_os_rows", None)
         if buf is None or buf.shape[0] < chunk:
             self._os_rows = None
             buf = self._os_rows = dv.empty((chunk, self.n_toa))
-        A2 = dv.empty((R, st["n_orf"]))
-        rho = dv.empty((R, len(st["plan"].den))) if pairs else None
+        A2 = rho = mout = None
+        if matched:
+            mout = self._os_matched_out(st, R, pairs)
+        else:
+            A2 = dv.empty((R, st["n_orf"]))
+            rho = dv.empty((R, len(st["plan"].den))) if pairs else None
 
         def rows_of(part, lo, n):
             return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
@@ -166,5 +219,87 @@ class OptimalStatisticMixin:
             else:
                 self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
             self._os_state("generate_os")     # generate_td / generate may have (re)prepared the engine
-            self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
-        return self._os_result(st, A2, rho)
+            if matched:
+                self._os_matched_launch(rows, n, mdev, lo, mout)
+            else:
+                self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
+        return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho)
+
+    # ---- the OS under per-realisation noise parameters ----
+    def _os_matched_theta(self, st, theta, R, what):
+        """theta validated as the OS's noise model (_hyper.check_theta_os) -> contiguous float64 device tensors {rn_log10_A, rn_gamma:
+        [R, P] or None (every pulsar as configured), gw_log10_A, gw_gamma: [R] or None (no GW auto-term)}; keys not given are filled
+        with the configured red noise / the prepared auto-term, pulsars configured without red noise get NaN amplitudes."""
+        m = st["matched"]
+        if m is None:
+            raise ValueError(f"{what}: theta needs prepare_optimal_statistic(matched=True)")
+        th = _hyper.check_theta_os(theta, R, self.P, self._rn, m["gw"] is not None)
+        gpu = dv.require_gpu()
+
+        def f64(x):
+            if hasattr(x, "data_ptr"):
+                return x.to(device=gpu, dtype=torch.float64).contiguous()
+            return dv.f64(np.ascontiguousarray(x, dtype=np.float64))
+        dev = dict.fromkeys(("rn_log10_A", "rn_gamma", "gw_log10_A", "gw_gamma"))
+        if m["gw"] is not None:
+            for k, key, conf in (("gw_log10_A", "gwb_log10_A", m["gw"][0]), ("gw_gamma", "gwb_gamma", m["gw"][1])):
+                dev[k] = f64(th[key]) if key in th else torch.full((R,), conf, dtype=torch.float64, device=gpu)
+        if any(k in th for k in _hyper.RN_KEYS) and m["K_rn"]:
+            for k, c in zip(_hyper.RN_KEYS, _hyper.configured_rn(self._rn)):
+                dev[k] = f64(th[k]) if k in th else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
+            none = self._hyper_tables()["rn_none"]
+            if len(none):
+                dev["rn_log10_A"] = dev["rn_log10_A"].clone()
+                dev["rn_log10_A"][:, none] = float("nan")
+        return dev
+
+    def _os_matched_chunk(self, st, R, with_rows):
+        """realisations per launch sequence: q and b [P, K], X [P, C], Z [P, C (C + 1) / 2] (and the generated rows) of a chunk within
+        workspace_bytes"""
+        m = st["matched"]
+        per_real = 8 * (self.P * (2 * m["K"] + st["C"] + m["nz"]) + (self.n_toa if with_rows else 0))
+        return max(1, min(R, int(self.workspace_bytes) // per_real))
+
+    def _os_matched_out(self, st, R, pairs):
+        npairs = len(st["plan"].den)
+        return {"A2": dv.empty((R, st["n_orf"])), "sigma": dv.empty((R, st["n_orf"])), "rho": dv.empty((R, npairs)) if pairs else None,
+                "sigma_pair": dv.empty((R, npairs)) if pairs else None}
+
+    def _os_matched_result(self, st, out):
+        res = {"A2": out["A2"], "snr": out["A2"] / out["sigma"], "sigma": out["sigma"], "names": list(st["names"])}
+        if out["rho"] is not None:
+            res.update(rho=out["rho"], sigma_pair=out["sigma_pair"], zeta=st["zeta"], pairs=st["pairs"])
+        return res
+
+    def _os_matched_launch(self, rows, n, dev, lo, out):
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of theta `dev` -> rows lo .. of out: pta_os_project per block of 64 rows of V,
+        pta_os_matched_prior, pta_os_matched_solve, pta_os_matched_pairs, all on the current stream"""
+        st = self._os
+        m = st["matched"]
+        P, C, K, K_rn, nz = self.P, st["C"], m["K"], m["K_rn"], m["nz"]
+        ws = m["ws"]
+        if ws is None or ws["n"] < n:
+            m["ws"] = None
+            ws = m["ws"] = dict(n=n, q=dv.empty((n, P * K)), b=dv.empty((n, P * K)), X=dv.empty((n, P * C)), Z=dv.empty((n, P * nz)))
+        s = dv.stream_ptr()
+        blk = 64                                   # PTA_OS_CMAX columns per pta_os_project call
+        for k0 in range(0, K, blk):
+            _lib.call("pta_os_project", ctypes.c_void_p(m["Vt"].data_ptr() + 8 * k0 * self.n_toa), self.n_toa, min(blk, K - k0), dv.ptr(st["off"]), P,
+                      ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n, ctypes.c_void_p(ws["q"].data_ptr() + 8 * P * k0), P * K, s)
+
+        def at(x, per_row):
+            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * per_row)
+        hy = self._hyper_tables() if K_rn else {}
+        _lib.call("pta_os_matched_prior", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
+                  dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], at(dev["gw_log10_A"], 1),
+                  at(dev["gw_gamma"], 1), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
+        _lib.call("pta_os_matched_solve", dv.ptr(m["A"]), P, K, C, n, dv.ptr(ws["b"]), dv.ptr(ws["q"]), P * K, blk, dv.ptr(m["S"]), dv.ptr(m["s"]),
+                  dv.ptr(ws["X"]), dv.ptr(ws["Z"]), s)
+        npairs = len(st["plan"].den)
+        A2, sg, rho, sp = out["A2"], out["sigma"], out["rho"], out["sigma_pair"]
+
+        def row(x):
+            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * x.stride(0))
+        _lib.call("pta_os_matched_pairs", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
+                  dv.ptr(m["G2"]), st["n_orf"], row(A2), A2.stride(0), row(sg), sg.stride(0), row(rho), row(sp), rho.stride(0) if rho is not None else 0, s)
+        self._os_theta_keep = dev   # the launches above read these buffers asynchronously

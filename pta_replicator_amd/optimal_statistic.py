@@ -233,3 +233,178 @@ def os_from_Y(plan, Y):
 def os_from_rows(plan, rows):
     """the whole per-realisation OS in NumPy: (A2, snr, num)."""
     return os_from_Y(plan, project(plan, rows))
+
+
+# ---------------------------------------------------------------- OS under per-realisation noise parameters -------------------
+# The noise model follows theta per realisation: white noise, ECORR and the timing model stay fixed, red noise and the GWB
+# auto-term change.  Per pulsar, with N' = N / s (white noise + ECORR over the mean white-noise variance s):
+#
+#     P0' = N'^-1 - N'^-1 M (M^T N'^-1 M)^-1 M^T N'^-1      (N'^-1 without a timing model)
+#     U   = [F_rn | F]  [N_a, K],  K = K_rn + C
+#     V   = U^T P0'     [K, N_a]            A = U^T P0' U  [K, K]
+#
+# are built once (matched_operator); per realisation and pulsar, with prior variances b [K] (matched_prior) and D = diag(sqrt b):
+#
+#     q = V r_a,   Mc = I + D A D = L L^T,   H = L^-1 D [q | A[:, F]]
+#     X = S^1/2 (q_F - H_F^T h_q) / s          (= W_a(theta) r_a)
+#     Z = S^1/2 (A_FF - H_F^T H_F) S^1/2 / s   (= Z_a(theta))
+#
+# and num_ab = X_a . X_b, den_ab = tr(Z_a Z_b) per realisation.  Mc has eigenvalues >= 1 for any finite theta.
+MATCHED_KMAX = 128   # K = K_rn + C of pta_os_matched_solve (PTA_OSM_KMAX)
+
+
+def matched_operator(sigma2, U, epoch_of=None, ecorr=None, M=None):
+    """(V [K, N], A [K, K], s) of one pulsar: U [N, K] = [F_rn | F]; the other arguments as pulsar_operator's."""
+    sigma2 = np.asarray(sigma2, dtype=np.float64)
+    if not np.all(sigma2 > 0):
+        raise ValueError("white-noise variances must be positive")
+    s = float(np.mean(sigma2))
+    Ninv = _NoiseInverse(sigma2 / s, epoch_of, None if ecorr is None else np.asarray(ecorr, dtype=np.float64) ** 2 / s)
+    PU = Ninv(U)
+    if M is not None:
+        NiM = Ninv(M)
+        B = M.T @ NiM
+        B = 0.5 * (B + B.T)
+        dg = np.sqrt(np.abs(np.diag(B)))
+        if not np.all(dg > 0):
+            raise ValueError("M^T N^-1 M is singular: a timing-model column vanishes on this pulsar's TOAs")
+        Bn = B / dg[:, None] / dg[None, :]
+        ev = np.linalg.eigvalsh(Bn)
+        if ev[0] <= 1e-12 * ev[-1]:
+            raise ValueError(f"M^T N^-1 M is singular (condition {ev[-1] / max(ev[0], 1e-300):.3g}): the pulsar's TOAs do not "
+                             "constrain its timing model")
+        PU = PU - NiM @ (np.linalg.solve(Bn, (M.T @ PU) / dg[:, None]) / dg[:, None])
+    A = U.T @ PU
+    return np.ascontiguousarray(PU.T), 0.5 * (A + A.T), s
+
+
+class MatchedPlan:
+    """theta-independent operands of the per-realisation-noise OS: V (list of [K, N_a]), A [P, K, K], s [P], S [C], the pairs and
+    the ORF values G [n_orf, n_pairs]."""
+
+    def __init__(self, V, A, s, S, K_rn, pair_a, pair_b, cos_zeta, names, G, nf, T):
+        self.V, self.A, self.s, self.S = V, A, np.asarray(s, dtype=np.float64), S
+        self.P, self.K, self.C, self.K_rn = len(V), A.shape[1], len(S), int(K_rn)
+        self.counts = np.array([v.shape[1] for v in V])
+        self.off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.pair_a, self.pair_b, self.cos_zeta = pair_a, pair_b, cos_zeta
+        self.zeta = np.arccos(cos_zeta)
+        self.names, self.G = names, G
+        self.nf, self.T = int(nf), float(T)
+        if not np.all(np.sum(G ** 2, axis=1) > 0):
+            bad = [n for n, g in zip(names, G) if not np.sum(g ** 2) > 0]
+            raise ValueError(f"ORF(s) {bad} vanish on every pair: their OS is undefined")
+
+    def Vt(self):
+        """[K, sum N_a]: V of every pulsar over the concatenated TOAs (pta_os_project's operand, in blocks of <= 64 rows)."""
+        return np.concatenate(self.V, axis=1)
+
+
+def prepare_matched(toas_s, sigma2, pos, components=14, gamma=13. / 3., orfs=ORF_NAMES, epoch_of=None, ecorr=None, F_rn=None, M=None,
+                    T=None):
+    """MatchedPlan of an array; arguments as prepare()'s, without the prior variances (they come per realisation).  F_rn: None (no
+    pulsar has red noise: K_rn = 0) or a per-pulsar list of [N_a, K_rn] bases (an entry None = a zero block)."""
+    P = len(toas_s)
+    if not 1 <= int(components) <= 32:
+        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
+    nf = int(components)
+    if T is None:
+        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
+    K_rn = 0 if F_rn is None else max([0] + [f.shape[1] for f in F_rn if f is not None])
+    if K_rn + 2 * nf > MATCHED_KMAX:
+        raise ValueError(f"K = K_rn + 2 n_f = {K_rn} + {2 * nf} exceeds the limit of {MATCHED_KMAX} columns per pulsar")
+    S = unit_spectrum(nf, T, gamma)
+    pair_a, pair_b, cz = pair_geometry(pos)
+    names, G = orf_weights(orfs, pair_a, pair_b, cz, P)
+
+    def pick(x, a):
+        return None if x is None else x[a]
+    V, A, s = [], np.zeros((P, K_rn + 2 * nf, K_rn + 2 * nf)), np.zeros(P)
+    for a in range(P):
+        F = fourier_basis(toas_s[a], nf, T)
+        Fr = pick(F_rn, a)
+        if Fr is None:
+            Fr = np.zeros((len(toas_s[a]), K_rn))
+        Va, A[a], s[a] = matched_operator(sigma2[a], np.concatenate([Fr, F], axis=1), pick(epoch_of, a), pick(ecorr, a), pick(M, a))
+        V.append(Va)
+    return MatchedPlan(V, A, s, S, K_rn, pair_a, pair_b, cz, names, G, nf, T)
+
+
+def rn_prior(f, tspan, log10_A, gamma):
+    """sqrt(prior)^2 of red-noise coefficients at frequencies f: pta_rn_amp(f, tspan, log10_A, gamma)^2, same operations."""
+    fyr = 1 / YEAR_IN_SEC
+    prior = (10 ** log10_A) ** 2 * (f / fyr) ** (-gamma) / (12 * np.pi ** 2 * tspan) * YEAR_IN_SEC ** 3
+    return np.sqrt(prior) ** 2
+
+
+def matched_prior(R, s, rn_f=None, rn_tspan=None, rn_phi=None, rn_log10_A=None, rn_gamma=None, nf=0, T=1.0, gw_log10_A=None,
+                  gw_gamma=None):
+    """b [R, P, K]: prior variances over s of every (realisation, pulsar, column) - the NumPy form of pta_os_matched_prior.
+
+    s [P]; rn_f [P, K_rn / 2], rn_tspan [P], rn_phi [P, K_rn] the configured prior variances (or all None: K_rn = 0); rn_log10_A,
+    rn_gamma [R, P] (None = every pulsar as configured; NaN amplitude = that pulsar as configured); nf, T: the OS frequencies
+    (k + 1) / T; gw_log10_A, gw_gamma [R] (None = no GW auto-term: those columns are 0)."""
+    s = np.asarray(s, dtype=np.float64)
+    P = len(s)
+    K_rn = 0 if rn_phi is None else np.shape(rn_phi)[1]
+    b = np.zeros((R, P, K_rn + 2 * nf))
+    if K_rn:
+        phi = np.broadcast_to(np.asarray(rn_phi, dtype=np.float64), (R, P, K_rn)).copy()
+        if rn_log10_A is not None:
+            lA, g = np.asarray(rn_log10_A, dtype=np.float64), np.asarray(rn_gamma, dtype=np.float64)
+            f = np.repeat(np.asarray(rn_f, dtype=np.float64), 2, axis=1)
+            with np.errstate(invalid="ignore"):
+                sampled = rn_prior(f[None], np.asarray(rn_tspan)[None, :, None], lA[:, :, None], g[:, :, None])
+            phi = np.where(np.isnan(lA)[:, :, None], phi, sampled)
+        b[:, :, :K_rn] = phi / s[None, :, None]
+    if gw_log10_A is not None:
+        lA, g = np.asarray(gw_log10_A, dtype=np.float64)[:, None], np.asarray(gw_gamma, dtype=np.float64)[:, None]
+        f = np.repeat(np.arange(1, nf + 1) / float(T), 2)[None, :]
+        fyr = 1.0 / YEAR_IN_SEC
+        phi = 10.0 ** (2.0 * lA) * (fyr ** (g - 3.0) * f ** (-g) / (12 * np.pi ** 2 * T))
+        b[:, :, K_rn:] = phi[:, None, :] / s[None, :, None]
+    return b
+
+
+def matched_solve(A, b, q, S, s, form="cholesky"):
+    """(X [..., C], Z [..., C, C]) of the small dense problems: A [..., K, K], b [..., K], q [..., K] (leading axes broadcast), S [C]
+    the unit spectrum of the last C columns, s the mean white-noise variance (scalar or [...]).  form "cholesky" is what the device
+    evaluates (H = L^-1 D [q | A_F]); "solve" is an independent route (Mc^-1 through np.linalg.solve, no factor) for error bars."""
+    A, b, q = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    K, C = A.shape[-1], len(S)
+    d = np.sqrt(b)
+    Mc = np.eye(K) + d[..., :, None] * A * d[..., None, :]
+    rhs = d[..., :, None] * np.concatenate([q[..., :, None], np.broadcast_to(A[..., :, K - C:], q.shape + (C,))], axis=-1)
+    if form == "cholesky":
+        H = np.linalg.solve(np.linalg.cholesky(Mc), rhs)
+        corr = np.swapaxes(H[..., :, 1:], -1, -2) @ H
+    elif form == "solve":
+        corr = np.swapaxes(rhs[..., :, 1:], -1, -2) @ np.linalg.solve(Mc, rhs)
+    else:
+        raise ValueError(f"form={form!r}: 'cholesky' or 'solve'")
+    rs = np.sqrt(S)
+    s = np.asarray(s, dtype=np.float64)
+    X = rs * (q[..., K - C:] - corr[..., :, 0]) / s[..., None]
+    Z = rs[:, None] * (A[..., K - C:, K - C:] - corr[..., :, 1:]) * rs[None, :] / s[..., None, None]
+    return X, 0.5 * (Z + np.swapaxes(Z, -1, -2))
+
+
+def matched_from_XZ(plan, X, Z):
+    """the pair half: dict of num, den [R, n_pairs], A2, sigma, snr [R, n_orf], rho, sigma_pair [R, n_pairs] from X [R, P, C], Z [R, P, C, C]."""
+    num = np.einsum("rpc,rpc->rp", X[:, plan.pair_a], X[:, plan.pair_b])
+    den = np.einsum("rpij,rpij->rp", Z[:, plan.pair_a], Z[:, plan.pair_b])
+    norm = den @ (plan.G ** 2).T
+    A2 = (num @ plan.G.T) / norm
+    sigma = norm ** -0.5
+    return dict(X=X, Z=Z, num=num, den=den, A2=A2, sigma=sigma, snr=A2 / sigma, rho=num / den, sigma_pair=den ** -0.5)
+
+
+def matched_from_rows(plan, rows, b, form="cholesky"):
+    """the whole per-realisation OS under prior variances b [R, P, K] of rows [R, sum N_a], in NumPy (matched_from_XZ's dict)."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    R = rows.shape[0]
+    X, Z = np.zeros((R, plan.P, plan.C)), np.zeros((R, plan.P, plan.C, plan.C))
+    for a in range(plan.P):
+        q = rows[:, plan.off[a]:plan.off[a + 1]] @ plan.V[a].T
+        X[:, a], Z[:, a] = matched_solve(plan.A[a], b[:, a], q, plan.S, plan.s[a], form=form)
+    return matched_from_XZ(plan, X, Z)
