@@ -647,6 +647,43 @@ int pta_os_matched_pairs(const double *X, const double *Z, int P, int C, int R, 
                          const double *G, const double *G2, int n_orf, double *A2, int64_t ld_a2, double *sigma, int64_t ld_sigma, double *rho,
                          double *sigma_pair, int64_t ld_pair, void *stream);
 
+/* ---- marginalised log-likelihood on a grid of noise parameters (ABI 8, additive) ----
+ * The noise model is the one of the statistic above (white noise, ECORR and the timing model fixed and the timing model marginalised
+ * with a flat prior; red noise on the K_rn red-noise columns, a common uncorrelated process with the GWB spectrum on the last C).
+ * Host NumPy (optimal_statistic.py: lnl_operator) builds per pulsar V, A and s as above, the m <= 16 timing-model rows
+ * G = chol(M^T N'^-1 M)^-1 M^T N'^-1, dinv = 1 / d (N' = diag(d) + ECORR epochs), the Sherman-Morrison weights g_e of the epochs and
+ * the constant c_a = ln det N_a + ln det(M^T N_a^-1 M) + (N_a - m) ln 2 pi.  pta_os_project over the K + m rows of [V; G] (in blocks of
+ * q_block rows, Y = q + P * k0) gives q; element (r, a, k) lies at q[r * ld_q + P * k0 + a * cb + (k - k0)], k0 = (k / q_block) * q_block,
+ * cb = min(q_block, K + m - k0).  With b [G, P, K] the prior variances of the G grid points (pta_os_matched_prior with the grid in place
+ * of the realisations), D = diag(sqrt b) and Mc = I + D A D = L L^T:
+ *     ln L[g, a, r] = -1/2 [ (r^T P0' r - || L^-1 D q ||^2) / s[a] + 2 sum_k ln L_kk + c[a] ]
+ * K <= 128 (PTA_E_ARG beyond, as for C > K and NULL operands).  Every value is bit-identical whatever R, G and the chunks it is
+ * computed in; no atomics.
+ *
+ * pta_lnl_quad: r0[r * P + a] = sum_i x_i^2 dinv_i - sum_e g_e (sum_{i in e} x_i dinv_i)^2 over the TOAs psr_off[a] .. psr_off[a + 1] of row r,
+ * x_i = r_i - sum_{k < m} Ht[k * ldh + psr_off[a] + i] q[r, a, K + k] the residual of the timing-model fit (Ht [m, sum N_a] the rows of
+ * H^T, H = M (M^T N'^-1 M)^-1/2, so that H G r = M beta_hat): the N'^-1 norm of x equals r^T N'^-1 r - || G r ||^2 without its cancellation.  Epochs need not be contiguous in TOA order: pulsar a owns epochs psr_ep[a] .. psr_ep[a + 1]
+ * (psr_ep [P + 1]; NULL = no ECORR anywhere), epoch e the entries ep_ptr[e] .. ep_ptr[e + 1] of ep_idx (TOA indices within the pulsar)
+ * and the weight ep_g[e].  q and Ht may be NULL when m = 0.  One workgroup per (r, a), fixed summation order.                              */
+int pta_lnl_quad(const double *rows, int64_t ld_rows, int R, const int32_t *psr_off, int P, const double *dinv, const int32_t *psr_ep,
+                 const int32_t *ep_ptr, const int32_t *ep_idx, const double *ep_g, const double *q, int64_t ld_q, int q_block, int K, int m,
+                 const double *Ht, int64_t ldh, double *r0, void *stream);
+/* pta_lnl_factor: per (g, a) the Cholesky factor of Mc from A [P, K, K] (symmetric) and b [G, P, K] (>= 0; zeros leave identity rows; Mc
+ * has eigenvalues >= 1, so the factorisation cannot fail), logdet[g * P + a] = 2 sum_k ln L_kk, and the operator of the blocked
+ * substitution, stored transposed: Lt[((g * P + a) * K + k) * K + i] = L[i, k], inside the 16 x 16 diagonal blocks (i / 16 == k / 16) the
+ * inverse of that block of L instead, zeros for i < k.  One workgroup per (g, a), packed factor in LDS (66 KiB at K = 128).  C (the
+ * GWB columns) is checked against K only.                                                                                           */
+int pta_lnl_factor(const double *A, int P, int K, int C, int G, const double *b, double *Lt, double *logdet, void *stream);
+/* pta_lnl_apply: lnl_pulsar[g * ld_g + a * ld_a + r] = ln L[g, a, r] for g < G, a < P, r < R from pta_lnl_factor's Lt and logdet, the same
+ * b, q (Kt = K + m operator rows in the layout above; rows >= K are not read), r0 [R, P], s [P], c [P].  y = L^-1 D q is a forward
+ * substitution in blocks of 16 rows on the fp64 matrix cores (v_mfma_f64_16x16x4_f64): the blocks left of the diagonal multiply the
+ * y already found, the inverted diagonal block finishes the block row.  One workgroup per pulsar x 128 realisations x a run of grid
+ * points, the operator staged in LDS (up to 145 KiB); the zero upper triangle is never touched.                                      */
+int pta_lnl_apply(const double *Lt, const double *logdet, const double *b, int P, int K, int C, int G, const double *q, int64_t ld_q, int q_block,
+                  int Kt, int R, const double *r0, const double *s, const double *c, double *lnl_pulsar, int64_t ld_g, int64_t ld_a, void *stream);
+/* pta_lnl_reduce: lnl[g * ld_lnl + r] = sum_a lnl_pulsar[g * ld_g + a * ld_a + r], pulsars in ascending order.                          */
+int pta_lnl_reduce(const double *lnl_pulsar, int64_t ld_g, int64_t ld_a, int P, int G, int R, double *lnl, int64_t ld_lnl, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays
  * back to rank 0"): realisations are sharded by contiguous row ranges - rank r owns rows [a_r, b_r) of the [total_rows x n_cols]

@@ -408,3 +408,204 @@ def matched_from_rows(plan, rows, b, form="cholesky"):
         q = rows[:, plan.off[a]:plan.off[a + 1]] @ plan.V[a].T
         X[:, a], Z[:, a] = matched_solve(plan.A[a], b[:, a], q, plan.S, plan.s[a], form=form)
     return matched_from_XZ(plan, X, Z)
+
+
+# ---------------------------------------------------------------- marginalised log-likelihood on a theta grid -----------------
+# The noise model is the matched OS's (white noise, ECORR and the timing model fixed; red noise on the K_rn red-noise columns, a
+# common uncorrelated process with the GWB spectrum on the last C columns).  With the timing model marginalised under a flat prior,
+#
+#     -2 ln L_a(r, theta) = [ r^T P0' r - || L^-1 D q ||^2 ] / s  +  2 sum_k ln L_kk  +  c_a
+#     q = V r,  D = diag(sqrt b(theta)),  Mc = I + D A D = L L^T
+#     c_a = ln det N_a + ln det(M^T N_a^-1 M) + (N_a - m) ln 2 pi                     (theta-independent)
+#
+# r^T P0' r = r^T N'^-1 r - || G r ||^2 with N' = diag(d) + ECORR epochs (Sherman-Morrison weights g_e) and G = chol(M^T N'^-1 M)^-1
+# M^T N'^-1 (m rows).  It is evaluated as x^T N'^-1 x = sum x_i^2 / d_i - sum_e g_e (sum_{i in e} x_i / d_i)^2 of the fit residual
+# x = r - H G r, H = M (M^T N'^-1 M)^-1/2: un-fitted rows carry most of their power inside the span of M, and the difference of the
+# two large terms would lose (|r| / |x|)^2 eps (3e-11 of r^T P0' r on the engine's realisations).  Mc, L and ln det depend on (theta_g, pulsar) alone: one factorisation
+# serves every realisation, which is what pta_lnl_factor / pta_lnl_apply do for a whole grid of theta.
+def lnl_operator(sigma2, U, epoch_of=None, ecorr=None, M=None):
+    """theta-independent operands of one pulsar's likelihood, a dict: V [K, N], A [K, K], s (matched_operator's), Gt [m, N] (the
+    timing-model rows G; m = 0 without a timing model), Ht [m, N] (H^T, H G r = M beta_hat), dinv [N] = 1 / d, the epoch -> TOA lists ep_ptr [E + 1], ep_idx [sum of
+    the epochs' sizes] (TOA indices within the pulsar, epochs in ascending order, TOAs of an epoch in TOA order; E = 0 without
+    ECORR), ep_g [E], and the constant c."""
+    V, A, s = matched_operator(sigma2, U, epoch_of, ecorr, M)
+    d = np.asarray(sigma2, dtype=np.float64) / s
+    N = len(d)
+    j = None if ecorr is None else np.asarray(ecorr, dtype=np.float64) ** 2 / s
+    Ninv = _NoiseInverse(d, epoch_of, j)
+    logdet_N = N * np.log(s) + float(np.sum(np.log(d)))
+    ep_ptr, ep_idx, ep_g = np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
+    if Ninv.ep is not None:
+        order = np.argsort(Ninv.ep, kind="stable")
+        ep_ptr = np.searchsorted(Ninv.ep[order], np.arange(Ninv.E + 1)).astype(np.int32)
+        ep_idx, ep_g = order.astype(np.int32), Ninv.g
+        se = _epoch_sums((1.0 / d)[:, None], Ninv.ep, Ninv.E)[:, 0]
+        logdet_N += float(np.sum(np.log1p(j * se)))
+    m = 0 if M is None else M.shape[1]
+    Gt = Ht = np.zeros((0, N))
+    c = logdet_N + (N - m) * np.log(2 * np.pi)
+    if m:
+        NiM = Ninv(M)
+        B = M.T @ NiM
+        B = 0.5 * (B + B.T)
+        dg = np.sqrt(np.abs(np.diag(B)))                      # matched_operator has refused a singular B
+        Lb = np.linalg.cholesky(B / dg[:, None] / dg[None, :])
+        Gt = np.linalg.solve(Lb, (NiM / dg[None, :]).T)
+        Ht = np.linalg.solve(Lb, (M / dg[None, :]).T)
+        c += 2 * float(np.sum(np.log(dg))) + 2 * float(np.sum(np.log(np.diag(Lb)))) - m * np.log(s)
+    return dict(V=V, A=A, s=s, Gt=np.ascontiguousarray(Gt), Ht=np.ascontiguousarray(Ht), dinv=1.0 / d, ep_ptr=ep_ptr, ep_idx=ep_idx, ep_g=ep_g, c=float(c))
+
+
+class LnlPlan:
+    """theta-independent operands of the likelihood of an array: per pulsar V [K, N_a], Gt [m, N_a], the epoch lists; A [P, K, K],
+    s [P], c [P]; dinv over the concatenated TOAs.  The device reads Vt() (V and Gt stacked: K + m operator rows), dinv and the
+    concatenated epoch lists of epochs()."""
+
+    def __init__(self, ops, K_rn, nf, T):
+        self.V, self.Gt, self.Ht = [o["V"] for o in ops], [o["Gt"] for o in ops], [o["Ht"] for o in ops]
+        self.A = np.stack([o["A"] for o in ops])
+        self.s, self.c = np.array([o["s"] for o in ops]), np.array([o["c"] for o in ops])
+        self.P, self.K, self.K_rn, self.C = len(ops), self.A.shape[1], int(K_rn), 2 * int(nf)
+        self.m = max(g.shape[0] for g in self.Gt)
+        self.counts = np.array([v.shape[1] for v in self.V])
+        self.off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.dinv = np.concatenate([o["dinv"] for o in ops])
+        self.ep = [(o["ep_ptr"], o["ep_idx"], o["ep_g"]) for o in ops]
+        self.nf, self.T = int(nf), float(T)
+
+    def Vt(self):
+        """[K + m, sum N_a]: V, then the timing-model rows G (zero rows where a pulsar has fewer than m), over the concatenated TOAs."""
+        out = np.zeros((self.K + self.m, int(self.off[-1])))
+        for a in range(self.P):
+            out[:self.K, self.off[a]:self.off[a + 1]] = self.V[a]
+            out[self.K:self.K + self.Gt[a].shape[0], self.off[a]:self.off[a + 1]] = self.Gt[a]
+        return out
+
+    def Ht_all(self):
+        """[m, sum N_a]: the rows of H^T of every pulsar over the concatenated TOAs (pta_lnl_quad's operand)."""
+        out = np.zeros((self.m, int(self.off[-1])))
+        for a in range(self.P):
+            out[:self.Ht[a].shape[0], self.off[a]:self.off[a + 1]] = self.Ht[a]
+        return out
+
+    def epochs(self):
+        """(psr_ep [P + 1], ep_ptr [E + 1], ep_idx [n_idx], ep_g [E]) int32 / float64: the pulsars' epochs concatenated, ep_idx
+        holding TOA indices within the pulsar, ep_ptr offsets into ep_idx."""
+        psr_ep, ptr, idx, g = [0], [np.zeros(1, dtype=np.int64)], [], []
+        base = 0
+        for p, i, w in self.ep:
+            psr_ep.append(psr_ep[-1] + len(w))
+            ptr.append(base + p[1:].astype(np.int64))
+            idx.append(i)
+            g.append(w)
+            base += int(p[-1])
+        return (np.asarray(psr_ep, dtype=np.int32), np.concatenate(ptr).astype(np.int32),
+                np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, dtype=np.int32), np.concatenate(g) if g else np.zeros(0))
+
+
+def prepare_lnl(toas_s, sigma2, components=14, epoch_of=None, ecorr=None, F_rn=None, M=None, T=None):
+    """LnlPlan of an array; arguments as prepare_matched()'s (no positions and no ORFs: the likelihood is a sum over pulsars)."""
+    P = len(toas_s)
+    if not 1 <= int(components) <= 32:
+        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
+    nf = int(components)
+    if T is None:
+        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
+    K_rn = 0 if F_rn is None else max([0] + [f.shape[1] for f in F_rn if f is not None])
+    if K_rn + 2 * nf > MATCHED_KMAX:
+        raise ValueError(f"K = K_rn + 2 n_f = {K_rn} + {2 * nf} exceeds the limit of {MATCHED_KMAX} columns per pulsar")
+
+    def pick(x, a):
+        return None if x is None else x[a]
+    ops = []
+    for a in range(P):
+        F = fourier_basis(toas_s[a], nf, T)
+        Fr = pick(F_rn, a)
+        if Fr is None:
+            Fr = np.zeros((len(toas_s[a]), K_rn))
+        ops.append(lnl_operator(sigma2[a], np.concatenate([Fr, F], axis=1), pick(epoch_of, a), pick(ecorr, a), pick(M, a)))
+    return LnlPlan(ops, K_rn, nf, T)
+
+
+def lnl_quad(plan, rows):
+    """r0 [R, P] = r_a^T P0' r_a of rows [R, sum N_a] (NumPy; the streaming pass of pta_lnl_quad and its timing-model term)."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    out = np.zeros((rows.shape[0], plan.P))
+    for a in range(plan.P):
+        r = rows[:, plan.off[a]:plan.off[a + 1]]
+        r = r - (r @ plan.Gt[a].T) @ plan.Ht[a]          # the residual of the timing-model fit
+        w = r * plan.dinv[plan.off[a]:plan.off[a + 1]][None, :]
+        t = np.sum(r * w, axis=1)
+        ptr, idx, g = plan.ep[a]
+        if len(g):
+            es = np.add.reduceat(w[:, idx], ptr[:-1], axis=1)
+            t = t - np.sum(g[None, :] * es ** 2, axis=1)
+        out[:, a] = t
+    return out
+
+
+def lnl_solve(A, b, q, r0, s, c, form="cholesky"):
+    """ln L [R, G] of one pulsar: A [K, K], b [G, K] prior variances over s, q [R, K] = V r, r0 [R] = r^T P0' r, s and c scalars.
+    form "cholesky" is the device's route (factor Mc, y = L^-1 D q by substitution, || y ||^2, 2 sum ln L_kk); "solve" goes through
+    np.linalg.solve and slogdet without a factor, for error bars."""
+    A, b, q = np.asarray(A, dtype=np.float64), np.atleast_2d(np.asarray(b, dtype=np.float64)), np.atleast_2d(np.asarray(q, dtype=np.float64))
+    K = A.shape[-1]
+    d = np.sqrt(b)
+    Mc = np.eye(K) + d[:, :, None] * A[None] * d[:, None, :]
+    if form == "cholesky":
+        L = np.linalg.cholesky(Mc)
+        logdet = 2.0 * np.sum(np.log(np.diagonal(L, axis1=-2, axis2=-1)), axis=-1)
+        quad = np.sum(np.linalg.solve(L, d[:, :, None] * q.T[None]) ** 2, axis=1)      # [G, R]
+    elif form == "solve":
+        logdet = np.linalg.slogdet(Mc)[1]
+        dq = d[:, :, None] * q.T[None]                                                 # [G, K, R]
+        quad = np.sum(dq * np.linalg.solve(Mc, dq), axis=1)
+    else:
+        raise ValueError(f"form={form!r}: 'cholesky' or 'solve'")
+    r0 = np.asarray(r0, dtype=np.float64)
+    return (-0.5 * ((r0[None, :] - quad) / s + logdet[:, None] + c)).T
+
+
+def lnl_from_rows(plan, rows, b, form="cholesky"):
+    """(lnl_pulsar [R, P, G], lnl [R, G]) of rows [R, sum N_a] under prior variances b [G, P, K] (matched_prior with the grid in
+    place of the realisations), in NumPy; lnl sums the pulsars in ascending order."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    b = np.asarray(b, dtype=np.float64)
+    r0 = lnl_quad(plan, rows)
+    lp = np.zeros((rows.shape[0], plan.P, b.shape[0]))
+    tot = np.zeros((rows.shape[0], b.shape[0]))
+    for a in range(plan.P):
+        q = rows[:, plan.off[a]:plan.off[a + 1]] @ plan.V[a].T
+        lp[:, a] = lnl_solve(plan.A[a], b[:, a], q, r0[:, a], plan.s[a], plan.c[a], form=form)
+        tot = tot + lp[:, a]
+    return lp, tot
+
+
+GRID_KEYS = ("gwb_log10_A", "gwb_gamma", "rn_log10_A", "rn_gamma")
+
+
+def theta_grid(P=None, **axes):
+    """(grid, shape): the outer product of 1-D axes, flattened in C order (the first axis given varies slowest).  Axes are named
+    by the keys of theta; gwb_* entries come out [G], rn_* entries [G, P] (the same value for every pulsar; needs P).  shape is
+    the tuple of the axes' lengths: lnl.reshape(R, *shape) puts the grid back."""
+    if not axes:
+        raise ValueError("theta_grid: at least one axis")
+    unknown = set(axes) - set(GRID_KEYS)
+    if unknown:
+        raise ValueError(f"theta_grid: unknown axes {sorted(unknown)} (expected a subset of {list(GRID_KEYS)})")
+    vals = []
+    for k, v in axes.items():
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim != 1 or v.size < 1:
+            raise ValueError(f"theta_grid: axis {k!r} must be 1-D and non-empty, got shape {v.shape}")
+        vals.append(v)
+    mesh = np.meshgrid(*vals, indexing="ij")
+    grid = {}
+    for k, m in zip(axes, mesh):
+        flat = np.ascontiguousarray(m.reshape(-1))
+        if k.startswith("rn_"):
+            if P is None:
+                raise ValueError(f"theta_grid: axis {k!r} needs the number of pulsars P")
+            flat = np.ascontiguousarray(np.repeat(flat[:, None], int(P), axis=1))
+        grid[k] = flat
+    return grid, tuple(len(v) for v in vals)
