@@ -684,6 +684,36 @@ int pta_lnl_apply(const double *Lt, const double *logdet, const double *b, int P
 /* pta_lnl_reduce: lnl[g * ld_lnl + r] = sum_a lnl_pulsar[g * ld_g + a * ld_a + r], pulsars in ascending order.                          */
 int pta_lnl_reduce(const double *lnl_pulsar, int64_t ld_g, int64_t ld_a, int P, int G, int R, double *lnl, int64_t ld_lnl, void *stream);
 
+/* ---- continuous-wave F-statistics per realisation (ABI 8, additive) ----
+ * Fixed-noise Fp (incoherent, per GW frequency) and earth-term Fe (coherent, per GW frequency and sky point).  Host NumPy
+ * (pta_replicator_amd/f_statistic.py) builds per pulsar W_a [2 J, N_a] (rows 2 j, 2 j + 1 = [sin, cos](2 pi f_j t)^T P_a^-1), the
+ * inverses of G_aj = E_aj^T P_a^-1 E_aj, the antenna patterns phi [P, S, 2] = (F+, Fx) and the inverses of
+ * M_js = sum_a (phi_as phi_as^T) (x) G_aj.  Per realisation q_raj = Q[r, a, 2 j : 2 j + 2]:
+ *     Fp[r, j] = 1/2 sum_a q^T G_aj^-1 q,    Fe[r, j, s] = 1/2 N^T M_js^-1 N,  N = sum_a phi_as (x) q_raj  (+ sin, + cos, x sin, x cos).
+ * Every value is bit-identical whatever R, the chunk or the output mode it is computed in; no atomics.
+ *
+ * pta_fstat_project: Q[r * ld_q + a * C + c] = sum_i Wt[c * ldw + psr_off[a] + i] * rows[r * ld_rows + psr_off[a] + i] for r < R, a < P,
+ * c < C = 2 J (even, 2 .. PTA_FSTAT_CMAX), i < psr_off[a + 1] - psr_off[a]: pta_os_project's contract without its 64-column limit.  A
+ * ragged grouped GEMM on v_mfma_f64_16x16x4_f64: all pulsars in one launch, one workgroup per pulsar x 128 (64 in a small launch)
+ * realisations x up to 128 columns, K over the pulsar's own TOAs in ascending slabs of 16 (zeros past its end in both operands), no split-K.               */
+#define PTA_FSTAT_CMAX 4096
+#define PTA_FSTAT_PMAX 128
+#define PTA_FSTAT_SKY_TILE 64
+int pta_fstat_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R, double *Q,
+                      int64_t ld_q, void *stream);
+/* pta_fstat_fp: fp[r * ld_fp + j] = 1/2 sum_a (g0 x^2 + 2 g1 x y + g2 y^2), (x, y) = Q[r * ld_q + a * 2 J + 2 j + (0, 1)], (g0, g1, g2) =
+ * Ginv[(a * J + j) * 3 + (0, 1, 2)] the packed symmetric G_aj^-1; pulsars in ascending order.  Q 16-byte aligned, ld_q even.       */
+int pta_fstat_fp(const double *Q, int64_t ld_q, int P, int J, int R, const double *Ginv, double *fp, int64_t ld_fp, void *stream);
+/* pta_fstat_fe: phi[(a * S + s) * 2 + (0, 1)] = (F+, Fx); Minv[(j * S + s) * 10 + i] the upper triangle of M_js^-1, row-major.  2 <= P <=
+ * PTA_FSTAT_PMAX.  Two output modes, one per call: fe != NULL writes the full map fe[r * ld_fe + j * S + s] (fe_max, fe_arg NULL);
+ * fe == NULL writes fe_max[r * ld_max + j] = max_s Fe and fe_arg[r * ld_arg + j] = the lowest sky index attaining it, reduced in the
+ * kernel over 16 sky points at a time into the workspaces part_val, part_arg [R * J * pta_fstat_fe_tiles(S)] and folded over those
+ * in ascending order - the map is never written.  N is formed on the fp64 matrix cores (K = P in groups of four pulsars, ascending) and
+ * goes into the quadratic form in registers.                                                                                        */
+int64_t pta_fstat_fe_tiles(int S);
+int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, const double *phi, int S, const double *Minv, double *fe, int64_t ld_fe,
+                 double *fe_max, int64_t ld_max, int32_t *fe_arg, int64_t ld_arg, double *part_val, int32_t *part_arg, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays
  * back to rank 0"): realisations are sharded by contiguous row ranges - rank r owns rows [a_r, b_r) of the [total_rows x n_cols]

@@ -151,6 +151,10 @@ _SIGNATURES = {
     "pta_lnl_factor": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_lnl_apply": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int64, _P]),
     "pta_lnl_reduce": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, c_int64, _P]),
+    "pta_fstat_project": (c_int, [_P, c_int64, c_int, _P, c_int, _P, c_int64, c_int, _P, c_int64, _P]),
+    "pta_fstat_fp": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _P]),
+    "pta_fstat_fe_tiles": (c_int64, [c_int]),
+    "pta_fstat_fe": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, c_int, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "pta_gather_rank0":(c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
     "pta_dgemm": (c_int, [c_int, c_int, c_int, c_int, c_double, _P, c_int64, c_int64, _P, c_int64, c_double, _P, c_int64,
                           c_int, c_int, c_int64, c_int64, c_int64, c_int, _P]),
@@ -165,6 +169,8 @@ CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 OSM_KMAX = 128       # PTA_OSM_KMAX
 LNL_KMAX = 128       # PTA_LNL_KMAX
 LNL_MMAX = 16        # PTA_LNL_MMAX
+FSTAT_CMAX = 4096    # PTA_FSTAT_CMAX
+FSTAT_PMAX = 128     # PTA_FSTAT_PMAX
 TD_STRIP = 256      # PTA_TD_STRIP
 POTRF_ZERO_UPPER, POTRF_NO_LOOKAHEAD, POTRF_SUBSTITUTION, POTRF_VALU, POTRF_REG_STAGING, POTRF_LOCKSTEP, POTRF_DIAG_AHEAD, POTRF_DIAG64 = 1, 2, 4, 8, 32, 64, 128, 16
 POTRF_EPI1 = 0x100000

@@ -1,0 +1,215 @@
+"""Continuous-wave F-statistics (incoherent Fp, earth-term coherent Fe) of the ReplicaEngine's realisations, per realisation, on the
+device.
+
+``prepare_f_statistic(freqs, sky)`` builds the realisation-independent operands on the host from the noise model ``prepare()`` holds
+(pta_replicator_amd/f_statistic.py: W_a = E_a^T P_a^-1 over the frequency grid, G_aj^-1, the antenna patterns phi and M_js^-1) and
+uploads them once; ``f_statistic(rows)`` then costs per chunk of realisations
+
+    pta_fstat_project   Q[r, a, :] = W_a r_a                       ragged grouped GEMM over all pulsars (fp64 MFMA), 2 J columns
+    pta_fstat_fp        Fp[r, j] = 1/2 sum_a q^T G_aj^-1 q          ascending pulsars
+    pta_fstat_fe        Fe[r, j, s] = 1/2 N^T M_js^-1 N             N = sum_a phi_as (x) q_raj on the matrix cores, never stored;
+                                                                   the full map, or (sky_max) its maximum and argmax per (r, j)
+
+and ``generate_f_statistic(R)`` runs generate / generate_td / generate(theta=...) chunk by chunk into one reused buffer with the
+statistics behind each chunk, keeping only the statistics.  A realisation's statistics are bit-identical whatever chunk, row or
+output mode they are computed in.
+
+The noise weights are the configured ones (white noise + ECORR + red noise, optionally the GWB auto-term, timing model
+marginalised): a statistic matched to per-realisation noise parameters theta is out of scope, as are the pulsar term and frequency
+evolution across the data span.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _cw, _lib, device as dv
+from . import f_statistic as fst
+from . import optimal_statistic as ost
+from ._position import ra_dec
+
+
+class FStatisticMixin:
+    def prepare_f_statistic(self, freqs, sky=None, timing_model="spin", gwb_auto=None, components=14, gamma=13. / 3.):
+        """W, G^-1 (and with a sky grid phi, M^-1) of the array under the configured noise model (white noise + ECORR + red noise,
+        optionally the GWB auto-term), uploaded once.  Returns self.
+
+        freqs: [J] GW frequencies in Hz (finite, > 0); sky: None for Fp only, or a (cos_gwtheta [S], gwphi [S]) pair - the sky grid of
+        Fe, in the angles of theta's cw_cos_gwtheta / cw_gwphi (needs at least two pulsars); timing_model: "spin", "astrometric" or
+        None; gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False =
+        off; components, gamma: the frequencies k / T and spectral index of that auto-term, as in prepare_optimal_statistic.
+
+        The weights are those of the configured noise model for every realisation: a statistic matched to per-realisation theta is
+        out of scope.  A frequency at which a pulsar's sin / cos pair is not constrained (one the spin-down fit absorbs) is refused."""
+        f = fst.check_freqs(freqs)
+        sky = fst.check_sky(sky)
+        if timing_model not in ("spin", "astrometric", None):
+            raise ValueError(f"timing_model={timing_model!r} must be 'spin', 'astrometric' or None")
+        if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
+            raise ValueError(f"components={components!r}: an integer 1 .. 32")
+        J = len(f)
+        if 2 * J > _lib.FSTAT_CMAX:
+            raise ValueError(f"{J} frequencies: one preparation holds at most {_lib.FSTAT_CMAX // 2}")
+        if sky is not None and self.P < 2:
+            raise ValueError("the coherent Fe statistic needs at least two pulsars; Fp alone (sky=None) works for one")
+        if sky is not None and self.P > _lib.FSTAT_PMAX:
+            raise ValueError(f"the Fe kernel holds at most {_lib.FSTAT_PMAX} pulsars, got {self.P}")
+        if self._wn is None:
+            raise ValueError("the F-statistic needs measurement noise (set_white_noise): without it the noise covariance is singular")
+        if 2 * J * self.n_toa * 8 > int(self.workspace_bytes):
+            raise ValueError(f"the projection operator [2 J = {2 * J}, n_toa = {self.n_toa}] takes {2 * J * self.n_toa * 8} bytes, more than "
+                             f"workspace_bytes = {int(self.workspace_bytes)}: use fewer frequencies per preparation or raise workspace_bytes")
+        gw_lA = None
+        if gwb_auto is None:
+            gw_lA = float(self._gw["A"]) if self._gw is not None else None
+        elif gwb_auto is False:
+            pass
+        elif isinstance(gwb_auto, (bool, np.bool_)):
+            raise ValueError("gwb_auto: None, a log10 amplitude, or False")
+        else:
+            gw_lA = float(gwb_auto)
+        if not self._prepared:
+            self.prepare()
+        from .simulate import timing_design_matrix
+        P = self.P
+        toas = [m * 86400.0 for m in self.mjd]
+        wa, wb = self.d_wn_a.cpu().numpy(), self.d_wn_b.cpu().numpy()
+        sigma2 = [wa[self.off[a]:self.off[a + 1]] ** 2 + wb[self.off[a]:self.off[a + 1]] ** 2 for a in range(P)]
+        epoch_of = ecorr = None
+        if self._ec is not None:
+            epoch_of, ecorr = self.epoch_of, self.ecorrvec
+        F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]     # the low-rank part of C_a: red noise, then the GWB auto-term
+        if self.plan.rn_k:
+            for a in range(P):
+                F_low[a].append(self._rn_basis_host(a))
+                phi_low[a].append(self.rn_amp[a] ** 2)
+        if gw_lA is not None:
+            T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
+            S = ost.unit_spectrum(int(components), T, float(gamma))
+            for a in range(P):
+                F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
+                phi_low[a].append(10.0 ** (2 * gw_lA) * S)
+        low = bool(F_low[0])
+        M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
+        phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs]) if sky is not None else None
+        plan = fst.prepare(toas, sigma2, f, phat=phat, sky=sky, epoch_of=epoch_of, ecorr=ecorr,
+                           F_rn=[np.concatenate(x, axis=1) for x in F_low] if low else None,
+                           phi_rn=[np.concatenate(x) for x in phi_low] if low else None, M=M)
+        self._fs = dict(plan=plan, engine_plan=self.plan, J=J, S=plan.S, Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), Ginv=dv.f64(plan.Ginv_packed()),
+                        freqs=dv.f64(f), phi=None, Minv=None, ntile=0, ws=None)
+        if sky is not None:
+            self._fs.update(phi=dv.f64(plan.phi), Minv=dv.f64(plan.Minv_packed()), ntile=int(_lib.lib.pta_fstat_fe_tiles(plan.S)))
+        return self
+
+    def _fs_state(self, what, sky_max=False):
+        st = getattr(self, "_fs", None)
+        if st is None:
+            raise ValueError(f"{what}: the F-statistic is not prepared (prepare_f_statistic first)")
+        if not self._prepared or st["engine_plan"] is not self.plan:
+            raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_f_statistic(): call it again")
+        if sky_max and st["phi"] is None:
+            raise ValueError(f"{what}: sky_max=True needs a sky grid (prepare_f_statistic(freqs, sky=...))")
+        return st
+
+    def _fs_chunk(self, st, R, sky_max, with_rows):
+        """realisations per launch sequence: Q [P, 2 J], the per-tile maxima of sky_max (and the generated rows) within workspace_bytes.
+        The outputs (fp, fe or fe_max / fe_arg of all R realisations) are the call's result, not workspace."""
+        per_real = 8 * self.P * 2 * st["J"] + (12 * st["J"] * st["ntile"] if sky_max else 0) + (8 * self.n_toa if with_rows else 0)
+        return max(1, min(R, int(self.workspace_bytes) // per_real))
+
+    def _fs_out(self, st, R, sky_max):
+        J, S = st["J"], st["S"]
+        out = {"fp": dv.empty((R, J)), "fe": None, "fe_max": None, "fe_arg": None}
+        if st["phi"] is not None:
+            if sky_max:
+                out["fe_max"], out["fe_arg"] = dv.empty((R, J)), dv.empty((R, J), dtype=torch.int32)
+            else:
+                out["fe"] = dv.empty((R, J, S))
+        return out
+
+    def _fs_result(self, st, out):
+        res = {"fp": out["fp"], "freqs": st["freqs"]}
+        res.update({k: out[k] for k in ("fe", "fe_max", "fe_arg") if out[k] is not None})
+        return res
+
+    def _fs_launch(self, rows, n, lo, out):
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: pta_fstat_project into the reused Q buffer,
+        pta_fstat_fp, pta_fstat_fe - all on the current stream"""
+        st = self._fs
+        P, J, S = self.P, st["J"], st["S"]
+        sky_max = out["fe_max"] is not None
+        ws = st["ws"]
+        if ws is None or ws["n"] < n or (sky_max and ws["pv"] is None):
+            st["ws"] = None
+            ws = st["ws"] = dict(n=n, Q=dv.empty((n, P * 2 * J)), pv=dv.empty((n * J * st["ntile"],)) if sky_max else None,
+                                 pa=dv.empty((n * J * st["ntile"],), dtype=torch.int32) if sky_max else None)
+        s = dv.stream_ptr()
+        Q = ws["Q"]
+        _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, 2 * J, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
+                  dv.ptr(Q), P * 2 * J, s)
+        fp = out["fp"]
+        _lib.call("pta_fstat_fp", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["Ginv"]), ctypes.c_void_p(fp.data_ptr() + 8 * lo * J), J, s)
+        if st["phi"] is None:
+            return
+        if sky_max:
+            _lib.call("pta_fstat_fe", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]), None, 0,
+                      ctypes.c_void_p(out["fe_max"].data_ptr() + 8 * lo * J), J, ctypes.c_void_p(out["fe_arg"].data_ptr() + 4 * lo * J), J,
+                      dv.ptr(ws["pv"]), dv.ptr(ws["pa"]), s)
+        else:
+            _lib.call("pta_fstat_fe", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]),
+                      ctypes.c_void_p(out["fe"].data_ptr() + 8 * lo * J * S), J * S, None, 0, None, 0, None, None, s)
+
+    def f_statistic(self, rows, sky_max=False):
+        """Fp and Fe of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
+        generate_td, generate_sampled, or the caller's own residuals).  Returns a dict of device tensors: fp [R, J], freqs [J]; with a
+        sky grid fe [R, J, S], or with sky_max=True fe_max [R, J] and fe_arg [R, J] (int32: the sky index of the maximum, the lowest
+        on ties) - the map is then never written.  The noise weights are the configured ones (no per-realisation theta).  Rows are
+        processed in chunks that keep the workspace (Q, the per-tile maxima of sky_max) within workspace_bytes; the returned tensors
+        are the caller's result and lie outside that budget: the full map takes R J S 8 bytes, and sky_max=True is the way to stay
+        small."""
+        st = self._fs_state("f_statistic", sky_max)
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
+            raise ValueError("rows must be a float64 device tensor")
+        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
+        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
+            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
+        R = int(rows.shape[0])
+        out = self._fs_out(st, R, sky_max)
+        step = self._fs_chunk(st, R, sky_max, with_rows=False)
+        for lo in range(0, R, step):
+            self._fs_launch(rows[lo:lo + step], min(step, R - lo), lo, out)
+        return self._fs_result(st, out)
+
+    def generate_f_statistic(self, R, r0=0, theta=None, td=False, chunk=1024, sky_max=False):
+        """Fp / Fe of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td
+        with td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations, cw_* keys included); only
+        the statistics are kept.  Same results as f_statistic(generate(R, r0, ...), sky_max), bit for bit, whatever the chunk.  The
+        chunk is cut so that the buffer and Q stay within workspace_bytes.  theta only shapes the data: the statistic's noise weights
+        stay the configured ones."""
+        st = self._fs_state("generate_f_statistic", sky_max)
+        R, r0, chunk = int(R), int(r0), int(chunk)
+        if R < 1 or chunk < 1 or r0 < 0:
+            raise ValueError(f"generate_f_statistic: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
+        hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
+        chunk = max(1, min(chunk, self._fs_chunk(st, R, sky_max, with_rows=True)))
+        buf = getattr(self, "_fs_rows", None)
+        if buf is None or buf.shape[0] < chunk:
+            self._fs_rows = None
+            buf = self._fs_rows = dv.empty((chunk, self.n_toa))
+        out = self._fs_out(st, R, sky_max)
+
+        def rows_of(part, lo, n):
+            return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
+        for lo in range(0, R, chunk):
+            n = min(chunk, R - lo)
+            rows = buf[:n]
+            if td:
+                self.generate_td(n, r0=r0 + lo, out=rows)
+                if cw:
+                    self._cw_apply(rows_of(cw, lo, n), n, rows)
+            else:
+                self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
+            self._fs_state("generate_f_statistic")     # generate_td / generate may have (re)prepared the engine
+            self._fs_launch(rows, n, lo, out)
+        return self._fs_result(st, out)
