@@ -50,7 +50,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * deviate is Philox-4x32-10(key = seed, counter = (pair, stream, realisation)) + Box-Muller.
  * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor),
  * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform),
- * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform). */
+ * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform.  In a catalogue the
+ * field is the source index s, pta_cw_catalog_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -480,6 +481,47 @@ int pta_engine_cw_params(const pta_cw_engine *cw_host, int R, void *stream);
  * cancellation.  A TOA whose contribution is not finite (after the merger) gets 0 (deterministic.py:435,556).  No atomics.  */
 int pta_engine_cw_add(const pta_engine_plan *plan_host, const pta_cw_engine *cw_host, int R, double *out, int64_t ld_out, int accumulate,
                       void *stream);
+
+/* ---------------------------------------------------------------- a catalogue of CW sources per realisation (ABI 8, additive) */
+/* out[(r * S + s) * 8 + j] = lo[j] + (hi[j] - lo[j]) u (one fma), u = uniform u2 of pair j of stream (CW, s), realisation r0 + r: S
+ * independent sources from the same 8 boxes (the source columns of pta_cw_uniform).  Source 0 is pta_cw_uniform's draw bit for bit;
+ * S - 1 must fit the 24-bit stream field.  lo / hi: device [8].                                                              */
+int pta_cw_catalog_uniform(uint64_t seed, uint64_t r0, int R, int S, const double *lo, const double *hi, double *out, void *stream);
+
+/* S sources per realisation, of which realisation r uses the first count[r].  Device pointers.
+ * Table: par[((r * n_psr + a) * n_src + s) * NPAR + k], the source index fastest among the table's rows.  NPAR by mode:
+ *   mode 0: PTA_CW_CATALOG_NPAR_EVOLVE = 16, the row of pta_engine_cw_params;
+ *   mode 1, 2: PTA_CW_CATALOG_NPAR_FOLDED = 8, {Cs0, Cc0, W0, Cs1, Cc1, W1, 0, 0}: the term is Cs0 sin(W0 t) + Cc0 cos(W0 t)
+ *   [+ Cs1 sin(W1 t) + Cc1 cos(W1 t): phase_approx with the pulsar term only], the antenna patterns, inclination and polarisation
+ *   factors, phase0 and the pulsar term's phase offset folded into the constants (csrc/pta_cw_catalog.h).                  */
+#define PTA_CW_CATALOG_NPAR_EVOLVE 16
+#define PTA_CW_CATALOG_NPAR_FOLDED 8
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_src;              /* S >= 1, S - 1 <= 0xFFFFFF */
+  int32_t mode;               /* 0 evolve, 1 phase_approx, 2 monochromatic */
+  int32_t psr_term;           /* 0 / 1 */
+  int32_t amp_is_h;           /* 1: column 4 of a source is log10 h (strain); 0: log10 dist [Mpc] */
+  int32_t has_pdist;          /* 1: pdist is [R x ld_pdist], per realisation (shared by its sources); 0: [n_psr] */
+  double tref;                /* [s] */
+  const double *phat;         /* [n_psr x 3] pulsar unit vectors */
+  const double *pdist;        /* pulsar distances [kpc] */
+  int64_t ld_pdist;           /* >= n_psr (has_pdist = 1) */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *src;          /* [R x ld_src]: source s of realisation r at src[r * ld_src + 8 s .. + 7] (the columns of pta_cw_uniform) */
+  int64_t ld_src;             /* >= 8 n_src */
+  const int32_t *count;       /* [R] sources in use per realisation, 0 .. n_src (clamped to that range), or NULL = n_src each */
+  double *par;                /* [R x n_psr x n_src x NPAR] table written by pta_engine_cw_catalog_params */
+} pta_cw_catalog_engine;
+
+/* the table rows of every (r, a, s) with s < count[r]; rows past the count are neither read nor written.  One thread per row.  */
+int pta_engine_cw_catalog_params(const pta_cw_catalog_engine *cw_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum over s < count[r], ascending, of the residual of source s of realisation r at TOA i (accumulate = 1
+ * adds, 0 writes), over the plan's TOA tiles.  The sum is formed in a register and added once; a source's term that is not finite (a
+ * TOA after its merger) contributes exactly 0, per source.  count[r] = 0 adds 0.  No atomics.                               */
+int pta_engine_cw_catalog_add(const pta_engine_plan *plan_host, const pta_cw_catalog_engine *cw_host, int R, double *out, int64_t ld_out,
+                              int accumulate, void *stream);
 
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,

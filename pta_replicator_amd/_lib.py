@@ -78,6 +78,15 @@ class CwEngine(ctypes.Structure):
     ]
 
 
+class CwCatalogEngine(ctypes.Structure):
+    """pta_cw_catalog_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_src", c_int32), ("mode", c_int32), ("psr_term", c_int32), ("amp_is_h", c_int32), ("has_pdist", c_int32),
+        ("tref", c_double), ("phat", _P), ("pdist", _P), ("ld_pdist", c_int64), ("toa_s", _P), ("src", _P), ("ld_src", c_int64),
+        ("count", _P), ("par", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -134,6 +143,9 @@ _SIGNATURES = {
     "pta_cw_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P]),
     "pta_engine_cw_params": (c_int, [POINTER(CwEngine), c_int, _P]),
     "pta_engine_cw_add": (c_int, [POINTER(EnginePlan), POINTER(CwEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_cw_catalog_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P]),
+    "pta_engine_cw_catalog_params": (c_int, [POINTER(CwCatalogEngine), c_int, _P]),
+    "pta_engine_cw_catalog_add": (c_int, [POINTER(EnginePlan), POINTER(CwCatalogEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
@@ -166,6 +178,7 @@ _SIGNATURES = {
 ENGINE_TILE = 256   # PTA_ENGINE_TILE
 ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX
 CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
+CW_CATALOG_NPAR = (16, 8, 8)  # by mode: PTA_CW_CATALOG_NPAR_EVOLVE, PTA_CW_CATALOG_NPAR_FOLDED (phase_approx, monochromatic)
 OSM_KMAX = 128       # PTA_OSM_KMAX
 LNL_KMAX = 128       # PTA_LNL_KMAX
 LNL_MMAX = 16        # PTA_LNL_MMAX

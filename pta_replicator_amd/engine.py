@@ -401,13 +401,19 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         """realisations per launch sequence: the launch-grid limit of the mix / fused kernels (65536) and the workspace byte
         budget (coef + G0 + G per realisation: 0.68 MB at 68 pulsars, so 8 GiB hold 12 600 realisations; with per-realisation
         theta (hyper=True) also the GWB spectrum-scale row, 8 Nf bytes; with CW theta (cw=True) also the CW source row and the
-        [P, 16] scalar table of pta_engine_cw_params)."""
+        [P, 16] scalar table of pta_engine_cw_params; cw = S, an integer: a catalogue of S sources per realisation, S source rows
+        and the [P, S, 16] table of pta_engine_cw_catalog_params, whose one-launch index range R P S < 2^31 also bounds the batch)."""
         per_real = 8 * self.P * ((self.K if self.plan.rn_k else 0) + 2 * self.plan.gw_npts)
         if hyper and self.plan.gw_npts:
             per_real += 8 * self.grid["Nf"]
+        cap = 65536
         if cw:
-            per_real += 8 * (self.P * _lib.CW_ENGINE_NPAR + _cw.N_SRC + self.P)
-        return int(max(16, min(65536, self.workspace_bytes // max(per_real, 1))))
+            S = 1 if cw is True else int(cw)
+            if S < 1:
+                raise ValueError(f"max_batch: cw must be True, False or a source count >= 1, got {cw!r}")
+            per_real += 8 * (self.P * S * _lib.CW_ENGINE_NPAR + _cw.N_SRC * S + self.P)
+            cap = min(cap, ((1 << 31) - 1) // (self.P * S))
+        return int(max(1 if cap < 16 else 16, min(cap, self.workspace_bytes // max(per_real, 1))))
 
     def generate(self, R, r0=0, out=None, theta=None):
         """out[R, n_toa] (device tensor, seconds): realisations r0 .. r0+R-1, every deviate drawn on chip: one call of
@@ -416,7 +422,9 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         theta: per-realisation GWB / red-noise parameters of realisations r0 .. r0+R-1, a dict with any subset of
         gwb_log10_A [R], gwb_gamma [R], rn_log10_A [R, P], rn_gamma [R, P] (NumPy arrays or tensors; pta_replicator_amd._hyper).
         Keys not given keep their configured values; NaN in rn_log10_A = that pulsar as configured.  With set_cw(), theta may also
-        hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch."""
+        hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch, or a
+        catalogue of S sources per realisation (the same keys with shape [R, S], optional cw_count [R]), summed over the sources and
+        added once by pta_engine_cw_catalog_add."""
         hyper, cw = self._theta_parts(theta, R)
         return self._generate(R, r0, out, hyper, cw)
 
@@ -445,7 +453,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         dev = None if hyper is None else self._theta_device(hyper, R, mask_unconfigured)
         if out is None:
             out = dv.empty((R, self.n_toa))
-        step = self.max_batch(hyper=hyper is not None, cw=bool(cw))
+        step = self.max_batch(hyper=hyper is not None, cw=_cw.n_sources(cw))
         ws = self.workspace(min(R, step))
         hy = None if dev is None else self._hyper_tables()
         gw_theta = dev is not None and dev["gwb_log10_A"] is not None
@@ -554,7 +562,10 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
 
     def _cw_apply(self, cw, R, out, accumulate=True):
         """out[R, n_toa] (+)= the CW term of every row for validated CW theta `cw` (row r = the source of realisation r0 + r): the
-        source table -> pta_engine_cw_params -> pta_engine_cw_add, in batches of max_batch(hyper=True, cw=True)."""
+        source table -> pta_engine_cw_params -> pta_engine_cw_add, in batches of max_batch(hyper=True, cw=True).  Source keys of
+        shape [R, S] are a catalogue (_cw_catalog_apply)."""
+        if _cw.is_catalog(cw):
+            return self._cw_catalog_apply(cw, R, out, accumulate)
         if not self._prepared:
             self.prepare()
         dev = dv.require_gpu()
@@ -589,13 +600,60 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self._cw_keep = src   # the launches above read it asynchronously
         return out
 
+    def _cw_catalog_apply(self, cw, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the sum of the catalogue of every row for validated CW theta `cw` with source keys [R, S] (and cw_count
+        [R]): the [R, S, 8] source table -> pta_engine_cw_catalog_params -> pta_engine_cw_catalog_add (one accumulator per element over
+        the sources, one read-modify-write of out), in batches of max_batch(hyper=True, cw=S)."""
+        if not self._prepared:
+            self.prepare()
+        dev = dv.require_gpu()
+        P, S = self.P, _cw.n_sources(cw)
+
+        def col(x, shape, dtype=torch.float64):
+            if hasattr(x, "data_ptr"):
+                t = x.to(device=dev, dtype=dtype)
+            else:
+                t = torch.as_tensor(np.asarray(x, dtype=np.float64 if dtype is torch.float64 else np.int32), device=dev)
+            return t.reshape(shape)
+        amp = _cw.amp_key(cw)
+        src = torch.stack([col(cw[amp if c == "amp" else "cw_" + c], (R, S)) for c in _cw.COLUMNS], dim=2).contiguous()   # [R, S, 8]
+        has_pd = _cw.PDIST_KEY in cw
+        conf, tb = self._cw, self._cw_tables()
+        pdist = col(cw[_cw.PDIST_KEY], (R, P)).contiguous() if has_pd else tb["pdist"]
+        count = col(cw[_cw.COUNT_KEY], (R,), torch.int32).contiguous() if _cw.COUNT_KEY in cw else None
+        mode = _cw.mode(conf)
+        npar = _lib.CW_CATALOG_NPAR[mode]
+        step = min(R, self.max_batch(hyper=True, cw=S))
+        par = getattr(self, "_cwc_par", None)
+        if par is None or par.numel() < step * P * S * npar:
+            self._cwc_par = None
+            par = self._cwc_par = dv.empty((step * P * S * npar,))
+        c = _lib.CwCatalogEngine()
+        c.n_psr, c.n_src, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = P, S, mode, int(conf["psrTerm"]), int(amp == "cw_log10_h"), int(has_pd)
+        c.tref, c.phat, c.toa_s = conf["tref"], tb["phat"].data_ptr(), self.d_toa_s.data_ptr()
+        c.ld_src, c.ld_pdist, c.par = src.stride(0), (pdist.stride(0) if has_pd else 0), par.data_ptr()
+        s = dv.stream_ptr()
+        for lo in range(0, R, step):
+            n = min(step, R - lo)
+            c.src = src.data_ptr() + 8 * lo * src.stride(0)
+            c.pdist = pdist.data_ptr() + (8 * lo * pdist.stride(0) if has_pd else 0)
+            c.count = None if count is None else count.data_ptr() + 4 * lo
+            _lib.call("pta_engine_cw_catalog_params", ctypes.byref(c), n, s)
+            _lib.call("pta_engine_cw_catalog_add", ctypes.byref(self.plan), ctypes.byref(c), n,
+                      ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0)), out.stride(0), 1 if accumulate else 0, s)
+        self._cw_keep = (src, pdist, count)   # the launches above read them asynchronously
+        return out
+
     def set_cw_prior(self, log10_mc=None, log10_fgw=None, log10_h=None, log10_dist=None, cos_gwtheta=None, gwphi=None, phase0=None,
-                     psi=None, cos_inc=None, pdist=None):
+                     psi=None, cos_inc=None, pdist=None, n_sources=None):
         """uniform boxes (lo, hi) of the per-realisation CW source of generate_sampled() (set_cw configures it).  Required: log10_mc
         [Msun], log10_fgw [Hz] and exactly one of log10_h / log10_dist [Mpc].  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), phase0
         (0, 2 pi), psi (0, pi), cos_inc (-1, 1) (isotropic sky and orientation).  pdist [kpc]: (lo, hi) or [P, 2]; left out = set_cw's
-        pdist.  Drawn from stream (8, 0), pair = label column (_cw.COLUMNS), independently of set_hyper_prior's parameters."""
-        self._cw_prior = _cw.make_prior(self.P, log10_mc=log10_mc, log10_fgw=log10_fgw, log10_h=log10_h, log10_dist=log10_dist,
+        pdist.  Drawn from stream (8, 0), pair = label column (_cw.COLUMNS), independently of set_hyper_prior's parameters.
+        n_sources = S: a catalogue of S sources per realisation, S independent draws from the same boxes, source s from stream (8, s)
+        (source 0 is the single-source draw); the labels are then [R, S].  pdist stays [R, P] on stream (8, 0).  None: one source,
+        labels [R]."""
+        self._cw_prior = _cw.make_prior(self.P, n_sources=n_sources, log10_mc=log10_mc, log10_fgw=log10_fgw, log10_h=log10_h, log10_dist=log10_dist,
                                         cos_gwtheta=cos_gwtheta, gwphi=gwphi, phase0=phase0, psi=psi, cos_inc=cos_inc, pdist=pdist)
         self._cw_prior_dev = None
         return self
@@ -636,7 +694,15 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         if cw_prior is not None:   # stream (8, 0): pair j = label column j, whatever else is sampled
             if self._cw_prior_dev is None:
                 self._cw_prior_dev = [dv.f64(x) for x in _cw.prior_bounds(cw_prior, self.P)]
-            theta.update(_cw.labels(self._uniform_table("pta_cw_uniform", self._cw_prior_dev, R, r0), cw_prior, self.P))
+            S = cw_prior["n_sources"]
+            table = catalog = None
+            if S is None or "pdist" in cw_prior:   # (with a catalogue: for the pdist columns, pairs 8 .. 8 + P - 1 of stream (8, 0))
+                table = self._uniform_table("pta_cw_uniform", self._cw_prior_dev, R, r0)
+            if S is not None:                      # source s from stream (8, s), pair = label column
+                catalog = dv.empty((R, S, _cw.N_SRC))
+                d_lo, d_hi = self._cw_prior_dev
+                _lib.call("pta_cw_catalog_uniform", self.seed, r0, R, S, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(catalog), dv.stream_ptr())
+            theta.update(_cw.labels(table, cw_prior, self.P, catalog))
         if prior is None:
             return theta
         if self._prior_dev is None:
@@ -700,11 +766,12 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         signal (the batched counterpart of the reference's per-signal ``added_signals_time`` entries).  Every deviate is a pure
         function of (seed, realisation, stream, index), so running the fused kernel once per signal with the other inputs
         switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate(); with
-        CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer)."""
+        CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer; for a catalogue the
+        sum over its sources, pta_engine_cw_catalog_add)."""
         hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
-        step = self.max_batch(hyper=theta is not None, cw=bool(cw))
+        step = self.max_batch(hyper=theta is not None, cw=_cw.n_sources(cw))
         if R > step:
             raise ValueError(f"generate_per_signal: at most {step} realisations per call (one workspace batch)")
         total = self._generate(R, r0, None, hyper, cw)       # also fills the workspace (coefficients, mixed GWB grid series)
