@@ -274,7 +274,9 @@ int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf, const dou
  * interleaved (re, im) rows as in pta_gwb_idft (ldw = 0: one row of draws shared by all rows - timing probe).  */
 int pta_gwb_czt_fits(int Nf, int npts, int i0);
 /* pta_gwb_czt `variant`: 0 (default): six LDS exchanges, draws / product / output in registers, computed twiddles;
- *                        1: every stage through LDS with table twiddles (cross-check); 10+f: ladder step f              */
+ *                        1: every stage through LDS with table twiddles (cross-check); 10+f: ladder step f (25 = the default
+ *                        without its twiddle reuse and pruned last butterfly; 137 = all steps, with the LDS twiddle table; all steps from 25 up are
+ *                        bit-identical to each other)                                                                    */
 int pta_gwb_czt_setup(const double *sqrtC, int Nf, int npts, int i0, double inv_dt, double *pre, double *FB, double *tw,
                       double *post, void *stream);
 int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t ldw, int R, int P, int Nf, int npts, int i0,
@@ -376,7 +378,8 @@ typedef struct {
   int32_t rng_fast;           /* Gaussian transform of the on-chip draws (see "RNG" above); 0 = fp64 (default) */
   int32_t synth_variant;      /* fused-kernel variant: 0 (default) = red-noise F @ y on the matrix cores (16 realisations x 256 TOAs
                                  per workgroup), workgroups dealt to the XCDs in contiguous (tile, realisation-group) ranges; 1 = same
-                                 kernel in plain linear workgroup order (A/B); 4 / 6 / 8 = all-VALU kernel compiled for that many
+                                 kernel in plain linear workgroup order (A/B); 2 = same as 0 with the red-noise loop's per-lane 64-bit
+                                 index products instead of scalar row offsets (A/B, bit-identical); 4 / 6 / 8 = all-VALU kernel compiled for that many
                                  waves per SIMD (kept for cross-checks); 100 + k (k <= 64) = the default kernel with k KB of unused
                                  dynamic LDS per workgroup (occupancy probe of round 3: profiles/r03_bench_final.json, DESIGN.md §4.1 "measured and not kept") */
 } pta_engine_plan;

@@ -88,11 +88,25 @@ extern "C" int pta_gwb_czt_setup(const double *sqrtC, int Nf, int npts, int i0, 
 
 extern "C" int pta_gwb_czt_fits(int Nf, int npts, int i0) { return czt_fits(Nf, npts, i0) ? 1 : 0; }
 
+// the production ladder step of k_gwb_czt (variant 0 of both entry points)
+// (15 + 16 + 64: the LDS twiddle table of bit 32 measured no faster than the products it replaces - DESIGN.md 4.5 - and stays an A/B step)
+#define PTA_CZT_FUSE_DEFAULT (15 + 16 + 64)
+// the window [i0 - 1, i0 - 1 + npts) of the transform's output lies inside [0, 1024): the last (s = 512) butterfly, whose outputs are
+// o + 512 q, only ever stores q = 0 and q = 1
+static int czt_last2(int npts, int i0) { return i0 - 2 + npts < 1024 ? 1 : 0; }
+
 // One workgroup per (realisation, pulsar) row.  FUSE selects how much stays in registers between LDS exchanges:
 //   bit 0: forward s=1 butterfly, chirp-spectrum product and inverse s=1 butterfly in one go (two exchanges fewer);
 //   bit 1: the last butterfly writes the npts-sample window straight to memory;
 //   bit 2: the first butterfly starts from registers (draws generated per thread for its own 512-strided elements);
-//   bit 3: one twiddle load per butterfly, the rest by squaring / products (pta_fft_twiddles<.., 1>).
+//   bit 3: one twiddle load per butterfly, the rest by squaring / products (pta_fft_twiddles<.., 1>);
+//   bit 4 (16): the s = 512 twiddle set of the first butterfly stays in registers and serves, conjugated, the last one (needs bits 1, 2);
+//   bit 5 (32): the twiddle sets the workgroup shares come from an LDS table filled once per workgroup with the product sequence
+//           of pta_fft_twiddles<.., 1> - s = 8: o = l & 7, 8 complete sets; s = 64: o < 64, (w1, w2, w4) per o and four products -
+//           read by the forward and the inverse pass alike (needs bit 3: the table holds the squared values);
+//   bit 6 (64): where the launch says the window lies inside [0, 1024) (`last2`), the last butterfly computes outputs 0 and 1 only
+//           (pta_fft_core_inv_out01; needs bit 1).
+// Bits 4 to 6 remove work, not roundings: every variant 15 + bits is bit-identical to 15.  The production kernel is 15 + 16 + 64.
 // FUSE = 15 is the production kernel: 6 LDS exchanges instead of 10, and - what mattered most on MI355X - 6 instead of 56
 // global twiddle loads per thread (the q-strided twiddle gathers, not LDS or the barriers, bounded the first version:
 // 3.2 -> 2.0 ms per 65 280 rows; rocprofv3 SQ_INSTS_VALU now accounts for ~95 % of the time).  FUSE = 0 (every stage through
@@ -107,11 +121,32 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
                                                                   const double *__restrict__ pre, const double *__restrict__ FB,
                                                                   const double *__restrict__ tw, const double *__restrict__ post,
                                                                   double *__restrict__ G0, int64_t ldg,
-                                                                  const double *__restrict__ scale, int64_t ld_scale) {
+                                                                  const double *__restrict__ scale, int64_t ld_scale, int last2) {
+  static_assert(!(FUSE & 16) || (FUSE & 6) == 6, "bit 4 carries the twiddles from the register-fed first butterfly to the storing last one");
+  static_assert(!(FUSE & 32) || (FUSE & 8), "bit 5 tabulates the squared twiddles of bit 3");
+  static_assert(!(FUSE & 64) || (FUSE & 2), "bit 6 prunes the storing last butterfly");
   __shared__ double re[PTA_FFT_PLANE], im[PTA_FFT_PLANE];
+  constexpr bool TAB = (FUSE & 32) != 0;
+  // (the two tables are only referenced - and only allocated - when TAB)
+  __shared__ pta_cplx tw8[7][8];    // [q - 1][o]: w[q] of the s = 8 butterflies, o = l & 7
+  __shared__ pta_cplx tw64[3][64];  // [0, 1, 2][o]: w[1], w[2], w[4] of the s = 64 butterflies
   const int tid = threadIdx.x;
   const int row = blockIdx.x;
   const int Kf = Nf - 2;
+  if (TAB) {  // waves 0 and 1; read after the barriers that precede the s = 64 pass
+    if (tid < 64) {
+      pta_cplx tq[8];
+      pta_fft_twiddles<6, 1>(tw, tid, tq);  // only w[1], w[2], w[4] are kept (the products are dead code here)
+      tw64[0][tid] = tq[1];
+      tw64[1][tid] = tq[2];
+      tw64[2][tid] = tq[4];
+    } else if (tid < 72) {
+      pta_cplx tq[8];
+      pta_fft_twiddles<3, 1>(tw, tid - 64, tq);
+#pragma unroll
+      for (int q = 1; q < 8; ++q) tw8[q - 1][tid - 64] = tq[q];
+    }
+  }
   if (RNG) {
     pta_rng_stage_tables();  // Box-Muller tables -> LDS (pta_rng.h)
     __syncthreads();
@@ -124,9 +159,10 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
   // them (L1/L2 hits) instead of carrying 28 registers per pass across the whole kernel in scratch
   const double *twi = tw;
   asm volatile("" : "+s"(twi));
+  pta_cplx tv[8];  // the s = 512 set: FUSE & 16 keeps it from the first butterfly to the last
   if (FUSE & 4) {
     int b, o;
-    pta_cplx v[8], tv[8];
+    pta_cplx v[8];
     pta_fft_map<9>(tid, b, o);
     pta_fft_twiddles<9, TW>(tw, o, tv);
 #pragma unroll
@@ -181,9 +217,30 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
     pta_fft_pass<false, 9, TW>(re, im, tw, tid);
   }
   __syncthreads();
-  pta_fft_pass<false, 6, TW>(re, im, tw, tid);
-  __syncthreads();
-  pta_fft_pass<false, 3, TW>(re, im, tw, tid);
+  // the shared sets of one pass, from the table (same bits as pta_fft_twiddles<.., 1> for this thread's o)
+  auto tab64 = [&](pta_cplx *wq) {
+    const int o = 8 * (tid >> 6) + (tid & 7);
+    wq[1] = tw64[0][o];
+    wq[2] = tw64[1][o];
+    wq[4] = tw64[2][o];
+    pta_fft_twiddle_products(wq);
+  };
+  auto tab8 = [&](pta_cplx *wq) {
+#pragma unroll
+    for (int q = 1; q < 8; ++q) wq[q] = tw8[q - 1][tid & 7];
+  };
+  if (TAB) {
+    pta_cplx wq[8];
+    tab64(wq);
+    pta_fft_pass_w<false, 6>(re, im, tid, wq);
+    __syncthreads();
+    tab8(wq);
+    pta_fft_pass_w<false, 3>(re, im, tid, wq);
+  } else {
+    pta_fft_pass<false, 6, TW>(re, im, tw, tid);
+    __syncthreads();
+    pta_fft_pass<false, 3, TW>(re, im, tw, tid);
+  }
   __syncthreads();
   if (FUSE & 1) {
     int b, o;
@@ -214,25 +271,41 @@ __global__ __launch_bounds__(PTA_FFT_THREADS, 4) void k_gwb_czt(uint64_t seed, u
     pta_fft_pass<true, 0, TW>(re, im, twi, tid);
   }
   __syncthreads();
-  pta_fft_pass<true, 3, TW>(re, im, twi, tid);
-  __syncthreads();
-  pta_fft_pass<true, 6, TW>(re, im, twi, tid);
+  if (TAB) {
+    pta_cplx wq[8];
+    tab8(wq);
+    pta_fft_pass_w<true, 3>(re, im, tid, wq);
+    __syncthreads();
+    tab64(wq);
+    pta_fft_pass_w<true, 6>(re, im, tid, wq);
+  } else {
+    pta_fft_pass<true, 3, TW>(re, im, twi, tid);
+    __syncthreads();
+    pta_fft_pass<true, 6, TW>(re, im, twi, tid);
+  }
   __syncthreads();
   const pta_cplx *post2 = reinterpret_cast<const pta_cplx *>(post);
   if (FUSE & 2) {
     int b, o;
-    pta_cplx v[8], tv[8];
+    pta_cplx v[8];
     pta_fft_map<9>(tid, b, o);
-    pta_fft_twiddles<9, TW>(twi, o, tv);
+    if (!(FUSE & 16)) pta_fft_twiddles<9, TW>(twi, o, tv);
     pta_fft_load<9>(re, im, b, o, v);
-    pta_fft_core<true, 9>(v, tv);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    auto put = [&](int q) {
       const int jj = o + 512 * q - (i0 - 1);
       if (jj >= 0 && jj < npts) {
         const pta_cplx pp = post2[jj];
         G0[(int64_t)row * ldg + jj] = v[q].re * pp.re - v[q].im * pp.im;
       }
+    };
+    if ((FUSE & 64) && last2) {  // workgroup-uniform: the window ends below 1024, outputs 2..7 would be dropped
+      pta_fft_core_inv_out01<9>(v, tv);
+      put(0);
+      put(1);
+    } else {
+      pta_fft_core<true, 9>(v, tv);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) put(q);
     }
   } else {
     pta_fft_pass<true, 9, TW>(re, im, twi, tid);
@@ -255,12 +328,14 @@ extern "C" int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t 
   int64_t M64 = (int64_t)R * P;
   PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_czt: R*P too large");
   const int M = (int)M64;
-  // variant: 0 = fully fused kernel (default), 1 = plain cross-check (FUSE = 0), 10 + FUSE = any ladder step
+  // variant: 0 = fully fused kernel (default, PTA_CZT_FUSE_DEFAULT), 1 = plain cross-check (FUSE = 0), 10 + FUSE = any ladder step
+  // (25 = the fused kernel without the twiddle / pruning bits 16, 32, 64; 137 = with all three)
   const int fastm = rng_fast ? 1 : 0;
-  const int fuse = variant == 0 ? 15 : (variant == 1 ? 0 : variant - 10);
+  const int fuse = variant == 0 ? PTA_CZT_FUSE_DEFAULT : (variant == 1 ? 0 : variant - 10);
+  const int last2 = czt_last2(npts, i0);
 #define PTA_CZT_X(RNGV, FASTV, FUSEV)                                                                                                  \
   hipLaunchKernelGGL((k_gwb_czt<RNGV, FASTV, FUSEV, false>), dim3(M), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), seed, r0, w, ldw, \
-                     M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, nullptr, 0)
+                     M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, nullptr, 0, last2)
 #define PTA_CZT_XF(FUSEV)              \
   if (w)                               \
     PTA_CZT_X(false, false, FUSEV);    \
@@ -269,7 +344,12 @@ extern "C" int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t 
   else                                 \
     PTA_CZT_X(true, false, FUSEV)
   switch (fuse) {
+    case PTA_CZT_FUSE_DEFAULT: PTA_CZT_XF(PTA_CZT_FUSE_DEFAULT); break;
+    case 15 + 16 + 32 + 64: PTA_CZT_XF(15 + 16 + 32 + 64); break;
     case 15: PTA_CZT_XF(15); break;
+    case 15 + 16: PTA_CZT_XF(15 + 16); break;
+    case 15 + 32: PTA_CZT_XF(15 + 32); break;
+    case 15 + 64: PTA_CZT_XF(15 + 64); break;
     case 0: PTA_CZT_XF(0); break;
     case 1: PTA_CZT_XF(1); break;
     case 3: PTA_CZT_XF(3); break;
@@ -301,12 +381,12 @@ extern "C" int pta_gwb_czt_scaled(uint64_t seed, uint64_t r0, const double *w, i
   PTA_REQUIRE(variant == 0 || variant == 1, PTA_E_ARG, "pta_gwb_czt_scaled: variant %d (0 or 1)", variant);
 #define PTA_CZT_S(FASTV, FUSEV)                                                                                                     \
   hipLaunchKernelGGL((k_gwb_czt<true, FASTV, FUSEV, true>), dim3(M), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), seed, r0, nullptr, \
-                     0, M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, scale, ld_scale)
+                     0, M, P, Nf, npts, i0, pre, FB, tw, post, G0, ldg, scale, ld_scale, czt_last2(npts, i0))
   if (variant == 0) {
     if (rng_fast)
-      PTA_CZT_S(true, 15);
+      PTA_CZT_S(true, PTA_CZT_FUSE_DEFAULT);
     else
-      PTA_CZT_S(false, 15);
+      PTA_CZT_S(false, PTA_CZT_FUSE_DEFAULT);
   } else {
     if (rng_fast)
       PTA_CZT_S(true, 0);

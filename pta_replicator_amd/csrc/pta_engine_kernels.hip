@@ -151,7 +151,10 @@ typedef double pta_f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 
 // (SINGLE keeps four deviates alive from a lane's even TOA to its odd one: 8 VGPRs more than the 128 that four workgroups per CU allow -
 // it is compiled for three, where the occupancy curve of the kernel is already flat: 4.9 against 4.8 ms at 3 / 4 workgroups per CU)
-template <bool FAST, bool SINGLE>
+// RNIDX (red-noise loop addressing): true = a wave-uniform row offset from the scalar unit added to per-lane 32-bit byte offsets that are
+// computed once (the host guards their range); false = the per-lane 64-bit index product per load (synth_variant 2, and any plan
+// beyond the 32-bit range).  Same loads' values, same MFMA sequence: the two are bit-identical.
+template <bool FAST, bool SINGLE, bool RNIDX>
 __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synth_mfma(pta_engine_plan pl, uint64_t seed, uint64_t r0, int R,
                                                                            double *__restrict__ out, int64_t ld_out, int xcd_aware) {
   constexpr int fast = FAST ? 1 : 0;  // template parameters: the RNG-math modes and the single-deviate white noise are separate kernels
@@ -232,16 +235,61 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] = pta_mfma_f64(av, bv[j], acc[j]);
     };
-    double a0, a1, a2, b0[4], b1[4], b2[4];
-    ld(0, a0, b0);
-    ld(4, a1, b1);
-    for (int k0 = 0; k0 < K; k0 += 12) {
-      ld(k0 + 8, a2, b2);
-      mm(a0, b0);
-      ld(k0 + 12, a0, b0);
-      mm(a1, b1);  // steps past K carry a zero coefficient: no exits inside the rotation
-      ld(k0 + 16, a1, b1);
-      mm(a2, b2);
+    // the rotation, over either form of the loads
+    auto run = [&](auto &&ldx) {
+      double a0, a1, a2, b0[4], b1[4], b2[4];
+      ldx(0, a0, b0);
+      ldx(4, a1, b1);
+      for (int k0 = 0; k0 < K; k0 += 12) {
+        ldx(k0 + 8, a2, b2);
+        mm(a0, b0);
+        ldx(k0 + 12, a0, b0);
+        mm(a1, b1);  // steps past K carry a zero coefficient: no exits inside the rotation
+        ldx(k0 + 16, a1, b1);
+        mm(a2, b2);
+      }
+    };
+    if (RNIDX) {
+      // Only `quad` of a load's bin k0 + quad differs between lanes: the byte offsets (quad ldf + TOA) 8 into the design matrix and
+      // ((ra P + a) K + quad) 8 into the coefficients are per-lane constants of the whole loop, and the row k0 is wave-uniform - its
+      // byte offset is one scalar multiply per K-step.  Each load is (scalar base pointer) + (32-bit lane offset), the lane offset
+      // being constant + row offset: ONE 32-bit add per load in place of the 64-bit per-lane index product.  (The row offset has to
+      // go into the lane offset, not the base: a loop-invariant lane offset is zero-extended outside the loop, and an address of
+      // scalar + 64-bit vector is no scalar-base load any more - the compiler then carries 64-bit vector addresses.)
+      // A step at or beyond the last group of four bins reads that last group (its coefficient is zero from bin K on), and only when
+      // K is no multiple of 4 does that group need lanes clamped to bin K - 1: a loop of its own (workgroup-uniform branch) that
+      // takes the clamp off the row offset of such a step, so that K % 4 == 0 pays nothing for it.
+      const int klast = (K - 1) & ~3;  // first bin of the last group
+      const char *__restrict__ Fbytes = reinterpret_cast<const char *>(Fb);
+      const char *__restrict__ cbytes = reinterpret_cast<const char *>(pl.rn_coef);
+      const uint32_t ldfb = (uint32_t)pl.ldf * 8u;
+      uint32_t offF[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) offF[j] = (uint32_t)quad * ldfb + (uint32_t)tcl[j] * 8u;
+      const uint32_t offC = (uint32_t)(((int64_t)ra * P + a) * K + quad) * 8u;
+      const int kq = K - quad;
+      // rowF / rowC: byte offset of the step's first bin (wave-uniform, or per lane where the tail loop clamps)
+      auto ldu = [&](int k0, auto rowF, auto rowC, double &av, double (&bv)[4]) {
+        const double a_ld = *reinterpret_cast<const double *>(cbytes + (uint32_t)(offC + rowC));
+        av = (k0 < kq) ? a_ld : 0.0;  // k0 + quad < K, against the lane constant K - quad
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const double *>(Fbytes + (uint32_t)(offF[j] + rowF));
+      };
+      if ((K & 3) == 0) {
+        run([&](int k0, double &av, double (&bv)[4]) {
+          const uint32_t kg = (uint32_t)min(k0, klast);  // wave-uniform
+          ldu(k0, kg * ldfb, kg * 8u, av, bv);
+        });
+      } else {
+        const uint32_t dq = (uint32_t)(quad - min(quad, K - 1 - klast));  // bins this lane steps back inside the last group
+        run([&](int k0, double &av, double (&bv)[4]) {
+          const uint32_t kg = (uint32_t)min(k0, klast);
+          const uint32_t back = k0 >= klast ? dq : 0u;
+          ldu(k0, kg * ldfb - back * ldfb, kg * 8u - back * 8u, av, bv);
+        });
+      }
+    } else {
+      run(ld);
     }
   }
   const uint32_t strm_wn = pta_stream_id(PTA_STREAM_WN, (uint32_t)a);
@@ -356,16 +404,24 @@ extern "C" int pta_engine_synth(const pta_engine_plan *plan_host, uint64_t seed,
   // staging variant (17 KB, 6 per CU, 3 barriers) measured 6.0 ms at 6 AND when padded back to 4: occupancy is saturated at 4.
   const int variant = p.synth_variant;
   const int rng_fast = p.rng_fast ? 1 : 0;
-  // 0 = MFMA kernel (default); 1 = same, linear workgroup order (A/B of the XCD mapping); 4 / 6 / 8 = all-VALU kernel; 100 + k = MFMA
+  // 0 = MFMA kernel (default); 1 = same, linear workgroup order (A/B of the XCD mapping); 2 = same as 0 with the red-noise loop's
+  // per-lane 64-bit index products (A/B of its addressing); 4 / 6 / 8 = all-VALU kernel; 100 + k = MFMA
   // kernel with k KB of unused dynamic LDS per workgroup - the occupancy probe of round 3 (script since removed; result in DESIGN.md §4.1): the 34 KB ECORR
   // staging buffer allows 4 workgroups per CU (+12 KB: 3, +20 KB: 2)
-  if (variant == 0 || variant == 1 || (variant >= 100 && variant <= 164)) {
+  if (variant == 0 || variant == 1 || variant == 2 || (variant >= 100 && variant <= 164)) {
     const int xcd = variant == 1 ? 0 : 1;
     const unsigned pad = variant >= 100 ? (unsigned)(variant - 100) * 1024u : 0u;
     const int64_t total = (int64_t)pta_cdiv(R, ENG_MR) * p.n_tiles, nwg = ((total + 7) >> 3) << 3;
     PTA_REQUIRE(nwg < (1LL << 31), PTA_E_ARG, "pta_engine_synth: %lld workgroups exceed one launch", (long long)nwg);
-    auto kern = p.wn_c ? (rng_fast ? k_engine_synth_mfma<true, true> : k_engine_synth_mfma<false, true>)
-                       : (rng_fast ? k_engine_synth_mfma<true, false> : k_engine_synth_mfma<false, false>);
+    // the 32-bit lane offsets of the red-noise loop: up to ((K - 1) ldf + 255) 8 from a tile's first design-matrix entry, R P K 8
+    // into the coefficients
+    const bool rnidx = variant != 2 && p.rn_k > 0 && p.ldf < (1LL << 28) && ((int64_t)p.rn_k * p.ldf + PTA_ENGINE_TILE) * 8 < (1LL << 32) &&
+                       (int64_t)R * p.n_psr * p.rn_k * 8 < (1LL << 32);
+#define PTA_SYNTH_K(IDX)                                                                                                \
+  (p.wn_c ? (rng_fast ? k_engine_synth_mfma<true, true, IDX> : k_engine_synth_mfma<false, true, IDX>)                  \
+          : (rng_fast ? k_engine_synth_mfma<true, false, IDX> : k_engine_synth_mfma<false, false, IDX>))
+    auto kern = rnidx ? PTA_SYNTH_K(true) : PTA_SYNTH_K(false);
+#undef PTA_SYNTH_K
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(PTA_ENGINE_TILE), pad, pta_stream(stream), p, seed, r0, R, out, ld_out, xcd);
     PTA_LAUNCH_CHECK();
     return PTA_OK;

@@ -114,6 +114,15 @@ PTA_HD void pta_fft_store(double *re, double *im, int b, int o, const pta_cplx *
   }
 }
 
+// w[3], w[5], w[6], w[7] of a butterfly from its w[1], w[2], w[4]: the ONE product sequence every twiddle set goes through, whether a
+// thread builds the set for itself or reads w[1], w[2], w[4] from a table another thread filled - the bits are the same
+PTA_HD void pta_fft_twiddle_products(pta_cplx *w) {
+  w[3] = pta_cmul(w[1], w[2]);
+  w[5] = pta_cmul(w[1], w[4]);
+  w[6] = pta_cmul(w[2], w[4]);
+  w[7] = pta_cmul(w[3], w[4]);
+}
+
 // the twiddles of one butterfly: w[q] = W^(q m1), W = e^{-2 pi i / 4096}, m1 = o * TSTEP.  Only W^m1, W^2m1 and W^4m1 are
 // loaded (for s = 512 the q-strided gathers of all seven touch up to 56 cache lines per wave and q; these three touch 14);
 // the other four are products - each one rounding (~1e-16) away from the table value.
@@ -130,10 +139,7 @@ PTA_HD void pta_fft_twiddles(const double *tw, int o, pta_cplx *w) {
       w[2] = tw2[2 * m1];
       w[4] = tw2[4 * m1];
     }
-    w[3] = pta_cmul(w[1], w[2]);
-    w[5] = pta_cmul(w[1], w[4]);
-    w[6] = pta_cmul(w[2], w[4]);
-    w[7] = pta_cmul(w[3], w[4]);
+    pta_fft_twiddle_products(w);
   } else {
 #pragma unroll
     for (int q = 1; q < 8; ++q) w[q] = pta_cplx{1.0, 0.0};
@@ -154,6 +160,45 @@ PTA_HD void pta_fft_core(pta_cplx *v, const pta_cplx *w) {
 #pragma unroll
     for (int q = 1; q < 8; ++q) v[q] = pta_cmul(v[q], w[q]);
   }
+}
+
+// Outputs 0 and 1 only of pta_dft8<true>, with its association (a0..a7; c0 = a0 + a2, c1 = a1 + a3, X0 = c0 + c1; t5, t6, t7,
+// d0 = a4 + t6, d1 = t5 + t7, X1 = d0 + d1): v[0], v[1] carry the bits the full butterfly gives, v[2..7] are left as they were.
+PTA_HD void pta_dft8_inv_out01(pta_cplx *v) {
+  const double h = 0.70710678118654752440;
+  pta_cplx a0 = pta_cadd(v[0], v[4]), a4 = pta_csub(v[0], v[4]);
+  pta_cplx a1 = pta_cadd(v[1], v[5]), a5 = pta_csub(v[1], v[5]);
+  pta_cplx a2 = pta_cadd(v[2], v[6]), a6 = pta_csub(v[2], v[6]);
+  pta_cplx a3 = pta_cadd(v[3], v[7]), a7 = pta_csub(v[3], v[7]);
+  pta_cplx t5 = pta_cplx{h * (a5.re - a5.im), h * (a5.re + a5.im)};
+  pta_cplx t6 = pta_cmuli<true>(a6);
+  pta_cplx t7 = pta_cplx{-h * (a7.re + a7.im), h * (a7.re - a7.im)};
+  pta_cplx c0 = pta_cadd(a0, a2), c1 = pta_cadd(a1, a3);
+  v[0] = pta_cadd(c0, c1);
+  pta_cplx d0 = pta_cadd(a4, t6), d1 = pta_cadd(t5, t7);
+  v[1] = pta_cadd(d0, d1);
+}
+
+// the inverse butterfly of pta_fft_core<true, LOG2S> pruned to its outputs 0 and 1 (the last pass of a transform of which only a
+// window inside [0, 2 s) is kept): the same input products, then pta_dft8_inv_out01
+template <int LOG2S>
+PTA_HD void pta_fft_core_inv_out01(pta_cplx *v, const pta_cplx *w) {
+  if (LOG2S > 0) {
+#pragma unroll
+    for (int q = 1; q < 8; ++q) v[q] = pta_cmul(v[q], pta_cplx{w[q].re, -w[q].im});
+  }
+  pta_dft8_inv_out01(v);
+}
+
+// load - butterfly - store of one pass for one thread, twiddles given
+template <bool INV, int LOG2S>
+PTA_HD void pta_fft_pass_w(double *re, double *im, int tid, const pta_cplx *w) {
+  int b, o;
+  pta_fft_map<LOG2S>(tid, b, o);
+  pta_cplx v[8];
+  pta_fft_load<LOG2S>(re, im, b, o, v);
+  pta_fft_core<INV, LOG2S>(v, w);
+  pta_fft_store<LOG2S>(re, im, b, o, v);
 }
 
 // load - butterfly - store of one pass for one thread

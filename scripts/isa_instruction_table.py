@@ -8,7 +8,12 @@ element of k_engine_synth_mfma<false> go.  No GPU needed: hipcc --save-temps for
     MFMA loop (5 trips at K = 60), the unrolled 4-TOA epilogue (once) - static counts weighted by those trip counts give the
     dynamic VALU count per workgroup and per output element (16 realisations x 256 TOAs).
 
-Writes profiles/r03_isa_instruction_classes.txt.  The PMC figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of profiles/r03_pmc.json."""
+  * both addressings of the red-noise loop (template parameter RNIDX of the kernel) are listed side by side, and the chirp-z kernel
+    k_gwb_czt<true, false, FUSE, false> is counted for the fused step 15, each of the bits 16 / 32 / 64 alone, the default and all three, with
+    the twiddle and butterfly pieces those bits remove compiled on their own like the pieces of the draw.
+
+Writes profiles/r13_isa_instruction_classes.txt (r03_isa_instruction_classes.txt is the table of the kernel as it was in round 3).  The PMC
+figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of profiles/r06_pmc.json."""
 import collections
 import os
 import re
@@ -24,7 +29,17 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 PROBE = r'''
 #include <hip/hip_runtime.h>
 #include "%(csrc)s/pta_rng.h"
+#include "%(csrc)s/pta_fft.h"
 extern "C" {
+// chirp-z pieces: eight complex inputs per thread from memory, eight (or two) complex results back
+#define P_LOADV(v) pta_cplx v[8]; for (int q = 0; q < 8; ++q) v[q] = ((const pta_cplx *)in)[8 * threadIdx.x + q]
+#define P_STOREV(v, n) for (int q = 0; q < n; ++q) ((pta_cplx *)out)[8 * threadIdx.x + q] = v[q]
+__global__ void p_c_empty(const double *in, double *out) { P_LOADV(v); P_STOREV(v, 8); }
+__global__ void p_c_twiddles(const double *in, double *out) { pta_cplx w[8]; w[0] = {1.0, 0.0}; pta_fft_twiddles<9, 1>(in, threadIdx.x, w); P_STOREV(w, 8); }
+__global__ void p_c_load1(const double *in, double *out) { pta_cplx w[8]; for (int q = 0; q < 8; ++q) w[q] = ((const pta_cplx *)in)[threadIdx.x]; P_STOREV(w, 8); }
+__global__ void p_c_products(const double *in, double *out) { P_LOADV(w); pta_fft_twiddle_products(w); P_STOREV(w, 8); }
+__global__ void p_c_dft8_inv(const double *in, double *out) { P_LOADV(v); pta_dft8<true>(v); P_STOREV(v, 8); }
+__global__ void p_c_dft8_inv01(const double *in, double *out) { P_LOADV(v); pta_dft8_inv_out01(v); P_STOREV(v, 8); }
 __global__ void p_philox(const uint32_t *in, uint32_t *out) {
   pta_u32x4 v = pta_philox_draw(((const uint64_t *)in)[0], ((const uint64_t *)in)[1] + threadIdx.x, in[4], in[5] + threadIdx.x);
   out[4 * threadIdx.x] = v.x; out[4 * threadIdx.x + 1] = v.y; out[4 * threadIdx.x + 2] = v.z; out[4 * threadIdx.x + 3] = v.w;
@@ -124,17 +139,38 @@ def main():
         subprocess.check_call([HIPCC] + FLAGS + ["-DPTA_ISA_TABLE_MAIN_PATH_ONLY", os.path.join(CSRC, "pta_engine_kernels.hip"), "-o", os.path.join(d, "eng.o")],
                               cwd=d, stderr=subprocess.DEVNULL)
         kb = kernel_bodies(os.path.join(d, "pta_engine_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"))
-        name = next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0E"))
+        def kernel_rows(name, title):
+            rep.append("")
+            rep.append(f"{title} ({name}): basic blocks with VALU / MFMA / LDS / VMEM counts")
+            rows = []
+            for lab, ls in blocks(kb[name]):
+                c, vops = count(ls)
+                if sum(c.values()) == 0: continue
+                back = any(re.search(r"s_cbranch\w*\s+" + re.escape(lab) + r"\b", x) for x in ls)
+                rows.append((lab, c, back, vops))
+                rep.append(f"  {lab:12s} valu {c['valu']:5d}  mfma {c['mfma']:3d}  lds {c['lds']:3d}  vmem {c['vmem']:3d}  salu {c['salu']:4d}  wait {c['wait']:3d}{'   <- loop' if back else ''}")
+            return rows
+
+        def mix(vops):
+            mul = sum(n for op, n in vops.items() if op.startswith(("v_mul_lo", "v_mul_hi", "v_mad_u64", "v_mad_i64")))
+            w64 = sum(n for op, n in vops.items() if op.endswith("_u64") or op.endswith("_b64") or op.endswith("_i64")) - sum(n for op, n in vops.items() if op.startswith("v_mad_"))
+            return f"integer multiplies {mul}, other 64-bit integer {w64}: " + ", ".join(f"{op} {n}" for op, n in vops.most_common(8))
+
+        # the red-noise loop with the per-lane 64-bit index products (RNIDX = false: synth_variant 2, the kernel before the change) ...
+        old_rows = kernel_rows(next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb0E")), "k_engine_synth_mfma<false, false, false>")
+        old_rn = [r for r in old_rows if r[2] and r[1]["mfma"] > 0]
+        # ... and with scalar row offsets (RNIDX = true, default): two copies of the loop, K % 4 == 0 (fewer VALU: the bench's K = 60) and K % 4 != 0
+        name = next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb1E"))
+        rows = kernel_rows(name, "k_engine_synth_mfma<false, false, true>")
+        new_rn = sorted((r for r in rows if r[2] and r[1]["mfma"] > 0), key=lambda r: r[1]["valu"])
         rep.append("")
-        rep.append(f"k_engine_synth_mfma<false, false> ({name}): basic blocks with VALU / MFMA / LDS / VMEM counts")
-        bl = blocks(kb[name])
-        rows = []
-        for lab, ls in bl:
-            c, _ = count(ls)
-            if sum(c.values()) == 0: continue
-            back = any(re.search(r"s_cbranch\w*\s+" + re.escape(lab) + r"\b", x) for x in ls)
-            rows.append((lab, c, back))
-            rep.append(f"  {lab:12s} valu {c['valu']:5d}  mfma {c['mfma']:3d}  lds {c['lds']:3d}  vmem {c['vmem']:3d}  salu {c['salu']:4d}  wait {c['wait']:3d}{'   <- loop' if back else ''}")
+        rep.append("red-noise MFMA loop, per trip of 12 bins (3 K-steps, 15 loads):")
+        for title, r in [("per-lane 64-bit index products (before; synth_variant 2)", old_rn[0]), ("scalar row offsets, K % 4 == 0 (default)", new_rn[0]),
+                         ("scalar row offsets, K % 4 != 0 (tail clamp)", new_rn[-1])]:
+            rep.append(f"  {title:58s} {r[0]:10s} valu {r[1]['valu']:3d} salu {r[1]['salu']:3d}   {mix(r[3])}")
+        rep.append(f"  static VALU of the kernel, per thread: {sum(r[1]['valu'] for r in old_rows)} before, {sum(r[1]['valu'] for r in rows)} after (after holds both copies of the loop)")
+        tail_valu = new_rn[-1][1]["valu"] if len(new_rn) > 1 else 0
+        rows = [r for r in rows if not (len(new_rn) > 1 and r[0] == new_rn[-1][0])]   # the dynamic estimate below takes the K % 4 == 0 copy
         # dynamic estimate: loops = blocks that branch back to themselves.  Identify them by content: the staging loop holds the
         # Philox multiplies (v_mad_u64_u32) and LDS writes but no MFMA; the red-noise loop holds MFMAs
         stag = [r for r in rows if r[2] and r[1]["mfma"] == 0 and r[1]["valu"] > 50]
@@ -155,7 +191,37 @@ def main():
         rep.append(f"of which Gaussian draws: (1 EFAC/EQUAD pair + {n_epochs_pairs / 256.0:.3f} ECORR pairs) per element x {pair} = {rng:.1f} "
                    f"({100 * rng / per_elem:.0f} %); the remaining {per_elem - rng:.1f} are GWB interpolation, accumulation, operand addressing, MFMA feeding and stores")
         rep.append("per Gaussian pair: Philox 46 (20 of them v_mad_u64_u32 at half rate), uniforms 10, -2 ln u 22, sqrt 10, sin / cos 26, products 2")
-    path = os.path.join(ROOT, "profiles", "r03_isa_instruction_classes.txt")
+        old_dyn = sum(r[1]["valu"] for r in old_rows if not r[2]) + sum(r[1]["valu"] for r in old_rows if r[2] and r[1]["mfma"] == 0 and r[1]["valu"] > 50) * t_stag + old_rn[0][1]["valu"] * t_rn
+        rep.append(f"the same estimate with the per-lane index products: {old_dyn:.0f} per wave, {old_dyn / 16.0:.1f} per output element ({100 * (old_dyn - dyn) / old_dyn:.1f} % more)")
+        # ---- the chirp-z kernel
+        rep.append("")
+        rep.append("k_gwb_czt<true, false, FUSE, false>: static counts per thread (FUSE & 64 holds the full AND the pruned last butterfly: a launch runs one of them)")
+        subprocess.check_call([HIPCC] + FLAGS + [os.path.join(CSRC, "pta_czt_kernels.hip"), "-o", os.path.join(d, "czt.o")], cwd=d, stderr=subprocess.DEVNULL)
+        asm = os.path.join(d, "pta_czt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+        kc = kernel_bodies(asm)
+        meta = open(asm).read()
+        for fuse, what in ((15, "fused kernel (variant 25, before)"), (15 + 16, "+ s = 512 twiddle set carried in registers"), (15 + 32, "+ s = 8 / s = 64 sets from the LDS table"),
+                           (15 + 64, "+ pruned last butterfly"), (15 + 16 + 64, "carried set + pruned butterfly (variant 0)"), (127, "all three (variant 137)")):
+            kn = f"_Z9k_gwb_cztILb1ELb0ELi{fuse}ELb0EEvmmPKdliiiiiS1_S1_S1_S1_PdlS1_li"
+            c, vops = count(kc[kn])
+            f64 = sum(n for op, n in vops.items() if op.endswith("_f64"))
+            m = meta[meta.index(".amdhsa_kernel " + kn):]
+            res = [re.search(k + r"\s+(\d+)", m).group(1) for k in ("amdhsa_next_free_vgpr", "amdhsa_group_segment_fixed_size", "amdhsa_private_segment_fixed_size")]
+            rep.append(f"  FUSE {fuse:3d} {what:44s} valu {c['valu']:5d} (f64 {f64:4d})  lds {c['lds']:3d}  vmem {c['vmem']:3d}  salu {c['salu']:4d}   VGPR {res[0]}, LDS {res[1]} B, scratch {res[2]} B")
+        kp = kernel_bodies(os.path.join(d, "probe-hip-amdgcn-amd-amdhsa-gfx950.s"))
+        e = count(kp["p_c_empty"])[0]["valu"]
+        tw_own = count(kp["p_c_twiddles"])[0]["valu"] - count(kp["p_c_load1"])[0]["valu"]
+        prod = count(kp["p_c_products"])[0]["valu"] - e
+        full, out01 = count(kp["p_c_dft8_inv"])[0]["valu"] - e, count(kp["p_c_dft8_inv01"])[0]["valu"] - e
+        rep.append("the pieces (compiled on their own, probe overhead subtracted), VALU per thread:")
+        rep.append(f"  twiddle set w[2..7] from one loaded w[1] (pta_fft_twiddles<.., 1>: 6 complex products)   {tw_own:3d}   x 6 twiddled passes before")
+        rep.append(f"  w[3], w[5], w[6], w[7] from tabulated w[1], w[2], w[4] (pta_fft_twiddle_products)          {prod:3d}   the two s = 64 passes with bit 32")
+        rep.append(f"  8-point inverse butterfly pta_dft8<true>                                                {full:3d}")
+        rep.append(f"  its outputs 0 and 1 only (pta_dft8_inv_out01)                                           {out01:3d}   the last pass with bit 64, window inside [0, 1024)")
+        rep.append(f"removed per thread: bit 16 {tw_own} (last pass reuses the first pass's set), bit 32 {2 * tw_own} + {2 * (tw_own - prod)} (s = 8 sets complete from LDS, s = 64 sets four products "
+                   f"from LDS), bit 64 {full - out01} + the post-chirp products and exec-masked store blocks of outputs 2..7; the table fill ({tw_own} + 8 in waves 0 and 1) and "
+                   f"{2 * 7 + 2 * 3} ds_read_b128 per thread are added")
+    path = os.path.join(ROOT, "profiles", "r13_isa_instruction_classes.txt")
     open(path, "w").write("\n".join(rep) + "\n")
     print("\n".join(rep))
 
