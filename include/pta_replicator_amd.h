@@ -692,6 +692,28 @@ int pta_os_matched_pairs(const double *X, const double *Z, int P, int C, int R, 
                          const double *G, const double *G2, int n_orf, double *A2, int64_t ld_a2, double *sigma, int64_t ld_sigma, double *rho,
                          double *sigma_pair, int64_t ld_pair, void *stream);
 
+/* ---- per-frequency optimal statistic (ABI 8, additive) ----
+ * The cross-correlated power of every Fourier bin instead of one broadband amplitude.  C = 2 n_f even, column 2 k / 2 k + 1 = sin / cos
+ * of bin k.  Per pair p = (a < b):  n_p[k] = X_a[2k] X_b[2k] + X_a[2k+1] X_b[2k+1],
+ * D_p[k, j] = sum_{i in {2k, 2k+1}} sum_{l in {2j, 2j+1}} Z_a[i, l] Z_b[i, l];  per ORF o < n_orf <= 8:  b_o = sum_p G[o, p] n_p,
+ * F_o = sum_p G[o, p]^2 D_p.  mode 0 ("full"): a2_o = F_o^-1 b_o, sigma_o[k] = sqrt((F_o^-1)_kk); mode 1 ("narrowband"):
+ * a2_o[k] = b_o[k] / F_o[k, k], sigma_o[k] = F_o[k, k]^-1/2.
+ *
+ * pta_os_pairs_pf (fixed noise): Y [R, P C] of pta_os_project; op = F^-1 [n_orf, n_f, n_f] (mode 0) or 1 / diag F [n_orf, n_f] (mode 1),
+ * prepared by the host; a2[r * ld_a2 + o * n_f + k].  One workgroup per realisation, Y_r in LDS (P * C * 8 <= 64 KiB).
+ *
+ * pta_os_matched_pairs_pf (per-realisation noise): X [R, P, C] and the packed Z [R, P, C (C + 1) / 2] of pta_os_matched_solve, G and
+ * G2 = G * G [n_orf, n_pairs]; a2[r * ld_a2 + o * n_f + k], sigma[r * ld_sigma + o * n_f + k] and, where fisher is not NULL,
+ * fisher[r * ld_fisher + (o * n_f + k) * n_f + j] = F_o[k, j].  One workgroup per realisation; F_o is accumulated in registers, joined
+ * and solved in LDS (Jacobi-scaled Cholesky, up to 74 KiB).  A non-positive pivot (mode 1: diagonal entry) gives NaN in a2 and
+ * sigma of that (realisation, ORF).  Both: 2 <= C <= 64 (PTA_E_ARG beyond, as for odd C, n_orf > 8 and NULL operands); fixed
+ * summation order, bit-identical per realisation whatever R.                                                                        */
+int pta_os_pairs_pf(const double *Y, int64_t ld_y, int P, int C, int R, const int32_t *pair_a, const int32_t *pair_b, int n_pairs,
+                    const double *G, int n_orf, const double *op, int mode, double *a2, int64_t ld_a2, void *stream);
+int pta_os_matched_pairs_pf(const double *X, const double *Z, int P, int C, int R, const int32_t *pair_a, const int32_t *pair_b, int n_pairs,
+                            const double *G, const double *G2, int n_orf, int mode, double *a2, int64_t ld_a2, double *sigma,
+                            int64_t ld_sigma, double *fisher, int64_t ld_fisher, void *stream);
+
 /* ---- marginalised log-likelihood on a grid of noise parameters (ABI 8, additive) ----
  * The noise model is the one of the statistic above (white noise, ECORR and the timing model fixed and the timing model marginalised
  * with a flat prior; red noise on the K_rn red-noise columns, a common uncorrelated process with the GWB spectrum on the last C).

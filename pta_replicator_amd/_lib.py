@@ -159,6 +159,8 @@ _SIGNATURES = {
     "pta_os_matched_prior": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, _P]),
     "pta_os_matched_solve": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P]),
     "pta_os_matched_pairs": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P]),
+    "pta_os_pairs_pf": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, _P, c_int, _P, c_int64, _P]),
+    "pta_os_matched_pairs_pf": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P]),
     "pta_lnl_quad": (c_int, [_P, c_int64, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, _P, _P]),
     "pta_lnl_factor": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_lnl_apply": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int64, _P]),

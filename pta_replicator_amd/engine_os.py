@@ -20,6 +20,11 @@ GWB auto-term; white noise, ECORR and the timing model stay fixed): V = U^T P0' 
     pta_os_matched_pairs   A2, sigma (and rho, sigma_pair) per realisation
 
 with sigma (and sigma_pair) per realisation.
+
+``optimal_statistic_spectrum(rows)`` and ``generate_os_spectrum(R)`` return the per-frequency statistic instead: the cross-correlated
+power of every Fourier bin per ORF, a2 = F^-1 b ("full") or b_k / F_kk ("narrowband"), without a spectral shape.  The front is the
+same (pta_os_project, or project / prior / solve with theta); the pair stage is pta_os_pairs_pf (F fixed, its inverse prepared on the
+host at the first call) or pta_os_matched_pairs_pf (F accumulated and solved per realisation in LDS).
 """
 import ctypes
 
@@ -135,13 +140,7 @@ class OptimalStatisticMixin:
         row r is then weighted with the noise model of theta[r] (keys not given and NaN red-noise amplitudes: as configured / as
         prepared; cw_* keys are ignored).  sigma is then [R, n_orf] and sigma_pair [R, n_pairs]."""
         st = self._os_state("optimal_statistic")
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
-            raise ValueError("rows must be a float64 device tensor")
-        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
-        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
-            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
-        R = int(rows.shape[0])
+        R = self._os_check_rows(rows)
         if theta is not None:
             dev = self._os_matched_theta(st, theta, R, "optimal_statistic")
             out = self._os_matched_out(st, R, pairs)
@@ -153,22 +152,38 @@ class OptimalStatisticMixin:
         self._os_launch(rows, R, out["A2"], out["rho"])
         return self._os_result(st, out["A2"], out["rho"])
 
+    def _os_check_rows(self, rows):
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
+            raise ValueError("rows must be a float64 device tensor")
+        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
+        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
+            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
+        return int(rows.shape[0])
+
     def _os_result(self, st, A2, rho):
         res = {"A2": A2, "snr": A2 / st["sigma"], "sigma": st["sigma"], "names": list(st["names"])}
         if rho is not None:
             res.update(rho=rho, sigma_pair=st["sigma_pair"], zeta=st["zeta"], pairs=st["pairs"])
         return res
 
-    def _os_launch(self, rows, R, A2, rho):
-        """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream"""
+    def _os_project(self, rows, R):
+        """pta_os_project of rows [R, n_toa] into the reused Y buffer [>= R, P * C], on the current stream"""
         st = self._os
         P, C = self.P, st["C"]
         if st["Y"] is None or st["Y"].shape[0] < R:
             st["Y"] = dv.empty((R, P * C))
         Y = st["Y"]
-        s = dv.stream_ptr()
         _lib.call("pta_os_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), R,
-                  dv.ptr(Y), P * C, s)
+                  dv.ptr(Y), P * C, dv.stream_ptr())
+        return Y
+
+    def _os_launch(self, rows, R, A2, rho):
+        """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream"""
+        st = self._os
+        P, C = self.P, st["C"]
+        Y = self._os_project(rows, R)
+        s = dv.stream_ptr()
         npairs = len(st["plan"].den)
         _lib.call("pta_os_pairs", dv.ptr(Y), P * C, P, C, R, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(st["wt"]), st["n_orf"],
                   ctypes.c_void_p(A2.data_ptr()), A2.stride(0), dv.ptr(st["den"]) if rho is not None else None,
@@ -194,18 +209,28 @@ class OptimalStatisticMixin:
                 raise ValueError("generate_os: matched=True needs theta (the noise parameters every realisation is evaluated under)")
             mdev = self._os_matched_theta(st, theta, R, "generate_os")
             chunk = min(chunk, self._os_matched_chunk(st, R, with_rows=True))
-        per_real = 8 * (self.n_toa + self.P * st["C"])
-        chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
-        buf = getattr(self, "_os_rows", None)
-        if buf is None or buf.shape[0] < chunk:
-            self._os_rows = None
-            buf = self._os_rows = dv.empty((chunk, self.n_toa))
         A2 = rho = mout = None
         if matched:
             mout = self._os_matched_out(st, R, pairs)
         else:
             A2 = dv.empty((R, st["n_orf"]))
             rho = dv.empty((R, len(st["plan"].den))) if pairs else None
+        for lo, n, rows in self._os_generate_chunks("generate_os", st, R, r0, hyper, cw, td, chunk):
+            if matched:
+                self._os_matched_launch(rows, n, mdev, lo, mout)
+            else:
+                self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
+        return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho)
+
+    def _os_generate_chunks(self, what, st, R, r0, hyper, cw, td, chunk):
+        """realisations r0 .. r0+R-1 generated chunk by chunk into the reused [chunk, n_toa] buffer (the chunk cut so that rows and Y
+        stay within workspace_bytes): yields (lo, n, rows [n, n_toa]) per chunk"""
+        per_real = 8 * (self.n_toa + self.P * st["C"])
+        chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
+        buf = getattr(self, "_os_rows", None)
+        if buf is None or buf.shape[0] < chunk:
+            self._os_rows = None
+            buf = self._os_rows = dv.empty((chunk, self.n_toa))
 
         def rows_of(part, lo, n):
             return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
@@ -218,12 +243,8 @@ class OptimalStatisticMixin:
                     self._cw_apply(rows_of(cw, lo, n), n, rows)
             else:
                 self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
-            self._os_state("generate_os")     # generate_td / generate may have (re)prepared the engine
-            if matched:
-                self._os_matched_launch(rows, n, mdev, lo, mout)
-            else:
-                self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
-        return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho)
+            self._os_state(what)     # generate_td / generate may have (re)prepared the engine
+            yield lo, n, rows
 
     # ---- the OS under per-realisation noise parameters ----
     def _os_matched_theta(self, st, theta, R, what):
@@ -271,9 +292,9 @@ class OptimalStatisticMixin:
             res.update(rho=out["rho"], sigma_pair=out["sigma_pair"], zeta=st["zeta"], pairs=st["pairs"])
         return res
 
-    def _os_matched_launch(self, rows, n, dev, lo, out):
-        """rows [n, n_toa] = realisations lo .. lo+n-1 of theta `dev` -> rows lo .. of out: pta_os_project per block of 64 rows of V,
-        pta_os_matched_prior, pta_os_matched_solve, pta_os_matched_pairs, all on the current stream"""
+    def _os_matched_front(self, rows, n, dev, lo):
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of theta `dev` -> the workspace with X [n, P C] and packed Z [n, P nz]:
+        pta_os_project per block of 64 rows of V, pta_os_matched_prior, pta_os_matched_solve, all on the current stream"""
         st = self._os
         m = st["matched"]
         P, C, K, K_rn, nz = self.P, st["C"], m["K"], m["K_rn"], m["nz"]
@@ -295,11 +316,144 @@ class OptimalStatisticMixin:
                   at(dev["gw_gamma"], 1), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
         _lib.call("pta_os_matched_solve", dv.ptr(m["A"]), P, K, C, n, dv.ptr(ws["b"]), dv.ptr(ws["q"]), P * K, blk, dv.ptr(m["S"]), dv.ptr(m["s"]),
                   dv.ptr(ws["X"]), dv.ptr(ws["Z"]), s)
+        self._os_theta_keep = dev   # the launches above read these buffers asynchronously
+        return ws
+
+    def _os_matched_launch(self, rows, n, dev, lo, out):
+        """_os_matched_front, then pta_os_matched_pairs into rows lo .. of out"""
+        st = self._os
+        m = st["matched"]
+        ws = self._os_matched_front(rows, n, dev, lo)
         npairs = len(st["plan"].den)
         A2, sg, rho, sp = out["A2"], out["sigma"], out["rho"], out["sigma_pair"]
 
         def row(x):
             return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * x.stride(0))
-        _lib.call("pta_os_matched_pairs", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
-                  dv.ptr(m["G2"]), st["n_orf"], row(A2), A2.stride(0), row(sg), sg.stride(0), row(rho), row(sp), rho.stride(0) if rho is not None else 0, s)
-        self._os_theta_keep = dev   # the launches above read these buffers asynchronously
+        _lib.call("pta_os_matched_pairs", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), self.P, st["C"], n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
+                  dv.ptr(m["G2"]), st["n_orf"], row(A2), A2.stride(0), row(sg), sg.stride(0), row(rho), row(sp), rho.stride(0) if rho is not None else 0,
+                  dv.stream_ptr())
+
+    # ---- the per-frequency OS: the spectrum per realisation ----
+    def _os_spectrum_check(self, what, st, mode, theta, matched):
+        """the refusals shared by the two entry points, in their documented order -> the mode flag of the kernels"""
+        if mode not in ost.SPECTRUM_MODES:
+            raise ValueError(f"{what}: mode={mode!r} must be one of {ost.SPECTRUM_MODES}")
+        if theta is not None and matched and st["matched"] is None:
+            raise ValueError(f"{what}: theta needs prepare_optimal_statistic(matched=True)")
+        if matched and theta is None:
+            raise ValueError(f"{what}: matched=True needs theta (the noise parameters every realisation is evaluated under)")
+        return ost.SPECTRUM_MODES.index(mode)
+
+    def _os_spectrum_state(self, st):
+        """the fixed-noise operands of the per-frequency OS, built on the host at the first spectrum call: F [n_orf, n_f, n_f], F^-1 and
+        sigma of both modes, the template S_k and the frequencies"""
+        sp = st.get("spectrum")
+        if sp is None:
+            plan = st["plan"]
+            F = ost.spectrum_fisher(plan)
+            nf = F.shape[-1]
+            # right-hand sides e_j [n_f, 1, n_f] against F [n_orf, n_f, n_f] broadcast to x[j, o, :] = F_o^-1 e_j; F^-1[o, k, j] = x[j, o, k]
+            Finv = ost.spectrum_solve(F, np.eye(nf)[:, None, :], "full")[0].transpose(1, 2, 0)
+            sp = st["spectrum"] = dict(F=dv.f64(F), op=(dv.f64(Finv), dv.f64(1.0 / np.diagonal(F, axis1=1, axis2=2))),
+                                       sigma=tuple(dv.f64(ost.spectrum_solve(F, np.zeros(nf), mode)[1]) for mode in ost.SPECTRUM_MODES),
+                                       G=dv.f64(plan.G))
+        return sp
+
+    def _os_spectrum_axes(self, st):
+        """(S_k [n_f], f_k [n_f]) on the device: the unit template per bin and the frequencies, the same for the fixed and the matched path"""
+        ax = st.get("spectrum_axes")
+        if ax is None:
+            plan = st["plan"]
+            ax = st["spectrum_axes"] = (dv.f64(plan.S[0::2]), dv.f64(np.arange(1, plan.C // 2 + 1) / plan.T))
+        return ax
+
+    def _os_spectrum_out(self, st, R, matched, fisher):
+        nf = st["C"] // 2
+        return {"a2": dv.empty((R, st["n_orf"], nf)), "sigma": dv.empty((R, st["n_orf"], nf)) if matched else None,
+                "fisher": dv.empty((R, st["n_orf"], nf, nf)) if matched and fisher else None}
+
+    def _os_spectrum_launch(self, rows, n, mode, dev, lo, out):
+        """the per-frequency OS of rows [n, n_toa] into rows lo .. of out: pta_os_project + pta_os_pairs_pf, or with theta `dev` the
+        front of the matched OS + pta_os_matched_pairs_pf"""
+        st = self._os
+        P, C, n_orf = self.P, st["C"], st["n_orf"]
+        npairs = len(st["plan"].den)
+
+        def row(x):
+            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * x.stride(0))
+        a2 = out["a2"]
+        if dev is None:
+            sp = self._os_spectrum_state(st)
+            Y = self._os_project(rows, n)
+            _lib.call("pta_os_pairs_pf", dv.ptr(Y), P * C, P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(sp["G"]), n_orf,
+                      dv.ptr(sp["op"][mode]), mode, row(a2), a2.stride(0), dv.stream_ptr())
+            return
+        m = st["matched"]
+        ws = self._os_matched_front(rows, n, dev, lo)
+        sg, fi = out["sigma"], out["fisher"]
+        _lib.call("pta_os_matched_pairs_pf", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
+                  dv.ptr(m["G2"]), n_orf, mode, row(a2), a2.stride(0), row(sg), sg.stride(0), row(fi), fi.stride(0) if fi is not None else 0,
+                  dv.stream_ptr())
+
+    def _os_spectrum_result(self, st, out, mode, matched, fisher):
+        Sk, freqs = self._os_spectrum_axes(st)
+        if matched:
+            sigma = out["sigma"]
+        else:
+            sp = self._os_spectrum_state(st)
+            sigma = sp["sigma"][mode]
+        a2 = out["a2"]
+        res = {"a2": a2, "sigma": sigma, "snr": a2 / sigma, "phi": a2 * Sk, "phi_sigma": (sigma * Sk).expand(a2.shape), "freqs": freqs,
+               "names": list(st["names"])}
+        if fisher:
+            res["fisher"] = out["fisher"] if matched else sp["F"]
+        return res
+
+    def optimal_statistic_spectrum(self, rows, theta=None, mode="full", fisher=False):
+        """Per-frequency OS of every realisation of rows [R, n_toa] (as optimal_statistic takes them): the cross-correlated power of every
+        Fourier bin f_k = (k + 1) / T per ORF, without a spectral shape.  Returns a dict of device tensors: a2 [R, n_orf, n_f] (the bin's
+        GW variance over the unit template: A^2 in every bin if the data follow the template), sigma [n_orf, n_f], snr = a2 / sigma,
+        phi = a2 S_k and phi_sigma = sigma S_k (the variance of one sin / cos coefficient [s^2]), freqs [n_f], names; with fisher=True
+        also fisher [n_orf, n_f, n_f].
+
+        mode "full": a2 = F^-1 b with the coupling between the bins, sigma_k = sqrt((F^-1)_kk); "narrowband": a2_k = b_k / F_kk,
+        sigma_k = F_kk^-1/2.  theta (needs prepare_optimal_statistic(matched=True)): as optimal_statistic's; F then follows theta per
+        realisation, sigma is [R, n_orf, n_f] and fisher [R, n_orf, n_f, n_f]."""
+        what = "optimal_statistic_spectrum"
+        st = self._os_state(what)
+        mode = self._os_spectrum_check(what, st, mode, theta, theta is not None)
+        R = self._os_check_rows(rows)
+        matched = theta is not None
+        if not matched:
+            self._os_spectrum_state(st)
+            out = self._os_spectrum_out(st, R, False, fisher)
+            self._os_spectrum_launch(rows, R, mode, None, 0, out)
+            return self._os_spectrum_result(st, out, mode, False, fisher)
+        dev = self._os_matched_theta(st, theta, R, what)
+        out = self._os_spectrum_out(st, R, True, fisher)
+        step = self._os_matched_chunk(st, R, with_rows=False)
+        for lo in range(0, R, step):
+            self._os_spectrum_launch(rows[lo:lo + step], min(step, R - lo), mode, dev, lo, out)
+        return self._os_spectrum_result(st, out, mode, True, fisher)
+
+    def generate_os_spectrum(self, R, r0=0, theta=None, td=False, chunk=1024, matched=False, mode="full", fisher=False):
+        """Per-frequency OS of realisations r0 .. r0+R-1, generated chunk by chunk as generate_os does; only the statistics are kept.
+        Same results as optimal_statistic_spectrum(generate(R, r0, ...)), bit for bit, whatever the chunk; with matched=True (needs
+        theta) every chunk is evaluated under the theta it was generated with."""
+        what = "generate_os_spectrum"
+        st = self._os_state(what)
+        R, r0, chunk = int(R), int(r0), int(chunk)
+        if R < 1 or chunk < 1 or r0 < 0:
+            raise ValueError(f"{what}: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
+        mode = self._os_spectrum_check(what, st, mode, theta, matched)
+        hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
+        mdev = None
+        if matched:
+            mdev = self._os_matched_theta(st, theta, R, what)
+            chunk = min(chunk, self._os_matched_chunk(st, R, with_rows=True))
+        else:
+            self._os_spectrum_state(st)
+        out = self._os_spectrum_out(st, R, matched, fisher)
+        for lo, n, rows in self._os_generate_chunks(what, st, R, r0, hyper, cw, td, chunk):
+            self._os_spectrum_launch(rows, n, mode, mdev, lo, out)
+        return self._os_spectrum_result(st, out, mode, matched, fisher)
