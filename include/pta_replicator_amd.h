@@ -49,7 +49,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * (red_noise.py:119,127,176,238-240; white_noise.py:80,105-109,155,182); on the device every
  * deviate is Philox-4x32-10(key = seed, counter = (pair, stream, realisation)) + Box-Muller.
  * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor),
- * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform),
+ * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform.  Field 1: the
+ * nodes of a per-realisation GWB spectrum, pair j = node j; pta_hyper_uniform_field),
  * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform.  In a catalogue the
  * field is the source index s, pta_cw_catalog_uniform). */
 
@@ -298,6 +299,15 @@ int pta_gwb_idft_rng_scaled(uint64_t seed, uint64_t r0, int R, int P, int Nf, co
  * hcf0 = the configured spectrum's hcf on the grid f (red_noise.gwb_spectrum_hcf).                                      */
 int pta_gwb_spectrum_scale(const double *f, const double *hcf0, int Nf, int R, const double *log10_A, const double *gamma, int turnover,
                            double f0, double beta, double power, double *scale, int64_t ld_scale, void *stream);
+/* The same factor for a spectrum given per realisation (ABI 8, additive): log10_hc[r * ld_hc + j], j < M, the log10 characteristic
+ * strain of realisation r at the M >= 2 (<= 4096) nodes of a userSpec, sorted by frequency.  hc_r(f) is the userSpec branch of
+ * red_noise.gwb_spectrum_hcf (red_noise.py:255-263): log10 hc linear in log10 f between the nodes, constant outside them.  The
+ * host tabulates per bin k what does not depend on the values: seg[k] = j with xp[j] <= log10 f[k] < xp[j + 1], dx[k] = log10 f[k] -
+ * xp[j], dxp[k] = xp[j + 1] - xp[j]; dxp[k] = 0 marks a bin that takes node seg[k] itself (outside the nodes, or on one).
+ *   scale[r * ld_scale + k] = 10^(((fp[j + 1] - fp[j]) / dxp[k]) dx[k] + fp[j]) / hcf0[k],   fp = log10_hc + r * ld_hc
+ * (numpy.interp's operations in its order).  The caller points pta_engine_hyper.gw_scale at the result.  ld_hc >= M, ld_scale >= Nf. */
+int pta_gwb_spectrum_scale_user(const int32_t *seg, const double *dx, const double *dxp, const double *hcf0, int Nf, int M, int R,
+                                const double *log10_hc, int64_t ld_hc, double *scale, int64_t ld_scale, void *stream);
 
 /* G[r,a,:] = sum_b Mchol[a,b] G0[r,b,:]  (the M@w of red_noise.py:268, applied after the DFT). */
 /* variant 0 (default): LDS-resident Mchol kernel when P <= 80, generic batched MFMA GEMM otherwise; 1: always the generic
@@ -417,6 +427,10 @@ int pta_engine_generate(const pta_engine_plan *plan_host, const pta_engine_table
 /* out[r * n_par + j] = lo[j] + (hi[j] - lo[j]) u (one fma), u = uniform u2 of pair j of stream (HYPER, 0), realisation r0 + r:
  * theta of a realisation is a pure function of (seed, realisation).  lo / hi: device [n_par].                            */
 int pta_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *lo, const double *hi, double *out, void *stream);
+/* The same from stream (HYPER, field), 0 <= field < 2^24: field 0 is pta_hyper_uniform bit for bit; field 1 holds the nodes of a
+ * per-realisation GWB spectrum (pair j = node j), so the columns of field 0 do not move when a spectrum is sampled too.       */
+int pta_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_par, int field, const double *lo, const double *hi, double *out,
+                            void *stream);
 
 /* pta_engine_rn_coef with sqrt(prior) computed per (r, a, c) (red_noise.py:126):
  *   coef[(r*P + a)*K + c] = sqrt(A^2 (f / fyr)^-gamma / (12 pi^2 Tspan_a) yr^3) * z(seed, r0+r, (RN,a), c),
@@ -676,6 +690,12 @@ int pta_os_pairs(const double *Y, int64_t ld_y, int P, int C, int R, const int32
 int pta_os_matched_prior(int R, int P, int K_rn, int C, const double *rn_f, const double *rn_tspan, const double *rn_phi, const double *rn_log10_A,
                          const double *rn_gamma, double T, const double *gw_log10_A, const double *gw_gamma, const double *s, double *b,
                          void *stream);
+/* pta_os_matched_prior_spec: pta_os_matched_prior with the GW columns from a per-realisation spectrum (log10_hc, ld_hc, M as for
+ * pta_gwb_spectrum_scale_user): column K_rn + c is hc_r(f)^2 / (12 pi^2 f^3 T) / s[a], f = (c / 2 + 1) / T, the same quantity as above
+ * with hc^2 = A^2 (f yr)^(3 - gamma); seg, dx, dxp [C / 2]: the interpolation tables of the C / 2 frequencies.                        */
+int pta_os_matched_prior_spec(int R, int P, int K_rn, int C, const double *rn_f, const double *rn_tspan, const double *rn_phi,
+                              const double *rn_log10_A, const double *rn_gamma, double T, const int32_t *seg, const double *dx, const double *dxp,
+                              int M, const double *log10_hc, int64_t ld_hc, const double *s, double *b, void *stream);
 /* pta_os_matched_solve: X[(r * P + a) * C + c] and the packed lower triangle Z[(r * P + a) * C (C + 1) / 2 + c (c + 1) / 2 + c2] (c2 <= c)
  * from A [P, K, K] (symmetric), b [R, P, K] (>= 0, zeros allowed), S [C], s [P] and q: element (r, a, k) at
  * q[r * ld_q + P * k0 + a * cb + (k - k0)], k0 = (k / q_block) * q_block, cb = min(q_block, K - k0) - what pta_os_project writes when it

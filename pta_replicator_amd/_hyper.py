@@ -4,6 +4,7 @@ sampled theta.  Plain functions of the configuration and the arrays, so that the
 theta is a dict with any subset of
     gwb_log10_A, gwb_gamma   [R]      GWB amplitude / spectral index of realisation r0 + r
     rn_log10_A, rn_gamma     [R, P]   red-noise amplitude / spectral index of pulsar a in realisation r0 + r
+    gwb_log10_hc             [R, M]   log10 characteristic strain of realisation r0 + r at the M nodes of the configured userSpec
 as NumPy arrays or torch tensors.  A key that is not given keeps its configured value.  NaN in rn_log10_A means "this pulsar as
 configured" (amplitude and index); a pulsar configured without red noise keeps none whatever its entries say.
 """
@@ -12,6 +13,13 @@ import numpy as np
 GWB_KEYS = ("gwb_log10_A", "gwb_gamma")
 RN_KEYS = ("rn_log10_A", "rn_gamma")
 KEYS = GWB_KEYS + RN_KEYS
+# the per-realisation GWB spectrum of an engine configured with set_gwb(userSpec=U [M, 2]): row r replaces log10(U[:, 1]), column j
+# belongs to row j of U as given.  Kept beside KEYS: it is no column of the pta_hyper_uniform table (its nodes are drawn from
+# stream (7, SPEC_FIELD), pair = node)
+SPEC_KEY = "gwb_log10_hc"
+SPEC_FIELD = 1
+SPEC_MAX_NODES = 4096   # PTA_GWB_SPEC_MMAX: the nodes of one realisation are staged in LDS
+ALL_KEYS = KEYS + (SPEC_KEY,)
 
 
 def n_columns(P):
@@ -27,9 +35,11 @@ def columns(P):
 def check_config(keys, gw, rn, gwb_mode):
     """refuse theta keys the configuration cannot honour (before anything is launched)."""
     keys = set(keys)
-    unknown = keys - set(KEYS)
+    unknown = keys - set(ALL_KEYS)
     if unknown:
-        raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(KEYS)})")
+        raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(ALL_KEYS)})")
+    if SPEC_KEY in keys and gw is None:
+        raise ValueError("theta: a GWB spectrum given but no GWB is configured (set_gwb)")
     if keys & set(GWB_KEYS):
         if gw is None:
             raise ValueError("theta: GWB parameters given but no GWB is configured (set_gwb)")
@@ -37,8 +47,65 @@ def check_config(keys, gw, rn, gwb_mode):
             raise ValueError("theta: GWB parameters cannot rescale a userSpec spectrum (only the power law has (log10_A, gamma))")
         if gwb_mode == "grid":
             raise ValueError("theta: GWB parameters need gwb_mode='fourier' (the 'grid' factor is built for one spectrum)")
+    if SPEC_KEY in keys:
+        if gw.get("userSpec") is None:
+            raise ValueError(f"theta: {SPEC_KEY} needs a GWB configured with a userSpec spectrum (its frequency column fixes the nodes)")
+        if keys & set(GWB_KEYS):
+            raise ValueError("theta: GWB parameters cannot rescale a userSpec spectrum (only the power law has (log10_A, gamma))")
+        if gwb_mode == "grid":
+            raise ValueError(f"theta: {SPEC_KEY} needs gwb_mode='fourier' (the 'grid' factor is built for one spectrum)")
+        spec_nodes(gw["userSpec"])
     if keys & set(RN_KEYS) and rn is None:
         raise ValueError("theta: red-noise parameters given but no red noise is configured (set_red_noise)")
+
+
+def spec_nodes(userSpec):
+    """(order [M], xp [M]) of a userSpec [M, 2]: the stable sort by frequency that red_noise.gwb_spectrum_hcf applies and log10 of the
+    sorted node frequencies.  Refuses what a per-realisation spectrum cannot be interpolated on."""
+    U = np.asarray(userSpec, dtype=np.float64)
+    if U.ndim != 2 or U.shape[1] != 2 or U.shape[0] < 2:
+        raise ValueError(f"userSpec: a per-realisation spectrum needs at least 2 node frequencies ([M, 2], M >= 2), got shape {U.shape}")
+    if U.shape[0] > SPEC_MAX_NODES:
+        raise ValueError(f"userSpec: a per-realisation spectrum takes at most {SPEC_MAX_NODES} node frequencies, got {U.shape[0]}")
+    order = np.argsort(U[:, 0], kind="mergesort")
+    f = U[order, 0]
+    if not np.all(np.isfinite(f)) or np.any(f <= 0) or np.any(np.diff(f) <= 0):
+        raise ValueError("userSpec: a per-realisation spectrum needs finite, positive and distinct node frequencies")
+    if not np.all(np.isfinite(U[:, 1])) or np.any(U[:, 1] <= 0):   # the configured hc is the divisor of the per-realisation scale
+        raise ValueError("userSpec: a per-realisation spectrum needs finite, positive hc at every node")
+    return order, np.log10(f)
+
+
+def spec_tables(f, xp):
+    """(seg int32 [n], dx [n], dxp [n]) for frequencies f and sorted node abscissae xp = log10(node frequencies): what numpy.interp
+    derives from the abscissae alone.  seg = j with xp[j] <= log10 f < xp[j + 1], dx = log10 f - xp[j], dxp = xp[j + 1] - xp[j];
+    dxp = 0 marks a frequency that takes node seg itself: below the first node (seg 0), at or above the last (seg M - 1), or
+    exactly on a node.  pta_gwb_hcf_user (csrc/pta_hyper.h) and spec_eval evaluate a spectrum from them."""
+    x = np.log10(np.asarray(f, dtype=np.float64))
+    xp = np.asarray(xp, dtype=np.float64)
+    M = len(xp)
+    j = np.searchsorted(xp, x, side="right") - 1
+    seg = np.clip(j, 0, M - 1)
+    dx = x - xp[seg]
+    inside = (j >= 0) & (j < M - 1) & (dx != 0.0)
+    dxp = np.where(inside, xp[np.minimum(seg + 1, M - 1)] - xp[seg], 0.0)
+    return seg.astype(np.int32), np.where(inside, dx, 0.0), dxp
+
+
+def spec_eval(tables, fp):
+    """hc [..., n] of spectra with sorted node values fp [..., M] (log10 hc) at the frequencies of `tables` (spec_tables): NumPy form
+    of pta_gwb_hcf_user, the same operations in the same order."""
+    seg, dx, dxp = tables
+    fp = np.asarray(fp, dtype=np.float64)
+    lo = fp[..., seg]
+    hi = fp[..., np.minimum(seg + 1, fp.shape[-1] - 1)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = np.where(dxp != 0.0, (hi - lo) / dxp * dx + lo, lo)
+    return 10.0 ** y
+
+
+def _n_nodes(gw):
+    return None if gw is None or gw.get("userSpec") is None else int(np.shape(gw["userSpec"])[0])
 
 
 def _xp(x):
@@ -64,38 +131,48 @@ def check_theta(theta, R, P, gw, rn, gwb_mode, check_values=True):
     if not isinstance(theta, dict):
         raise ValueError("theta must be a dict of per-realisation parameters")
     check_config(theta.keys(), gw, rn, gwb_mode)
-    return _check_arrays(theta, R, P, rn, check_values)
+    return _check_arrays(theta, R, P, rn, check_values, _n_nodes(gw))
 
 
-def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True):
+def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True, gw=None):
     """validate theta as the noise model of the optimal statistic (optimal_statistic(theta=...), generate_os(matched=True)): keys,
     shapes and NaN rules of check_theta, without its gwb_mode restriction (the OS does not care how the GWB was generated).  GWB
     keys are refused when the OS was prepared without the GWB auto-term (gwb_auto false); cw_* keys are ignored (a deterministic
-    source is not part of the noise model).  Returns {key: array} of the GWB / red-noise keys."""
+    source is not part of the noise model).  gw: the engine's GWB configuration; given, the spectrum key gwb_log10_hc is accepted too
+    (its nodes are the configured userSpec's; left out, as by the likelihood grid, the key is unknown).  Returns {key: array} of the
+    GWB / red-noise keys."""
     from . import _cw
     theta, _ = _cw.split(theta)
-    unknown = set(theta) - set(KEYS)
+    known = KEYS if gw is None else ALL_KEYS
+    unknown = set(theta) - set(known)
     if unknown:
-        raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(KEYS)})")
-    if set(theta) & set(GWB_KEYS) and not gwb_auto:
+        raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(known)})")
+    if set(theta) & set(GWB_KEYS + (SPEC_KEY,)) and not gwb_auto:
         raise ValueError("theta: GWB parameters given but the optimal statistic was prepared without the GWB auto-term (gwb_auto)")
+    if SPEC_KEY in theta:
+        if gw.get("userSpec") is None:
+            raise ValueError(f"theta: {SPEC_KEY} needs a GWB configured with a userSpec spectrum (its frequency column fixes the nodes)")
+        if set(theta) & set(GWB_KEYS):
+            raise ValueError("theta: GWB parameters cannot rescale a userSpec spectrum (only the power law has (log10_A, gamma))")
+        spec_nodes(gw["userSpec"])
     if set(theta) & set(RN_KEYS) and rn is None:
         raise ValueError("theta: red-noise parameters given but no red noise is configured (set_red_noise)")
-    return _check_arrays(theta, R, P, rn, check_values)
+    return _check_arrays(theta, R, P, rn, check_values, _n_nodes(gw))
 
 
-def _check_arrays(theta, R, P, rn, check_values):
-    """shapes and values of theta's GWB / red-noise arrays (keys already checked against the configuration)."""
+def _check_arrays(theta, R, P, rn, check_values, M=None):
+    """shapes and values of theta's GWB / red-noise arrays (keys already checked against the configuration); M: nodes of the
+    configured userSpec (the columns of gwb_log10_hc)."""
     out = {}
     for k, v in theta.items():
         v = _as_array(k, v)
-        want = (R,) if k in GWB_KEYS else (R, P)
+        want = (R,) if k in GWB_KEYS else (R, M) if k == SPEC_KEY else (R, P)
         if tuple(v.shape) != want:
             raise ValueError(f"theta[{k!r}]: shape {tuple(v.shape)}, expected {want}")
         out[k] = v
     if not check_values:
         return out
-    for k in GWB_KEYS:
+    for k in GWB_KEYS + (SPEC_KEY,):
         if k in out and not bool(_xp(out[k]).isfinite(out[k]).all()):
             raise ValueError(f"theta[{k!r}]: non-finite values")
     if "rn_log10_A" in out:
@@ -137,25 +214,36 @@ def prior_bounds(prior, P):
     lo, hi = np.zeros(n_columns(P)), np.zeros(n_columns(P))
     cols = columns(P)
     for k, (l, h) in prior.items():
+        if k == SPEC_KEY:   # its own table: spec_bounds
+            continue
         c0, c1 = cols[k]
         lo[c0:c1], hi[c0:c1] = l, h
     return lo, hi
 
 
-def make_prior(P, **boxes):
-    """validated {key: (lo [n], hi [n])} of set_hyper_prior: GWB keys take (lo, hi); RN keys (lo, hi) for all pulsars or [P, 2]."""
+def spec_bounds(prior):
+    """lo, hi [M] of pta_hyper_uniform_field(field = SPEC_FIELD) for the gwb_log10_hc boxes of a prior dict: column j = node j of the
+    userSpec as given; None when the spectrum is not sampled."""
+    return prior.get(SPEC_KEY)
+
+
+def make_prior(P, M=None, **boxes):
+    """validated {key: (lo [n], hi [n])} of set_hyper_prior: GWB keys take (lo, hi); RN keys (lo, hi) for all pulsars or [P, 2];
+    gwb_log10_hc (lo, hi) for all M nodes of the configured userSpec or [M, 2] (M None: no userSpec is configured)."""
     prior = {}
     for k, box in boxes.items():
         if box is None:
             continue
-        if k not in KEYS:
-            raise ValueError(f"set_hyper_prior: unknown parameter {k!r} (expected one of {list(KEYS)})")
+        if k not in ALL_KEYS:
+            raise ValueError(f"set_hyper_prior: unknown parameter {k!r} (expected one of {list(ALL_KEYS)})")
+        if k == SPEC_KEY and M is None:
+            raise ValueError(f"set_hyper_prior: {k} needs a GWB configured with a userSpec spectrum (its frequency column fixes the nodes)")
         b = np.asarray(box, dtype=np.float64)
-        n = 1 if k in GWB_KEYS else P
+        n = 1 if k in GWB_KEYS else M if k == SPEC_KEY else P
         if b.shape == (2,):
             b = np.broadcast_to(b, (n, 2))
         if b.shape != (n, 2):
-            raise ValueError(f"set_hyper_prior: {k} must be (lo, hi){'' if n == 1 else f' or [{P}, 2]'}, got shape {np.shape(box)}")
+            raise ValueError(f"set_hyper_prior: {k} must be (lo, hi){'' if n == 1 else f' or [{n}, 2]'}, got shape {np.shape(box)}")
         if not np.all(np.isfinite(b)) or np.any(b[:, 1] < b[:, 0]):
             raise ValueError(f"set_hyper_prior: {k} needs finite bounds with lo <= hi")
         prior[k] = (b[:, 0].copy(), b[:, 1].copy())

@@ -175,6 +175,9 @@ _SIGNATURES = {
     "pta_microbench": (c_int, [c_int, c_int64, c_int, c_int, POINTER(c_double)]),
     "pta_clock_probe": (c_int, [_P, c_int, c_int, c_int, _P]),
     "pta_selftest_mfma_f64": (c_int, [POINTER(c_double)]),
+    "pta_gwb_spectrum_scale_user": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P]),
+    "pta_hyper_uniform_field": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pta_os_matched_prior_spec": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, c_int, _P, c_int64, _P, _P, _P]),
 }
 
 ENGINE_TILE = 256   # PTA_ENGINE_TILE

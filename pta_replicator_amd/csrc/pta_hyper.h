@@ -21,6 +21,14 @@ PTA_HD double pta_hyper_draw(uint64_t seed, uint64_t realisation, uint32_t j, do
   return pta_hyper_affine(lo, hi, u2);
 }
 
+// parameter column j of a further field of the hyperparameter stream: stream (PTA_STREAM_HYPER, field), pair j.  Field 0 is
+// pta_hyper_draw bit for bit; field 1 holds the nodes of a per-realisation GWB spectrum (gwb_log10_hc)
+PTA_HD double pta_hyper_draw_field(uint64_t seed, uint64_t realisation, uint32_t field, uint32_t j, double lo, double hi) {
+  double u1, u2;
+  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_HYPER, field), j), u1, u2);
+  return pta_hyper_affine(lo, hi, u2);
+}
+
 // characteristic strain hc(f) of the power-law GWB, with the optional turnover (red_noise.py:245-251): same operations in the
 // same order as red_noise.gwb_spectrum_hcf
 PTA_HD double pta_gwb_hcf(double f, double log10_A, double gamma, int turnover, double f0, double beta, double power) {
@@ -32,6 +40,21 @@ PTA_HD double pta_gwb_hcf(double f, double log10_A, double gamma, int turnover, 
     hcf = hcf / pow(1.0 + pow(f / f0, power * si), 1.0 / power);
   }
   return hcf;
+}
+
+// characteristic strain hc(f) of a user-supplied spectrum (red_noise.py:255-263): log10 hc linear in log10 f between the M nodes
+// fp (sorted by frequency), constant outside them - the userSpec branch of red_noise.gwb_spectrum_hcf, with numpy.interp's
+// operations in numpy.interp's order.  What does not depend on fp is tabulated per frequency by the host (_hyper.spec_tables):
+// the segment j (xp[j] <= x < xp[j + 1], x = log10 f), dx = x - xp[j] and dxp = xp[j + 1] - xp[j]; dxp = 0 marks a frequency
+// that takes fp[j] itself (below the first node, at or above the last, or exactly on a node).  j is clamped to the table.
+PTA_HD double pta_gwb_hcf_user(const double *fp, int M, int j, double dx, double dxp) {
+  j = j < 0 ? 0 : (j > M - 1 ? M - 1 : j);
+  double y = fp[j];
+  if (dxp != 0.0 && j + 1 < M) {
+    const double slope = (fp[j + 1] - fp[j]) / dxp;
+    y = slope * dx + fp[j];
+  }
+  return pow(10.0, y);
 }
 
 // sqrt(prior) of one red-noise coefficient at frequency f [Hz] (red_noise.py:126):

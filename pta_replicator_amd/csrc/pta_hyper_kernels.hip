@@ -1,6 +1,8 @@
 // Per-realisation hyperparameters in throughput mode (ReplicaEngine.generate(theta=...), generate_sampled):
 //   pta_hyper_uniform          theta drawn on chip from uniform boxes, keyed by (seed, realisation) like the residuals
 //   pta_gwb_spectrum_scale     hcf(f_k; A_r, gamma_r) / hcf0(f_k) per (realisation, bin): the factor the scaled GWB transforms apply
+//   pta_gwb_spectrum_scale_user  the same factor for a spectrum given per realisation as M nodes of log10 hc (gwb_log10_hc)
+//   pta_hyper_uniform_field    pta_hyper_uniform on stream (HYPER, field): the prior draws of those nodes (field 1)
 //   pta_engine_rn_coef_hyper   k_engine_rn_coef with sqrt(prior) evaluated per (realisation, pulsar, frequency)
 // pta_engine_generate_hyper (pta_engine_kernels.hip) is pta_engine_generate with the last two stages above switched in, in the stage
 // order of pta_engine_generate: pta_engine_rn_coef_hyper -> pta_gwb_spectrum_scale -> scaled GWB transform -> ORF mix -> synthesis.
@@ -92,6 +94,65 @@ extern "C" int pta_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P
   PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_engine_rn_coef_hyper: problem too large");
   hipLaunchKernelGGL(k_engine_rn_coef_hyper, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, P, K, rn_f,
                      rn_tspan, log10_A, gamma, amp_fixed, coef, rng_fast ? 1 : 0);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+__global__ void k_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_par, uint32_t field, const double *__restrict__ lo,
+                                      const double *__restrict__ hi, double *__restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)R * n_par) return;
+  const int j = (int)(idx % n_par);
+  const int64_t r = idx / n_par;
+  out[idx] = pta_hyper_draw_field(seed, r0 + (uint64_t)r, field, (uint32_t)j, lo[j], hi[j]);
+}
+
+extern "C" int pta_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_par, int field, const double *lo, const double *hi,
+                                       double *out, void *stream) {
+  PTA_REQUIRE(lo && hi && out, PTA_E_ARG, "pta_hyper_uniform_field: NULL argument");
+  PTA_REQUIRE(R > 0 && n_par > 0, PTA_E_ARG, "pta_hyper_uniform_field: R=%d n_par=%d", R, n_par);
+  PTA_REQUIRE(field >= 0 && field <= 0xFFFFFF, PTA_E_ARG, "pta_hyper_uniform_field: field=%d does not fit the 24-bit stream field", field);
+  const int64_t total = (int64_t)R * n_par;
+  PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_hyper_uniform_field: problem too large");
+  hipLaunchKernelGGL(k_hyper_uniform_field, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, n_par, (uint32_t)field,
+                     lo, hi, out);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+#define PTA_GWB_SPEC_MMAX 4096  // nodes of one spectrum: 32 KiB of LDS
+#define PTA_GWB_SPEC_BINS 1024  // bins per workgroup: 4 per thread, so the M nodes are staged once per 1024 bins
+
+// One workgroup = PTA_GWB_SPEC_BINS consecutive bins of ONE realisation: its M node values go to LDS once, every thread then
+// evaluates its bins from the per-bin tables (no bracket search).  Lanes read and write consecutive doubles.
+__global__ __launch_bounds__(256) void k_gwb_spectrum_scale_user(const int32_t *__restrict__ seg, const double *__restrict__ dx,
+                                                                 const double *__restrict__ dxp, const double *__restrict__ hcf0, int Nf,
+                                                                 int M, int nb, const double *__restrict__ log10_hc, int64_t ld_hc,
+                                                                 double *__restrict__ scale, int64_t ld_scale) {
+  extern __shared__ __attribute__((aligned(16))) double fp[];
+  const int64_t r = blockIdx.x / nb;
+  const int k0 = (int)(blockIdx.x % nb) * PTA_GWB_SPEC_BINS;
+  const double *row = log10_hc + r * ld_hc;
+  for (int j = threadIdx.x; j < M; j += 256) fp[j] = row[j];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < PTA_GWB_SPEC_BINS / 256; ++i) {
+    const int k = k0 + i * 256 + (int)threadIdx.x;
+    if (k < Nf) scale[r * ld_scale + k] = pta_gwb_hcf_user(fp, M, seg[k], dx[k], dxp[k]) / hcf0[k];
+  }
+}
+
+extern "C" int pta_gwb_spectrum_scale_user(const int32_t *seg, const double *dx, const double *dxp, const double *hcf0, int Nf, int M, int R,
+                                           const double *log10_hc, int64_t ld_hc, double *scale, int64_t ld_scale, void *stream) {
+  PTA_REQUIRE(seg && dx && dxp && hcf0 && log10_hc && scale, PTA_E_ARG, "pta_gwb_spectrum_scale_user: NULL argument");
+  PTA_REQUIRE(M >= 2 && M <= PTA_GWB_SPEC_MMAX, PTA_E_ARG, "pta_gwb_spectrum_scale_user: M=%d (2..%d nodes)", M, PTA_GWB_SPEC_MMAX);
+  PTA_REQUIRE(Nf >= 3 && R > 0 && ld_scale >= Nf && ld_hc >= M, PTA_E_ARG, "pta_gwb_spectrum_scale_user: Nf=%d R=%d ld_scale=%lld ld_hc=%lld", Nf,
+              R, (long long)ld_scale, (long long)ld_hc);
+  const int nb = (int)pta_cdiv(Nf, PTA_GWB_SPEC_BINS);
+  PTA_REQUIRE((int64_t)R * ld_scale < (1LL << 31) && (int64_t)R * ld_hc < (1LL << 31) && (int64_t)R * nb < (1LL << 31), PTA_E_ARG,
+              "pta_gwb_spectrum_scale_user: problem too large");
+  hipLaunchKernelGGL(k_gwb_spectrum_scale_user, dim3((unsigned)((int64_t)R * nb)), dim3(256), (size_t)M * sizeof(double), pta_stream(stream), seg,
+                     dx, dxp, hcf0, Nf, M, nb, log10_hc, ld_hc, scale, ld_scale);
   PTA_LAUNCH_CHECK();
   return PTA_OK;
 }

@@ -23,3 +23,10 @@ PTA_HD double pta_osm_gw_b(double f, double T, double log10_A, double gamma, dou
   const double S = pow(fyr, gamma - 3.0) * pow(f, -gamma) / (12.0 * pow(pi, 2.0) * T);
   return pow(10.0, 2.0 * log10_A) * S / s;
 }
+
+// GW auto-term column at frequency f = k / T for a characteristic strain hc given directly (a per-realisation spectrum):
+// hc^2 / (12 pi^2 f^3 T) / s - pta_osm_gw_b with hc^2 = A^2 (f yr)^(3 - gamma)
+PTA_HD double pta_osm_gw_b_hc(double f, double T, double hc, double s) {
+  const double pi = 3.14159265358979323846;
+  return pow(hc, 2.0) / (12.0 * pow(pi, 2.0) * pow(f, 3.0) * T) / s;
+}

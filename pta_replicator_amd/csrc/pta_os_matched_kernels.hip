@@ -3,6 +3,7 @@
 //
 //   pta_os_project         q[r, a, :] = V_a r_a                       the existing projection, once per block of <= 64 rows of V
 //   pta_os_matched_prior   b[r, a, k] = prior variance / s            elementwise (pta_os_matched.h)
+//   pta_os_matched_prior_spec   the same with the GW columns from a per-realisation spectrum (M nodes of log10 hc)
 //   pta_os_matched_solve   X[r, a, :], Z[r, a, :, :]                  one workgroup per (realisation, pulsar), everything in LDS
 //   pta_os_matched_pairs   num, den, A2, sigma per realisation        one workgroup per realisation, one wave per pair
 //
@@ -41,6 +42,30 @@ __global__ void k_osm_prior(int R, int P, int K_rn, int C, const double *__restr
     v = pta_osm_rn_b(rn_f[(int64_t)a * (K_rn / 2) + k / 2], rn_tspan[a], lA, rn_log10_A ? rn_gamma[ra] : 0.0, rn_phi[(int64_t)a * K_rn + k], s[a]);
   } else {
     v = gw_log10_A ? pta_osm_gw_b((double)((k - K_rn) / 2 + 1) / T, T, gw_log10_A[r], gw_gamma[r], s[a]) : 0.0;
+  }
+  b[idx] = v;
+}
+
+// k_osm_prior with the GW columns hc_r(f_k)^2 / (12 pi^2 f_k^3 T) / s_a: hc_r interpolated from realisation r's M nodes with the
+// tables of the n_f = C / 2 frequencies k / T (pta_gwb_hcf_user); the node rows are a few hundred bytes, read through the cache
+__global__ void k_osm_prior_spec(int R, int P, int K_rn, int C, const double *__restrict__ rn_f, const double *__restrict__ rn_tspan,
+                                 const double *__restrict__ rn_phi, const double *__restrict__ rn_log10_A, const double *__restrict__ rn_gamma,
+                                 double T, const int32_t *__restrict__ seg, const double *__restrict__ dx, const double *__restrict__ dxp, int M,
+                                 const double *__restrict__ log10_hc, int64_t ld_hc, const double *__restrict__ s, double *__restrict__ b) {
+  const int K = K_rn + C;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)R * P * K) return;
+  const int k = (int)(idx % K);
+  const int64_t ra = idx / K;
+  const int a = (int)(ra % P);
+  const int64_t r = ra / P;
+  double v;
+  if (k < K_rn) {
+    const double lA = rn_log10_A ? rn_log10_A[ra] : NAN;
+    v = pta_osm_rn_b(rn_f[(int64_t)a * (K_rn / 2) + k / 2], rn_tspan[a], lA, rn_log10_A ? rn_gamma[ra] : 0.0, rn_phi[(int64_t)a * K_rn + k], s[a]);
+  } else {
+    const int c = (k - K_rn) / 2;
+    v = pta_osm_gw_b_hc((double)(c + 1) / T, T, pta_gwb_hcf_user(log10_hc + r * ld_hc, M, seg[c], dx[c], dxp[c]), s[a]);
   }
   b[idx] = v;
 }
@@ -197,6 +222,26 @@ extern "C" int pta_os_matched_prior(int R, int P, int K_rn, int C, const double 
   PTA_REQUIRE(total < (1LL << 31) * 256, PTA_E_ARG, "pta_os_matched_prior: problem too large");
   hipLaunchKernelGGL(k_osm_prior, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), R, P, K_rn, C, rn_f, rn_tspan, rn_phi,
                      rn_log10_A, rn_gamma, T, gw_log10_A, gw_gamma, s, b);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
+extern "C" int pta_os_matched_prior_spec(int R, int P, int K_rn, int C, const double *rn_f, const double *rn_tspan, const double *rn_phi,
+                                         const double *rn_log10_A, const double *rn_gamma, double T, const int32_t *seg, const double *dx,
+                                         const double *dxp, int M, const double *log10_hc, int64_t ld_hc, const double *s, double *b,
+                                         void *stream) {
+  PTA_REQUIRE(s && b && seg && dx && dxp && log10_hc, PTA_E_ARG, "pta_os_matched_prior_spec: NULL argument");
+  PTA_REQUIRE(R > 0 && P > 0 && K_rn >= 0 && (K_rn % 2) == 0 && C >= 2 && (C % 2) == 0 && C <= PTA_OSM_CMAX && K_rn + C <= PTA_OSM_KMAX, PTA_E_ARG,
+              "pta_os_matched_prior_spec: R=%d P=%d K_rn=%d C=%d (K_rn, C even, C <= %d, K_rn + C <= %d)", R, P, K_rn, C, PTA_OSM_CMAX,
+              PTA_OSM_KMAX);
+  PTA_REQUIRE(M >= 2 && ld_hc >= M, PTA_E_ARG, "pta_os_matched_prior_spec: M=%d (>= 2 nodes) ld_hc=%lld", M, (long long)ld_hc);
+  PTA_REQUIRE(K_rn == 0 || (rn_f && rn_tspan && rn_phi), PTA_E_ARG, "pta_os_matched_prior_spec: red-noise tables missing");
+  PTA_REQUIRE(!rn_log10_A == !rn_gamma, PTA_E_ARG, "pta_os_matched_prior_spec: amplitude and index come together");
+  PTA_REQUIRE(T > 0, PTA_E_ARG, "pta_os_matched_prior_spec: T=%g", T);
+  const int64_t total = (int64_t)R * P * (K_rn + C);
+  PTA_REQUIRE(total < (1LL << 31) * 256 && (int64_t)R * ld_hc < (1LL << 31), PTA_E_ARG, "pta_os_matched_prior_spec: problem too large");
+  hipLaunchKernelGGL(k_osm_prior_spec, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), R, P, K_rn, C, rn_f, rn_tspan, rn_phi,
+                     rn_log10_A, rn_gamma, T, seg, dx, dxp, M, log10_hc, ld_hc, s, b);
   PTA_LAUNCH_CHECK();
   return PTA_OK;
 }

@@ -31,7 +31,7 @@
 #define PTA_STREAM_ECORR 4u // + pulsar index: pair p = epoch e>>1, branch e&1                   (white_noise.py:182)
 #define PTA_STREAM_TD 5u    // + pulsar index: TD-mode z[i] of the pulsar's N_a x N_a factor, pair p = i>>1, branch i&1
 #define PTA_STREAM_TDGW 6u  // + pulsar index: TD-mode z[j] of the npts x npts GWB grid factor, pair p = j>>1, branch j&1
-#define PTA_STREAM_HYPER 7u // pulsar field 0: per-realisation hyperparameters, pair p = parameter column j, uniform u2 (pta_hyper.h)
+#define PTA_STREAM_HYPER 7u // pulsar field 0: per-realisation hyperparameters, pair p = parameter column j, uniform u2 (pta_hyper.h); field 1: spectrum nodes
 #define PTA_STREAM_CW 8u    // pulsar field 0: per-realisation CW source labels, pair p = label column j, uniform u2 (pta_cw_hyper.h)
 
 PTA_HD uint32_t pta_stream_id(uint32_t kind, uint32_t pulsar) { return (kind << 24) | (pulsar & 0xFFFFFFu); }

@@ -138,7 +138,9 @@ class OptimalStatisticMixin:
 
         theta (needs prepare_optimal_statistic(matched=True)): per-realisation noise parameters as generate(theta=...) takes them;
         row r is then weighted with the noise model of theta[r] (keys not given and NaN red-noise amplitudes: as configured / as
-        prepared; cw_* keys are ignored).  sigma is then [R, n_orf] and sigma_pair [R, n_pairs]."""
+        prepared; cw_* keys are ignored).  sigma is then [R, n_orf] and sigma_pair [R, n_pairs].  With gwb_log10_hc [R, M] (an engine
+        configured with a userSpec, the statistic prepared with the GW auto-term) the GW auto-term of row r follows its own spectrum;
+        the broadband template S(gamma) stays the prepared one."""
         st = self._os_state("optimal_statistic")
         R = self._os_check_rows(rows)
         if theta is not None:
@@ -250,19 +252,26 @@ class OptimalStatisticMixin:
     def _os_matched_theta(self, st, theta, R, what):
         """theta validated as the OS's noise model (_hyper.check_theta_os) -> contiguous float64 device tensors {rn_log10_A, rn_gamma:
         [R, P] or None (every pulsar as configured), gw_log10_A, gw_gamma: [R] or None (no GW auto-term)}; keys not given are filled
-        with the configured red noise / the prepared auto-term, pulsars configured without red noise get NaN amplitudes."""
+        with the configured red noise / the prepared auto-term, pulsars configured without red noise get NaN amplitudes.  With
+        gwb_log10_hc [R, M] (an engine configured with a userSpec; needs the GW auto-term) the GW columns of realisation r are weighted
+        with its own spectrum instead: gw_log10_hc [R, M], columns in ascending node frequency (pta_os_matched_prior_spec).  The
+        broadband template S(gamma) of the statistic stays the prepared one."""
         m = st["matched"]
         if m is None:
             raise ValueError(f"{what}: theta needs prepare_optimal_statistic(matched=True)")
-        th = _hyper.check_theta_os(theta, R, self.P, self._rn, m["gw"] is not None)
+        th = _hyper.check_theta_os(theta, R, self.P, self._rn, m["gw"] is not None, gw=self._gw)
         gpu = dv.require_gpu()
 
         def f64(x):
             if hasattr(x, "data_ptr"):
                 return x.to(device=gpu, dtype=torch.float64).contiguous()
             return dv.f64(np.ascontiguousarray(x, dtype=np.float64))
-        dev = dict.fromkeys(("rn_log10_A", "rn_gamma", "gw_log10_A", "gw_gamma"))
-        if m["gw"] is not None:
+        dev = dict.fromkeys(("rn_log10_A", "rn_gamma", "gw_log10_A", "gw_gamma", "gw_log10_hc"))
+        if _hyper.SPEC_KEY in th:
+            order, _ = _hyper.spec_nodes(self._gw["userSpec"])
+            y = f64(th[_hyper.SPEC_KEY])
+            dev["gw_log10_hc"] = y if np.array_equal(order, np.arange(len(order))) else y.index_select(1, dv.i64(order)).contiguous()
+        elif m["gw"] is not None:
             for k, key, conf in (("gw_log10_A", "gwb_log10_A", m["gw"][0]), ("gw_gamma", "gwb_gamma", m["gw"][1])):
                 dev[k] = f64(th[key]) if key in th else torch.full((R,), conf, dtype=torch.float64, device=gpu)
         if any(k in th for k in _hyper.RN_KEYS) and m["K_rn"]:
@@ -311,13 +320,31 @@ class OptimalStatisticMixin:
         def at(x, per_row):
             return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * per_row)
         hy = self._hyper_tables() if K_rn else {}
-        _lib.call("pta_os_matched_prior", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
-                  dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], at(dev["gw_log10_A"], 1),
-                  at(dev["gw_gamma"], 1), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
+        if dev["gw_log10_hc"] is not None:
+            sp = self._os_matched_spec_tables(m, C)
+            M = dev["gw_log10_hc"].shape[1]
+            _lib.call("pta_os_matched_prior_spec", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
+                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], dv.ptr(sp[0]), dv.ptr(sp[1]),
+                      dv.ptr(sp[2]), M, at(dev["gw_log10_hc"], M), M, dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
+        else:
+            _lib.call("pta_os_matched_prior", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
+                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], at(dev["gw_log10_A"], 1),
+                      at(dev["gw_gamma"], 1), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
         _lib.call("pta_os_matched_solve", dv.ptr(m["A"]), P, K, C, n, dv.ptr(ws["b"]), dv.ptr(ws["q"]), P * K, blk, dv.ptr(m["S"]), dv.ptr(m["s"]),
                   dv.ptr(ws["X"]), dv.ptr(ws["Z"]), s)
         self._os_theta_keep = dev   # the launches above read these buffers asynchronously
         return ws
+
+    def _os_matched_spec_tables(self, m, C):
+        """(seg, dx, dxp) on the device for the C / 2 frequencies k / T of the statistic against the nodes of the configured userSpec
+        (_hyper.spec_tables), built at the first use and kept with the userSpec they were built from"""
+        U = self._gw["userSpec"]
+        sp = m.get("spec")
+        if sp is None or sp[3] is not U:
+            _, xp = _hyper.spec_nodes(U)
+            seg, dx, dxp = _hyper.spec_tables(np.arange(1, C // 2 + 1) / m["T"], xp)
+            sp = m["spec"] = (dv.i32(seg), dv.f64(dx), dv.f64(dxp), U)
+        return sp
 
     def _os_matched_launch(self, rows, n, dev, lo, out):
         """_os_matched_front, then pta_os_matched_pairs into rows lo .. of out"""

@@ -456,12 +456,16 @@ def rn_prior(f, tspan, log10_A, gamma):
 
 
 def matched_prior(R, s, rn_f=None, rn_tspan=None, rn_phi=None, rn_log10_A=None, rn_gamma=None, nf=0, T=1.0, gw_log10_A=None,
-                  gw_gamma=None):
-    """b [R, P, K]: prior variances over s of every (realisation, pulsar, column) - the NumPy form of pta_os_matched_prior.
+                  gw_gamma=None, gw_log10_hc=None, gw_nodes=None):
+    """b [R, P, K]: prior variances over s of every (realisation, pulsar, column) - the NumPy form of pta_os_matched_prior and, with
+    gw_log10_hc, of pta_os_matched_prior_spec.
 
     s [P]; rn_f [P, K_rn / 2], rn_tspan [P], rn_phi [P, K_rn] the configured prior variances (or all None: K_rn = 0); rn_log10_A,
     rn_gamma [R, P] (None = every pulsar as configured; NaN amplitude = that pulsar as configured); nf, T: the OS frequencies
-    (k + 1) / T; gw_log10_A, gw_gamma [R] (None = no GW auto-term: those columns are 0)."""
+    (k + 1) / T; gw_log10_A, gw_gamma [R] (None = no GW auto-term: those columns are 0).  gw_log10_hc [R, M] with gw_nodes [M] (in
+    place of gw_log10_A / gw_gamma): a spectrum per realisation, log10 hc at the node frequencies gw_nodes [Hz] in the order given
+    (sorted here as red_noise.gwb_spectrum_hcf sorts a userSpec), interpolated with the userSpec semantics; the GW columns are
+    hc(f)^2 / (12 pi^2 f^3 T) / s."""
     s = np.asarray(s, dtype=np.float64)
     P = len(s)
     K_rn = 0 if rn_phi is None else np.shape(rn_phi)[1]
@@ -480,6 +484,16 @@ def matched_prior(R, s, rn_f=None, rn_tspan=None, rn_phi=None, rn_log10_A=None, 
         f = np.repeat(np.arange(1, nf + 1) / float(T), 2)[None, :]
         fyr = 1.0 / YEAR_IN_SEC
         phi = 10.0 ** (2.0 * lA) * (fyr ** (g - 3.0) * f ** (-g) / (12 * np.pi ** 2 * T))
+        b[:, :, K_rn:] = phi[:, None, :] / s[None, :, None]
+    if gw_log10_hc is not None:
+        if gw_log10_A is not None or gw_nodes is None:
+            raise ValueError("matched_prior: gw_log10_hc comes with gw_nodes, in place of gw_log10_A / gw_gamma")
+        from . import _hyper
+        nodes = np.asarray(gw_nodes, dtype=np.float64)
+        order, xp = _hyper.spec_nodes(np.stack([nodes, np.ones_like(nodes)], axis=1))
+        f = np.arange(1, nf + 1) / float(T)
+        hc = _hyper.spec_eval(_hyper.spec_tables(f, xp), np.asarray(gw_log10_hc, dtype=np.float64)[:, order])
+        phi = np.repeat(hc ** 2 / (12 * np.pi ** 2 * f ** 3 * T), 2, axis=1)
         b[:, :, K_rn:] = phi[:, None, :] / s[None, :, None]
     return b
 
