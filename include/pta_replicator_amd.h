@@ -388,15 +388,13 @@ typedef struct {
   int32_t rng_fast;           /* Gaussian transform of the on-chip draws (see "RNG" above); 0 = fp64 (default) */
   int32_t synth_variant;      /* fused-kernel variant: 0 (default) = red-noise F @ y on the matrix cores (16 realisations x 256 TOAs
                                  per workgroup), workgroups dealt to the XCDs in contiguous (tile, realisation-group) ranges; 1 = same
-                                 kernel in plain linear workgroup order (A/B); 2 = same as 0 with the red-noise loop's per-lane 64-bit
-                                 index products instead of scalar row offsets (A/B, bit-identical); 4 / 6 / 8 = all-VALU kernel compiled for that many
-                                 waves per SIMD (kept for cross-checks); 16 + pf + 8 w3 + 16 noidx + 32 generic (16 .. 79) = the
-                                 kernel of 0 with its memory operands requested a phase ahead (pf: 2 = the red-noise rotation's first two K-steps
-                                 before the ECORR staging; 4 / 5 = the epilogue's GWB / all operands one step ahead, 6 / 7 = with 2;
-                                 0 = none - what 0 runs: the pipelining measured no gain), w3 = compiled for 3 workgroups per CU (4 .. 7 exist there only),
-                                 noidx = with the index products of 2, generic = never the copy compiled for a plan with GWB, white noise and
-                                 ECORR all present (48 = pf 0, generic: the kernel before any of this); all bit-identical (A/B); 100 + k (k <= 64) = the default kernel with k KB of unused
-                                 dynamic LDS per workgroup (occupancy probe of round 3: profiles/r03_bench_final.json, DESIGN.md §4.1 "measured and not kept") */
+                                 kernel in plain linear workgroup order (A/B); 2 = the red-noise loop's per-lane 64-bit index products
+                                 instead of scalar row offsets, and never the copy compiled for a plan with GWB, white noise and ECORR
+                                 all present (A/B); 6 = all-VALU kernel (kept for cross-checks); 16 + 16 noidx + 32 generic (16, 32, 48,
+                                 64) = test hook for the four copies of the kernel: noidx = with the index products of 2, generic =
+                                 without the complete-plan copy of 0; all of these bit-identical; 100 + k (k <= 64) =
+                                 the default kernel with k KB of unused dynamic LDS per workgroup (occupancy probe of round 3:
+                                 profiles/r03_bench_final.json, DESIGN.md §4.1 "measured and not kept"); any other value is refused */
 } pta_engine_plan;
 
 /* coef[(r*P + a)*K + c] = amp[a*K + c] * z(seed, r0+r, (RN,a), c)   (red_noise.py:126-127)   */

@@ -154,31 +154,15 @@ typedef double pta_f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 // RNIDX (red-noise loop addressing): true = a wave-uniform row offset from the scalar unit added to per-lane 32-bit byte offsets that are
 // computed once (the host guards their range); false = the per-lane 64-bit index product per load (synth_variant 2, and any plan
 // beyond the 32-bit range).  Same loads' values, same MFMA sequence: the two are bit-identical.
-//
-// PF (memory-operand pipelining; results are those of PF = 0 bit for bit - loads and stores change place, nothing else does):
-//   bit 2 = the epilogue's GWB operands (the four 16-byte gw_G brackets, which miss L2, and gw_w) one step ahead: those of step j + 1
-//           are requested before the Box-Muller chains of step j (step 0's before the ECORR staging), so that the wait in front of
-//           their first use is counted (vmcnt(N), N = the loads and stores issued since) instead of a full round trip with nothing
-//           of the wave to issue;
-//   bit 0 = the same for the L2-resident per-TOA operands (wn_a, wn_b, idx_in_psr, ecorr_toa, epoch_of, det), with bit 2 only: the
-//           vmcnt is in order, so per-TOA operands of step j requested behind the brackets of step j + 1 would wait for those too
-//           (4 alone requests them in front);
-//   bit 1 = the first two K-steps' operands of the red-noise rotation requested before the ECORR staging loop and its barrier.
-// WPC = workgroups per CU the register budget is compiled for (4: 128 VGPRs, 3: 168).
 // ALL = the plan has GWB, white noise and ECORR, known at compile time (the host looks): the waits the compiler places are exact only
 // over straight-line code - where a request sits in a branch (`if (has_gw)`), every value requested before that branch is waited for
 // as if the branch's requests had not been issued, i.e. together with them.  Every kernel therefore exists a second time for the plan
 // in which every group of operands is there (its straight-line epilogue also lets the compiler compute the GWB row addresses once
-// instead of per step: 4 % fewer VALU instructions per launch - the one piece of all this that measured faster); PF = 0, ALL = false is the kernel as it was.
-struct pta_synth_ops {  // the per-TOA operands of one epilogue step
-  pta_f64x2_a8 y[4];
-  double wgt, wa, wb, ec, det;
-  uint32_t pair;
-  int e, i;
-};
-template <bool FAST, bool SINGLE, bool RNIDX, int PF, int WPC, bool ALL>
-__global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_engine_plan pl, uint64_t seed, uint64_t r0, int R,
-                                                                           double *__restrict__ out, int64_t ld_out, int xcd_aware) {
+// instead of per step: 4 % fewer VALU instructions per launch); ALL = false is the kernel as it was.
+// (Measured, not kept - DESIGN.md §4.1: the memory operands requested one phase ahead, and the two-deviate kernel at 3 workgroups per CU.)
+template <bool FAST, bool SINGLE, bool RNIDX, bool ALL>
+__global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synth_mfma(pta_engine_plan pl, uint64_t seed, uint64_t r0, int R,
+                                                                                     double *__restrict__ out, int64_t ld_out, int xcd_aware) {
   constexpr int fast = FAST ? 1 : 0;  // template parameters: the RNG-math modes and the single-deviate white noise are separate kernels
                                       // (and profile rows) - folded into one, the extra live values spill the default path
   __shared__ double zec[ENG_MR][ENG_ZPITCH];
@@ -207,20 +191,17 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
   const int count = pl.tile_count[tile];
   const int epn = has_ec ? pl.tile_epn[tile] : 0;
   const int ep0 = has_ec ? pl.tile_ep0[tile] : 0;
-  auto stage = [&]() {  // the tile's ECORR deviates -> LDS
-    if (epn > 0) {
-      const uint32_t strm = pta_stream_id(PTA_STREAM_ECORR, (uint32_t)a);
-      for (int idx = t; idx < epn * ENG_MR; idx += PTA_ENGINE_TILE) {
-        int q = idx / epn, p = idx - q * epn;
-        double z0, z1;
-        pta_normal_pair(seed, r0 + (uint64_t)(rb + q), strm, (uint32_t)(ep0 + p), z0, z1, fast);
-        zec[q][2 * p] = z0;
-        zec[q][2 * p + 1] = z1;
-      }
-      __syncthreads();
+  if (epn > 0) {  // the tile's ECORR deviates -> LDS
+    const uint32_t strm = pta_stream_id(PTA_STREAM_ECORR, (uint32_t)a);
+    for (int idx = t; idx < epn * ENG_MR; idx += PTA_ENGINE_TILE) {
+      int q = idx / epn, p = idx - q * epn;
+      double z0, z1;
+      pta_normal_pair(seed, r0 + (uint64_t)(rb + q), strm, (uint32_t)(ep0 + p), z0, z1, fast);
+      zec[q][2 * p] = z0;
+      zec[q][2 * p + 1] = z1;
     }
-  };
-  if (PF == 0) stage();
+    __syncthreads();
+  }
   // No predicated stores anywhere below: a lane beyond the tile's count works on the tile's LAST TOA and a realisation row beyond
   // R on realisation R - 1 - same counters, same operands, bit-identical value - and stores it again to the same address.  (Stores
   // count in vmcnt on gfx950 and a predicated store is its own exec-masked block: behind a pending load the compiler waits
@@ -235,37 +216,6 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = pta_f64x4{0.0, 0.0, 0.0, 0.0};
   const bool has_gw = ALL || pl.gw_npts > 0, has_wn = ALL || pl.wn_a != nullptr || wn_single;
-  // every per-TOA operand of epilogue step j: all requested together - a load issued between the Box-Muller chains is waited for on
-  // the spot
-  auto ldgw = [&](int j, pta_synth_ops &o) {
-    const int i = start + min(tbase + 16 * j, count - 1);
-    o.wgt = has_gw ? pl.gw_w[i] : 0.0;
-    if (has_gw) {  // GWB: both bracket samples of the mixed grid series in one 16-byte load (red_noise.py:286-287)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        o.y[g] = *reinterpret_cast<const pta_f64x2_a8 *>(pl.gw_G + ((int64_t)(rb + rq[g]) * P + a) * pl.gw_npts + jl4[j]);
-    }
-  };
-  auto ldtoa = [&](int j, pta_synth_ops &o) {
-    const int i = start + min(tbase + 16 * j, count - 1);
-    o.i = i;
-    o.wa = has_wn ? (wn_single ? pl.wn_c[i] : pl.wn_a[i]) : 0.0;
-    o.wb = (has_wn && !wn_single) ? pl.wn_b[i] : 0.0;
-    o.pair = (uint32_t)pl.idx_in_psr[i];
-    o.ec = has_ec ? pl.ecorr_toa[i] : 0.0;
-    o.e = has_ec ? pl.epoch_of[i] : 0;
-    o.det = pl.det ? pl.det[i] : 0.0;
-  };
-  pta_synth_ops cur;
-  // PF: what goes between the requests of the rotation's first two K-steps and its loop (PF & 2), or in front of the red-noise block
-  // (otherwise) - step 0's epilogue operands (gw_G misses L2: requested behind the rotation's L2-resident ones, so that only the third
-  // K-step waits for them too), then the ~900 VALU instructions of the staging to cover both
-  auto mid = [&]() {
-    if (PF & 4) ldgw(0, cur);
-    if (PF & 1) ldtoa(0, cur);
-    stage();
-  };
-  if (PF != 0 && !(PF & 2)) mid();
   if (pl.rn_k > 0) {
     const int K = pl.rn_k;
     const int ra = min(rb + col, R - 1);
@@ -297,7 +247,6 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
       double a0, a1, a2, b0[4], b1[4], b2[4];
       ldx(0, a0, b0);
       ldx(4, a1, b1);
-      if (PF & 2) mid();
       for (int k0 = 0; k0 < K; k0 += 12) {
         ldx(k0 + 8, a2, b2);
         mm(a0, b0);
@@ -349,8 +298,6 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
     } else {
       run(ld);
     }
-  } else if (PF & 2) {
-    mid();
   }
   const uint32_t strm_wn = pta_stream_id(PTA_STREAM_WN, (uint32_t)a);
   const uint32_t strm_ec = pta_stream_id(PTA_STREAM_ECORR, (uint32_t)a);
@@ -366,39 +313,21 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
   int pend_i = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    // PF & 4: the operands of step j + 1 now, in front of the pending stores of step j - 1 and the chains of step j - the wait for
-    // step j's own (requested a step ago) leaves these loads and the stores in flight
-    pta_synth_ops nxt;
-    if (PF & 4) {
-      if (!(PF & 1)) ldtoa(j, cur);
-      if (j < 3) {
-        ldgw(j + 1, nxt);
-        if (PF & 1) ldtoa(j + 1, nxt);
-      }
-    }
-    double wgt, wa, wb, ec, det;
-    uint32_t pair;
-    int e, i;
+    // every per-TOA operand of this j: all requested together, up front - a load issued between the Box-Muller chains is waited for
+    // on the spot
+    const int i = start + min(tbase + 16 * j, count - 1);
+    const double wgt = has_gw ? pl.gw_w[i] : 0.0;
     pta_f64x2_a8 y[4];
-    if (PF & 4) {
-      wgt = cur.wgt, wa = cur.wa, wb = cur.wb, ec = cur.ec, det = cur.det, pair = cur.pair, e = cur.e, i = cur.i;
+    if (has_gw) {  // GWB: both bracket samples of the mixed grid series in one 16-byte load (red_noise.py:286-287)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) y[g] = cur.y[g];
-    } else {
-      // every per-TOA operand of this j is requested up front and waited for on the spot
-      i = start + min(tbase + 16 * j, count - 1);
-      wgt = has_gw ? pl.gw_w[i] : 0.0;
-      if (has_gw) {  // GWB: both bracket samples of the mixed grid series in one 16-byte load (red_noise.py:286-287)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          y[g] = *reinterpret_cast<const pta_f64x2_a8 *>(pl.gw_G + ((int64_t)(rb + rq[g]) * P + a) * pl.gw_npts + jl4[j]);
-      }
-      wa = has_wn ? (wn_single ? pl.wn_c[i] : pl.wn_a[i]) : 0.0, wb = (has_wn && !wn_single) ? pl.wn_b[i] : 0.0;
-      pair = (uint32_t)pl.idx_in_psr[i];
-      ec = has_ec ? pl.ecorr_toa[i] : 0.0;
-      e = has_ec ? pl.epoch_of[i] : 0;
-      det = pl.det ? pl.det[i] : 0.0;
+      for (int g = 0; g < 4; ++g)
+        y[g] = *reinterpret_cast<const pta_f64x2_a8 *>(pl.gw_G + ((int64_t)(rb + rq[g]) * P + a) * pl.gw_npts + jl4[j]);
     }
+    const double wa = has_wn ? (wn_single ? pl.wn_c[i] : pl.wn_a[i]) : 0.0, wb = (has_wn && !wn_single) ? pl.wn_b[i] : 0.0;
+    const uint32_t pair = (uint32_t)pl.idx_in_psr[i];
+    const double ec = has_ec ? pl.ecorr_toa[i] : 0.0;
+    const int e = has_ec ? pl.epoch_of[i] : 0;
+    const double det = pl.det ? pl.det[i] : 0.0;
     if (j > 0) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) out[(int64_t)(rb + rq[g]) * ld_out + pend_i] = pend[g];
@@ -456,43 +385,22 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, WPC) void k_engine_synth_mfma(pta_
 #pragma unroll
     for (int g = 0; g < 4; ++g) pend[g] = v[g] + det;
     pend_i = i;
-    if ((PF & 4) && j < 3) {
-      cur.wgt = nxt.wgt;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) cur.y[g] = nxt.y[g];
-      if (PF & 1) cur = nxt;
-    }
   }
 #pragma unroll
   for (int g = 0; g < 4; ++g) out[(int64_t)(rb + rq[g]) * ld_out + pend_i] = pend[g];
 }
 
-// the instance of k_engine_synth_mfma for a launch (the single-deviate white noise exists at 3 workgroups per CU only)
+// the instance of k_engine_synth_mfma for a launch
 typedef void (*pta_synth_fn)(pta_engine_plan, uint64_t, uint64_t, int, double *, int64_t, int);
-// Instances: 4 workgroups per CU with PF 0 / 2 only (epilogue operands ahead do not fit 128 VGPRs without scratch); the single-deviate
-// white noise at 3 per CU only, and there without the per-TOA operands ahead (scratch at 168).  nullptr = no such instance.
-template <bool FAST, bool SINGLE, bool RNIDX, int WPC, bool ALL>
-static pta_synth_fn synth_kernel_pf(int pf) {
-  if (pf == 0) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 0, WPC, ALL>;
-  if (pf == 2) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 2, WPC, ALL>;
-  if constexpr (WPC == 3) {
-    if (pf == 4) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 4, WPC, ALL>;
-    if (pf == 6) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 6, WPC, ALL>;
-    if constexpr (!SINGLE) {
-      if (pf == 5) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 5, WPC, ALL>;
-      if (pf == 7) return k_engine_synth_mfma<FAST, SINGLE, RNIDX, 7, WPC, ALL>;
-    }
-  }
-  return nullptr;
+static pta_synth_fn synth_kernel(bool rng_fast, bool single, bool rnidx, bool all) {
+#define PTA_SYNTH_COPIES(F, S)                                                                     \
+  {{k_engine_synth_mfma<F, S, false, false>, k_engine_synth_mfma<F, S, false, true>},             \
+   {k_engine_synth_mfma<F, S, true, false>, k_engine_synth_mfma<F, S, true, true>}}
+  static const pta_synth_fn kern[2][2][2][2] = {{PTA_SYNTH_COPIES(false, false), PTA_SYNTH_COPIES(false, true)},
+                                                {PTA_SYNTH_COPIES(true, false), PTA_SYNTH_COPIES(true, true)}};
+#undef PTA_SYNTH_COPIES
+  return kern[rng_fast][single][rnidx][all];
 }
-template <bool RNIDX, bool ALL>
-static pta_synth_fn synth_kernel(int rng_fast, bool single, int pf, bool w3) {
-  if (single) return rng_fast ? synth_kernel_pf<true, true, RNIDX, 3, ALL>(pf) : synth_kernel_pf<false, true, RNIDX, 3, ALL>(pf);
-  if (w3) return rng_fast ? synth_kernel_pf<true, false, RNIDX, 3, ALL>(pf) : synth_kernel_pf<false, false, RNIDX, 3, ALL>(pf);
-  return rng_fast ? synth_kernel_pf<true, false, RNIDX, 4, ALL>(pf) : synth_kernel_pf<false, false, RNIDX, 4, ALL>(pf);
-}
-#define PTA_SYNTH_DEFAULT_PF 0   // synth_variant 0: the pipelining and the register budget that measured fastest
-#define PTA_SYNTH_DEFAULT_WPC 4
 
 extern "C" int pta_engine_synth(const pta_engine_plan *plan_host, uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out,
                                 void *stream) {
@@ -508,57 +416,43 @@ extern "C" int pta_engine_synth(const pta_engine_plan *plan_host, uint64_t seed,
   PTA_REQUIRE(!p.wn_a || p.wn_b, PTA_E_ARG, "pta_engine_synth: wn_b missing");
   PTA_REQUIRE(!p.wn_c || !p.wn_a, PTA_E_ARG, "pta_engine_synth: wn_c (single-deviate white noise) replaces wn_a / wn_b - pass one or the other");
   PTA_REQUIRE(!p.ecorr_toa || p.epoch_of, PTA_E_ARG, "pta_engine_synth: epoch_of missing");
-  // 0 = MFMA kernel (default); 1 = same, linear workgroup order; 4 / 6 / 8 = all-VALU kernel; 100 + k = MFMA kernel with k KB of
-  // unused dynamic LDS per workgroup - the occupancy probe of round 3 (script since removed; result in DESIGN.md §4.1): the 34 KB ECORR staging buffer allows 4
-  // workgroups per CU (+12 KB: 3, +20 KB: 2).  Measured step time 10.3 / 7.2 / 5.9 / 5.5 ms at 1 / 2 / 3 / 4 workgroups; a two-pass
-  // staging variant (17 KB, 6 per CU, 3 barriers) measured 6.0 ms at 6 AND when padded back to 4: occupancy is saturated at 4.
+  // synth_variant: 0 = MFMA kernel (default: the copy for complete plans where the plan is complete, scalar row offsets in the red-noise
+  // loop where their 32-bit range allows); 1 = same, linear workgroup order (A/B of the XCD mapping); 2 = the kernel as it was: per-lane
+  // 64-bit index products in the red-noise loop (A/B of its addressing) and the copy for any plan; 6 = all-VALU kernel; 100 + k = MFMA
+  // kernel with k KB of unused dynamic LDS per workgroup - the occupancy probe of round 3 (script since removed; result in DESIGN.md
+  // §4.1): the 34 KB ECORR staging buffer allows 4 workgroups per CU (+12 KB: 3, +20 KB: 2).  Measured step time 10.3 / 7.2 / 5.9 /
+  // 5.5 ms at 1 / 2 / 3 / 4 workgroups; a two-pass staging variant (17 KB, 6 per CU, 3 barriers) measured 6.0 ms at 6 AND when padded
+  // back to 4: occupancy is saturated at 4.
+  // 16 + 16 noidx + 32 generic (16, 32, 48, 64) = test hook for the four (RNIDX, ALL) copies at a small shape: the per-lane index
+  // products of variant 2 if noidx, the copy for any plan (ALL = false) also where the plan is complete if generic.  Every other
+  // value is refused.
   const int variant = p.synth_variant;
-  const int rng_fast = p.rng_fast ? 1 : 0;
-  // 0 = MFMA kernel (default); 1 = same, linear workgroup order (A/B of the XCD mapping); 2 = same as 0 with the red-noise loop's
-  // per-lane 64-bit index products (A/B of its addressing); 4 / 6 / 8 = all-VALU kernel; 100 + k = MFMA
-  // kernel with k KB of unused dynamic LDS per workgroup - the occupancy probe of round 3 (script since removed; result in DESIGN.md §4.1): the 34 KB ECORR
-  // staging buffer allows 4 workgroups per CU (+12 KB: 3, +20 KB: 2)
-  // 16 + pf + 8 w3 + 16 noidx + 32 generic (16 .. 79) = the MFMA kernel with memory-operand pipelining pf (template parameter PF: 4 = the epilogue's
-  // GWB operands one step ahead, 5 = all of its operands, 2 = rotation prologue before the ECORR staging, 6 / 7 = 4 / 5 with 2),
-  // compiled for 3 workgroups per CU if w3, with the per-lane index products of variant 2 if noidx, the copy for any plan (ALL = false)
-  // also where the plan is complete if generic.  48 (pf 0, generic) is the kernel as it was before all this; 0 is 16 + what measured fastest
-  // (PTA_SYNTH_DEFAULT_*: no pipelining, 4 per CU - the copy for complete plans is the gain)
-  const bool pipe = variant >= 16 && variant <= 79;
-  PTA_REQUIRE(!pipe || (((variant - 16) & 7) != 1 && ((variant - 16) & 7) != 3), PTA_E_ARG,
-              "pta_engine_synth: synth_variant %d - per-TOA operands ahead (bit 0) exist with the GWB operands ahead (bit 2) only", variant);
-  if (variant == 0 || variant == 1 || variant == 2 || pipe || (variant >= 100 && variant <= 164)) {
+  const bool copies = variant == 16 || variant == 32 || variant == 48 || variant == 64;
+  PTA_REQUIRE(variant == 0 || variant == 1 || variant == 2 || variant == 6 || copies || (variant >= 100 && variant <= 164), PTA_E_ARG,
+              "pta_engine_synth: synth_variant %d does not exist (0, 1, 2, 6, 16, 32, 48, 64, 100 .. 164)", variant);
+  if (variant != 6) {
     const int xcd = variant == 1 ? 0 : 1;
     const unsigned pad = variant >= 100 ? (unsigned)(variant - 100) * 1024u : 0u;
     const int64_t total = (int64_t)pta_cdiv(R, ENG_MR) * p.n_tiles, nwg = ((total + 7) >> 3) << 3;
     PTA_REQUIRE(nwg < (1LL << 31), PTA_E_ARG, "pta_engine_synth: %lld workgroups exceed one launch", (long long)nwg);
     // the 32-bit lane offsets of the red-noise loop: up to ((K - 1) ldf + 255) 8 from a tile's first design-matrix entry, R P K 8
     // into the coefficients
-    const bool noidx = variant == 2 || (pipe && ((variant - 16) & 16));
+    const bool noidx = variant == 2 || (copies && ((variant - 16) & 16));
     const bool rnidx = !noidx && p.rn_k > 0 && p.ldf < (1LL << 28) && ((int64_t)p.rn_k * p.ldf + PTA_ENGINE_TILE) * 8 < (1LL << 32) &&
                        (int64_t)R * p.n_psr * p.rn_k * 8 < (1LL << 32);
-    // variant 2 stays round 12's loop in the kernel as it was (no pipelining); 1 and 100 + k are A/Bs of the default kernel
-    const int pf = pipe ? (variant - 16) & 7 : variant == 2 ? 0 : PTA_SYNTH_DEFAULT_PF;
-    const bool w3 = p.wn_c || (pipe ? ((variant - 16) & 8) != 0 : variant == 2 ? false : PTA_SYNTH_DEFAULT_WPC == 3);
-    const bool all = !(pipe && ((variant - 16) & 32)) && variant != 2 && p.gw_npts > 0 && (p.wn_a || p.wn_c) && p.ecorr_toa;
-    pta_synth_fn kern = all ? (rnidx ? synth_kernel<true, true>(rng_fast, p.wn_c != nullptr, pf, w3) : synth_kernel<false, true>(rng_fast, p.wn_c != nullptr, pf, w3))
-                            : (rnidx ? synth_kernel<true, false>(rng_fast, p.wn_c != nullptr, pf, w3) : synth_kernel<false, false>(rng_fast, p.wn_c != nullptr, pf, w3));
-    PTA_REQUIRE(kern, PTA_E_ARG, "pta_engine_synth: synth_variant %d - no kernel with pipelining %d at %d workgroups per CU%s (scratch)", variant, pf,
-                w3 ? 3 : 4, p.wn_c ? ", single-deviate white noise" : "");
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(PTA_ENGINE_TILE), pad, pta_stream(stream), p, seed, r0, R, out, ld_out, xcd);
+    const bool generic = variant == 2 || (copies && ((variant - 16) & 32));
+    const bool all = !generic && p.gw_npts > 0 && (p.wn_a || p.wn_c) && p.ecorr_toa;
+    hipLaunchKernelGGL(synth_kernel(p.rng_fast != 0, p.wn_c != nullptr, rnidx, all), dim3((unsigned)nwg), dim3(PTA_ENGINE_TILE), pad,
+                       pta_stream(stream), p, seed, r0, R, out, ld_out, xcd);
     PTA_LAUNCH_CHECK();
     return PTA_OK;
   }
   PTA_REQUIRE(!p.wn_c, PTA_E_ARG, "pta_engine_synth: the single-deviate white noise exists in the MFMA kernel only");
   PTA_REQUIRE(p.n_tiles <= 65535, PTA_E_ARG, "pta_engine_synth: %d tiles exceed the 2-D launch of the all-VALU kernel", p.n_tiles);
-  dim3 g(pta_cdiv(R, ENG_RB), p.n_tiles), b(PTA_ENGINE_TILE);
-  // register budget per lane (waves per SIMD the compiler must allow): the kernel alternates long Box-Muller chains
+  // register budget per lane (6 waves per SIMD the compiler must allow): the kernel alternates long Box-Muller chains
   // with a load-fed FMA loop, so occupancy matters more than keeping all eight chains' temporaries in registers
-  if (variant >= 8)
-    hipLaunchKernelGGL(k_engine_synth<8>, g, b, 0, pta_stream(stream), p, seed, r0, R, out, ld_out, rng_fast);
-  else if (variant >= 6)
-    hipLaunchKernelGGL(k_engine_synth<6>, g, b, 0, pta_stream(stream), p, seed, r0, R, out, ld_out, rng_fast);
-  else
-    hipLaunchKernelGGL(k_engine_synth<4>, g, b, 0, pta_stream(stream), p, seed, r0, R, out, ld_out, rng_fast);
+  hipLaunchKernelGGL(k_engine_synth<6>, dim3(pta_cdiv(R, ENG_RB), p.n_tiles), dim3(PTA_ENGINE_TILE), 0, pta_stream(stream), p, seed, r0, R,
+                     out, ld_out, p.rng_fast ? 1 : 0);
   PTA_LAUNCH_CHECK();
   return PTA_OK;
 }

@@ -13,18 +13,11 @@ element of k_engine_synth_mfma<false> go.  No GPU needed: hipcc --save-temps for
     the twiddle and butterfly pieces those bits remove compiled on their own like the pieces of the draw.
 
 Writes profiles/r13_isa_instruction_classes.txt (r03_isa_instruction_classes.txt is the table of the kernel as it was in round 3).  The PMC
-figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of profiles/r06_pmc.json.
-
-    python scripts/isa_instruction_table.py --synth-prefetch
-
-writes profiles/r16_isa_synth_prefetch.txt instead: the memory schedule of every pipelined instance of k_engine_synth_mfma (template
-parameters PF, WPC, ALL) - VGPRs, scratch, and the order of requests, stores and s_waitcnt vmcnt(N) around the rotation and through
-the four epilogue steps, with the VALU instructions between them."""
+figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of profiles/r06_pmc.json."""
 import collections
 import os
 import re
 import subprocess
-import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,97 +114,7 @@ def blocks(lines):
     return out
 
 
-def resources(asm_text, kn):
-    m = asm_text[asm_text.index(".amdhsa_kernel " + kn):]
-    return [int(re.search(k + r"\s+(\d+)", m).group(1)) for k in ("amdhsa_next_free_vgpr", "amdhsa_private_segment_fixed_size")]
-
-
-def memory_schedule(lines):
-    """the kernel's text in order as tokens: ("L" | "S", n) runs of vector-memory loads / stores, ("W", N) s_waitcnt vmcnt(N), ("V", n) VALU
-    instructions in between, ("M", n) MFMAs, ("B", 0) s_barrier, ("loop", 0) a backward branch"""
-    toks, seen = [], set()
-
-    def push(k, n):
-        if toks and toks[-1][0] == k and k in "LSVM":
-            toks[-1][1] += n
-        else:
-            toks.append([k, n])
-    for ln in lines:
-        t = ln.split(";")[0].strip()
-        m = re.match(r"^(\.LBB\w+):", t)
-        if m:
-            seen.add(m.group(1)); continue
-        if not t or t.startswith("."): continue
-        op = t.split()[0]
-        if op.startswith("v_mfma"): push("M", 1)
-        elif op.startswith("v_"): push("V", 1)
-        elif op.startswith(("global_load", "buffer_load", "flat_load", "scratch_load")): push("L", 1)
-        elif op.startswith(("global_store", "buffer_store", "flat_store", "scratch_store")): push("S", 1)
-        elif op == "s_barrier": push("B", 0)
-        elif op == "s_waitcnt":
-            w = re.search(r"vmcnt\((\d+)\)", t)
-            if w: push("W", int(w.group(1)))
-        elif op.startswith("s_cbranch") and t.split()[-1] in seen: push("loop", 0)
-    return toks
-
-
-def show(toks, vmin=40):
-    out = []
-    for k, n in toks:
-        if k == "V":
-            if n >= vmin: out.append(f"v{n}")
-        elif k == "W": out.append(f"W({n})")
-        elif k in ("B", "loop"): out.append("barrier" if k == "B" else "<-loop")
-        else: out.append(f"{k}{n}")
-    return " ".join(out)
-
-
-def synth_prefetch():
-    """profiles/r16_isa_synth_prefetch.txt"""
-    rep = ["k_engine_synth_mfma<FAST = false, SINGLE, RNIDX, PF, WPC, ALL>: the memory schedule the compiler made of each instance (gfx950, the staged-ECORR",
-           "path: -DPTA_ISA_TABLE_MAIN_PATH_ONLY).  PF: 4 = the epilogue's GWB operands one step ahead, 5 = all of its operands, 2 = the rotation's first",
-           "two K-steps requested before the ECORR staging, 6 / 7 = 4 / 5 with 2; WPC = workgroups per CU compiled for; ALL = the copy for a plan with GWB,",
-           "white noise and ECORR (no request inside a branch).  Tokens in program order: Ln / Sn = n vector-memory loads / stores, W(N) = s_waitcnt",
-           "vmcnt(N), vN = N VALU instructions (runs under 40 left out), Mn = n MFMAs, barrier, <-loop = backward branch.  The ECORR staging loop is the",
-           "loop without MFMAs, the rotation the loop(s) with them (RNIDX = true holds two copies: K % 4 == 0 and the tail clamp); the epilogue is what follows",
-           "the last MFMA: four Box-Muller runs of ~400 VALU, each behind the wait for its own operands.  'waits in front of the four chains' = the last",
-           "vmcnt wait before each VALU run of 300 or more.  VGPR = next free VGPR of this build (the library's own, with the per-TOA ECORR path, needs a",
-           "few more: 123 for PF 0 / 2, 144 / 154 for PF 4 / 5 in the ALL copies; scratch 0 in all of them).", ""]
-    with tempfile.TemporaryDirectory() as d:
-        subprocess.check_call([HIPCC] + FLAGS + ["-DPTA_ISA_TABLE_MAIN_PATH_ONLY", os.path.join(CSRC, "pta_engine_kernels.hip"), "-o", os.path.join(d, "eng.o")],
-                              cwd=d, stderr=subprocess.DEVNULL)
-        asm = os.path.join(d, "pta_engine_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
-        kb, text = kernel_bodies(asm), open(asm).read()
-        pat = re.compile(r"^_Z19k_engine_synth_mfmaILb0ELb([01])ELb([01])ELi(\d)ELi(\d)ELb([01])E")
-        rows = sorted((tuple(int(x) for x in pat.match(k).groups()), k) for k in kb if pat.match(k))
-        rep.append(f"{'SINGLE RNIDX PF WPC ALL':24s} {'VGPR':>5s} {'scratch':>8s} {'vmcnt(0) in epilogue':>21s}   waits in front of the four chains")
-        detail = []
-        for (single, rnidx, pf, wpc, al), k in rows:
-            vg, scr = resources(text, k)
-            toks = memory_schedule(kb[k])
-            last_m = max(i for i, t in enumerate(toks) if t[0] == "M")
-            epi = toks[last_m + 1:]
-            zero = sum(1 for t in epi if t[0] == "W" and t[1] == 0)
-            # the wait that precedes each long VALU run of the epilogue (the last W token before it)
-            fronts, lastw = [], None
-            for t in epi:
-                if t[0] == "W": lastw = t[1]
-                elif t[0] == "V" and t[1] >= 300: fronts.append(lastw); lastw = None
-            rep.append(f"{single:6d} {rnidx:5d} {pf:2d} {wpc:3d} {al:3d}      {vg:5d} {scr:8d} {zero:21d}   {fronts}")
-            if not single and rnidx:
-                first_m = min(i for i, t in enumerate(toks) if t[0] == "M")
-                detail.append(f"PF {pf} WPC {wpc} ALL {al}")
-                detail.append("  up to the first MFMA: " + show(toks[:first_m + 1]))
-                detail.append("  epilogue:             " + show(epi))
-        rep += ["", "SINGLE = false, RNIDX = true (the headline's kernels) in full:"] + detail
-    path = os.path.join(ROOT, "profiles", "r16_isa_synth_prefetch.txt")
-    open(path, "w").write("\n".join(rep) + "\n")
-    print("\n".join(rep))
-
-
 def main():
-    if "--synth-prefetch" in sys.argv:
-        return synth_prefetch()
     rep = []
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "probe.hip")
@@ -253,10 +156,10 @@ def main():
             return f"integer multiplies {mul}, other 64-bit integer {w64}: " + ", ".join(f"{op} {n}" for op, n in vops.most_common(8))
 
         # the red-noise loop with the per-lane 64-bit index products (RNIDX = false: synth_variant 2, the kernel before the change) ...
-        old_rows = kernel_rows(next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb0ELi0ELi4ELb0E")), "k_engine_synth_mfma<false, false, false>")
+        old_rows = kernel_rows(next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb0ELb0E")), "k_engine_synth_mfma<false, false, false>")
         old_rn = [r for r in old_rows if r[2] and r[1]["mfma"] > 0]
         # ... and with scalar row offsets (RNIDX = true, default): two copies of the loop, K % 4 == 0 (fewer VALU: the bench's K = 60) and K % 4 != 0
-        name = next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb1ELi0ELi4ELb0E"))
+        name = next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb1ELb0E"))
         rows = kernel_rows(name, "k_engine_synth_mfma<false, false, true>")
         new_rn = sorted((r for r in rows if r[2] and r[1]["mfma"] > 0), key=lambda r: r[1]["valu"])
         rep.append("")

@@ -1,7 +1,9 @@
-"""The fused synthesis kernel with its memory operands requested one phase ahead (synth_variant 16 + pf + 8 w3 + 16 noidx + 32 generic: epilogue
-operands of step j + 1 before the chains of step j, the red-noise rotation's first two K-steps before the ECORR staging, at 3 or 4
-workgroups per CU, with either addressing of the red-noise loop) against the kernel without any of it (synth_variant 48): loads and
-stores change place, no arithmetic does - the same bits, at the small shapes at which a reordering can go wrong.
+"""The four copies of the fused synthesis kernel's MFMA variant (synth_variant 16 + 16 noidx + 32 generic: scalar row offsets or per-lane
+index products in the red-noise loop, the straight-line epilogue compiled for a plan with GWB, white noise and ECORR or the epilogue for
+any plan) and the default (synth_variant 0, which picks among them) against one of them, the kernel as it was before the copies
+(synth_variant 48): the same loads, the same arithmetic - the same bits, at the small shapes at which the copies can differ (a single
+clamped lane, a tile less or plus one TOA, a partial realisation group, a counter offset beyond 2^32).  Values of synth_variant
+without a kernel, those of the retired prefetch and 3-per-CU instances among them, are refused.
 
 The host guard that sends a plan beyond the 32-bit lane offsets to the per-lane index products needs rn_k ldf 8 >= 2^32 (a design
 matrix of 4 GB): not reachable at a small shape.  The noidx bit of the variant runs the same loads."""
@@ -10,13 +12,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-BASE = 48                              # pf = 0 at 4 workgroups per CU, scalar row offsets, the copy for any plan: the kernel as it was
-PF4, PF3 = (0, 2), (0, 2, 4, 5, 6, 7)  # pipelining compiled at 4 / at 3 workgroups per CU (epilogue operands ahead: scratch at 128 VGPRs)
-VARIANTS = [16 + pf + 8 * w3 + 16 * noidx for noidx in (0, 1) for w3 in (0, 1) for pf in (PF3 if w3 else PF4)]
+BASE = 48                              # scalar row offsets, the copy for any plan: the kernel as it was
+VARIANTS = [16, 32]                    # 16 + 16 noidx: the copy for a complete plan where the plan is complete, either addressing
 # + 32: the copy compiled for any plan (requests inside `if (has_gw)` ...) also where the plan is complete and its own copy would run
-VARIANTS_GENERIC = [v + 32 for v in VARIANTS if v != 16]
-# wn_mode "single" is compiled at 3 per CU only (w3 is implied) and without the per-TOA operands ahead (scratch at 168 VGPRs)
-VARIANTS_SINGLE = [16 + pf + 8 + 16 * noidx for noidx in (0, 1) for pf in (0, 2, 4, 6)] + [16 + 2, 16 + 2 + 16]
+VARIANTS_GENERIC = [64]
+VARIANTS_SINGLE = [16, 32]             # wn_mode "single" has the same four copies (at 3 workgroups per CU)
 COUNTS = (1, 255, 256, 257, 300)       # a single clamped lane, a tile less one, a full tile, a tile plus one TOA, a short last tile
 BATCHES = ((1, 0), (16, 0), (17, 0), (17, 2 ** 32 - 3))   # (R, r0): 17 = a partial realisation group
 
@@ -107,8 +107,8 @@ def test_tail_clamp_loop_and_a_pulsar_without_red_noise(psrs):
 
 @pytest.mark.parametrize("off", ["rn", "gw", "wn", "ec"])
 def test_one_group_of_operands_absent(psrs, off):
-    """an engine without red noise (no rotation: the prologue has nothing to request), without GWB, without white noise, without
-    ECORR: each drops a group of prefetched operands, and the kernels compiled for a complete plan are not the ones launched."""
+    """an engine without red noise (no rotation), without GWB, without white noise, without ECORR: each drops a group of operands,
+    and the kernels compiled for a complete plan are not the ones launched."""
     eng = engine(psrs, rn=0 if off == "rn" else 30, wn=off != "wn", ec=off != "ec", gw=off != "gw")
     check(eng, VARIANTS, batches=BATCHES[1:])
 
@@ -127,7 +127,7 @@ def test_single_deviate_white_noise(psrs):
     eng = engine(psrs)
     eng.wn_mode = "single"
     check(eng, VARIANTS_SINGLE + [v + 32 for v in VARIANTS_SINGLE], batches=BATCHES[1:])
-    eng.synth_variant = 16 + 5 + 8   # per-TOA operands ahead do not exist for this mode: refused, not replaced
+    eng.synth_variant = 16 + 5 + 8   # a retired prefetch instance: refused, not replaced
     with pytest.raises(Exception):
         eng.generate(2)
     eng.synth_variant = 0
@@ -140,9 +140,14 @@ def test_rng_fast(psrs):
 
 
 def test_variants_without_a_kernel_are_refused(psrs):
+    import torch
     eng = engine(psrs, gw=False)
-    for v in (16 + 4, 16 + 5, 16 + 1, 16 + 3 + 8):   # epilogue operands ahead at 4 per CU; per-TOA operands ahead without the GWB ones
+    # 20, 21, 17, 27: never had a kernel; 18, 24, 50: one per retired bit (rotation prologue, 3 workgroups per CU, the prologue on the
+    # generic copy); 4, 8: the all-VALU kernel at other register budgets
+    for v in (16 + 4, 16 + 5, 16 + 1, 16 + 3 + 8, 18, 24, 50, 4, 8):
         eng.synth_variant = v
         with pytest.raises(Exception):
             eng.generate(2)
-    eng.synth_variant = 0
+        eng.synth_variant = 0
+        out = eng.generate(2)
+        assert out.shape == (2, eng.n_toa) and bool(torch.isfinite(out).all()) and float(out.abs().max()) > 0, v
