@@ -389,7 +389,8 @@ typedef struct {
   int32_t synth_variant;      /* fused-kernel variant: 0 (default) = red-noise F @ y on the matrix cores (16 realisations x 256 TOAs
                                  per workgroup), workgroups dealt to the XCDs in contiguous (tile, realisation-group) ranges; 1 = same
                                  kernel in plain linear workgroup order (A/B); 2 = the red-noise loop's per-lane 64-bit index products
-                                 instead of scalar row offsets, and never the copy compiled for a plan with GWB, white noise and ECORR
+                                 instead of scalar row offsets, a lane's four TOAs 16 apart with 8-byte accesses instead of two adjacent
+                                 pairs with 16-byte ones, and never the copy compiled for a plan with GWB, white noise and ECORR
                                  all present (A/B); 6 = all-VALU kernel (kept for cross-checks); 16 + 16 noidx + 32 generic (16, 32, 48,
                                  64) = test hook for the four copies of the kernel: noidx = with the index products of 2, generic =
                                  without the complete-plan copy of 0; all of these bit-identical; 100 + k (k <= 64) =

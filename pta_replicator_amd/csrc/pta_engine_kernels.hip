@@ -153,7 +153,8 @@ typedef double pta_f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 // it is compiled for three, where the occupancy curve of the kernel is already flat: 4.9 against 4.8 ms at 3 / 4 workgroups per CU)
 // RNIDX (red-noise loop addressing): true = a wave-uniform row offset from the scalar unit added to per-lane 32-bit byte offsets that are
 // computed once (the host guards their range); false = the per-lane 64-bit index product per load (synth_variant 2, and any plan
-// beyond the 32-bit range).  Same loads' values, same MFMA sequence: the two are bit-identical.
+// beyond the 32-bit range).  Same loads' values, same MFMA sequence: the two are bit-identical.  RNIDX = true (unless SINGLE) also gives a
+// lane two pairs of adjacent TOAs and 16-byte loads and stores (WIDE, below); RNIDX = false is the kernel as it was, TOAs 16 apart.
 // ALL = the plan has GWB, white noise and ECORR, known at compile time (the host looks): the waits the compiler places are exact only
 // over straight-line code - where a request sits in a branch (`if (has_gw)`), every value requested before that branch is waited for
 // as if the branch's requests had not been issued, i.e. together with them.  Every kernel therefore exists a second time for the plan
@@ -184,6 +185,16 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
   constexpr bool wn_single = SINGLE;            // opt-in: ONE deviate per TOA, amplitude sqrt((efac sigma)^2 + (efac equad | equad)^2)
   const int col = l & 15, quad = l >> 4;
   const int tbase = wv * 64 + col;  // TOA (inside the tile) of MFMA tile 0; tile j adds 16 j
+  // WIDE: column c of MFMA tile j stands for TOA 64 wv + 32 (j >> 1) + 2 c + (j & 1) instead - a lane owns two PAIRS of adjacent TOAs,
+  // 2 c, 2 c + 1 of each half of the wave's 64: its four design-matrix entries of a K-step are two 16-byte loads and its sixteen results
+  // eight 16-byte stores, and the sixteen lanes of a quad cover 256 contiguous bytes with each of them - whole cache lines, as the
+  // 8-byte accesses of the other mapping do.  (Four adjacent TOAs per lane, 4 c + j, make every 16-byte access of a quad touch half of
+  // each of four lines, the other half by the next instruction: measured slower than the 8-byte accesses)  Every dot
+  // product sums the same K-steps in the same order and every draw has the same counter: the values are those of the other mapping, bit
+  // for bit.  (The single-deviate kernel keeps 16 j: its lanes share a Box-Muller pair between TOAs 16 apart.)
+  constexpr bool WIDE = RNIDX && !SINGLE;
+  const int t2 = wv * 64 + 2 * col;
+  auto toa = [&](int j) { return WIDE ? t2 + 32 * (j >> 1) + (j & 1) : tbase + 16 * j; };  // TOA (inside the tile) of this lane in MFMA tile j, unclamped
   const int tile = (int)(item / nrg);
   const int rb = (int)(item - (int64_t)tile * nrg) * ENG_MR;
   const int a = pl.tile_psr[tile];
@@ -193,15 +204,30 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
   const int ep0 = has_ec ? pl.tile_ep0[tile] : 0;
   if (epn > 0) {  // the tile's ECORR deviates -> LDS
     const uint32_t strm = pta_stream_id(PTA_STREAM_ECORR, (uint32_t)a);
-    for (int idx = t; idx < epn * ENG_MR; idx += PTA_ENGINE_TILE) {
-      int q = idx / epn, p = idx - q * epn;
-      double z0, z1;
-      pta_normal_pair(seed, r0 + (uint64_t)(rb + q), strm, (uint32_t)(ep0 + p), z0, z1, fast);
-      zec[q][2 * p] = z0;
-      zec[q][2 * p + 1] = z1;
+    if (WIDE) {
+      // thread t draws realisation t >> 4, pairs (t & 15) + 16 trip: no division, and the realisation - with it the counter words
+      // the first Philox rounds multiply - is the same in every trip
+      const int q = t >> 4;
+      for (int p = t & 15; p < epn; p += PTA_ENGINE_TILE / ENG_MR) {
+        double z0, z1;
+        pta_normal_pair(seed, r0 + (uint64_t)(rb + q), strm, (uint32_t)(ep0 + p), z0, z1, fast);
+        zec[q][2 * p] = z0;
+        zec[q][2 * p + 1] = z1;
+      }
+    } else {
+      for (int idx = t; idx < epn * ENG_MR; idx += PTA_ENGINE_TILE) {
+        int q = idx / epn, p = idx - q * epn;
+        double z0, z1;
+        pta_normal_pair(seed, r0 + (uint64_t)(rb + q), strm, (uint32_t)(ep0 + p), z0, z1, fast);
+        zec[q][2 * p] = z0;
+        zec[q][2 * p + 1] = z1;
+      }
     }
     __syncthreads();
   }
+  // no barrier from here on: a wave whose 64 TOAs all lie beyond the tile's count would only repeat, lane for lane, the stores of the
+  // tile's last TOA that a live wave makes
+  if (WIDE && wv * 64 >= count) return;
   // No predicated stores anywhere below: a lane beyond the tile's count works on the tile's LAST TOA and a realisation row beyond
   // R on realisation R - 1 - same counters, same operands, bit-identical value - and stores it again to the same address.  (Stores
   // count in vmcnt on gfx950 and a predicated store is its own exec-masked block: behind a pending load the compiler waits
@@ -211,7 +237,7 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
   for (int g = 0; g < 4; ++g) rq[g] = min(quad + 4 * g, R - 1 - rb);
   int jl4[4];  // GWB bracket indices of this lane's four TOAs: requested now, needed (as addresses) after the red-noise product
 #pragma unroll
-  for (int j = 0; j < 4; ++j) jl4[j] = pl.gw_npts > 0 ? pl.gw_jlo[start + min(tbase + 16 * j, count - 1)] : 0;
+  for (int j = 0; j < 4; ++j) jl4[j] = pl.gw_npts > 0 ? pl.gw_jlo[start + min(toa(j), count - 1)] : 0;
   pta_f64x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = pta_f64x4{0.0, 0.0, 0.0, 0.0};
@@ -227,7 +253,7 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
     // one s_waitcnt vmcnt(0) per step: 15 serialised L2 round trips per workgroup)
     int tcl[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) tcl[j] = min(tbase + 16 * j, count - 1);
+    for (int j = 0; j < 4; ++j) tcl[j] = min(toa(j), count - 1);
     // three K-steps in flight: the operands of steps k0 + 4 and k0 + 8 are being loaded while step k0 runs on the matrix cores
     // (rotation by name, not by register moves; loads past K re-read bin K - 1 and are dropped)
     auto ld = [&](int k0, double &av, double (&bv)[4]) {
@@ -282,19 +308,33 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
 #pragma unroll
         for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const double *>(Fbytes + (uint32_t)(offF[j] + rowF));
       };
-      if ((K & 3) == 0) {
-        run([&](int k0, double &av, double (&bv)[4]) {
-          const uint32_t kg = (uint32_t)min(k0, klast);  // wave-uniform
-          ldu(k0, kg * ldfb, kg * 8u, av, bv);
-        });
-      } else {
-        const uint32_t dq = (uint32_t)(quad - min(quad, K - 1 - klast));  // bins this lane steps back inside the last group
-        run([&](int k0, double &av, double (&bv)[4]) {
-          const uint32_t kg = (uint32_t)min(k0, klast);
-          const uint32_t back = k0 >= klast ? dq : 0u;
-          ldu(k0, kg * ldfb - back * ldfb, kg * 8u - back * 8u, av, bv);
-        });
-      }
+      // WIDE, a full tile: the lane's four entries of a bin are two adjacent pairs, 32 TOAs apart - two 16-byte loads (rows are only
+      // 8-byte aligned)
+      auto lduw = [&](int k0, auto rowF, auto rowC, double &av, double (&bv)[4]) {
+        const double a_ld = *reinterpret_cast<const double *>(cbytes + (uint32_t)(offC + rowC));
+        av = (k0 < kq) ? a_ld : 0.0;
+        const char *__restrict__ src = Fbytes + (uint32_t)(offF[0] + rowF);
+        const pta_f64x2_a8 lo = *reinterpret_cast<const pta_f64x2_a8 *>(src), hi = *reinterpret_cast<const pta_f64x2_a8 *>(src + 256);
+        bv[0] = lo.x, bv[1] = lo.y, bv[2] = hi.x, bv[3] = hi.y;
+      };
+      auto rows = [&](auto &&ldx) {
+        if ((K & 3) == 0) {
+          run([&](int k0, double &av, double (&bv)[4]) {
+            const uint32_t kg = (uint32_t)min(k0, klast);  // wave-uniform
+            ldx(k0, kg * ldfb, kg * 8u, av, bv);
+          });
+        } else {
+          const uint32_t dq = (uint32_t)(quad - min(quad, K - 1 - klast));  // bins this lane steps back inside the last group
+          run([&](int k0, double &av, double (&bv)[4]) {
+            const uint32_t kg = (uint32_t)min(k0, klast);
+            const uint32_t back = k0 >= klast ? dq : 0u;
+            ldx(k0, kg * ldfb - back * ldfb, kg * 8u - back * 8u, av, bv);
+          });
+        }
+      };
+      // a tile cut short by the end of its pulsar keeps the clamped 8-byte loads (workgroup-uniform)
+      if (WIDE && count == PTA_ENGINE_TILE) rows(lduw);
+      else rows(ldu);
     } else {
       run(ld);
     }
@@ -311,27 +351,47 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
   // under that iteration's Box-Muller chains instead of in front of its first use of a loaded value.
   double pend[4] = {0.0, 0.0, 0.0, 0.0};
   int pend_i = 0;
+  // WIDE: a step writes v[g] + det back into acc[j][g]; two finished steps j0, j0 + 1 (j0 even) are two adjacent TOAs of every
+  // realisation row - one 16-byte store per row (ld_out and a view's first column leave rows 8-byte aligned).  The first pair goes out
+  // behind the operand loads of step 2, like the delayed stores above - holding all sixteen results to the end costs the registers the
+  // steps need.  A tile cut short by the end of its pulsar stores element by element at the clamped TOAs (workgroup-uniform choice).
+  auto store_half = [&](int j0) {
+    if (count == PTA_ENGINE_TILE) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<pta_f64x2_a8 *>(out + (int64_t)(rb + rq[g]) * ld_out + (start + toa(j0))) = pta_f64x2_a8{acc[j0][g], acc[j0 + 1][g]};
+    } else {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        out[(int64_t)(rb + rq[g]) * ld_out + (start + min(toa(j0), count - 1))] = acc[j0][g];
+        out[(int64_t)(rb + rq[g]) * ld_out + (start + min(toa(j0 + 1), count - 1))] = acc[j0 + 1][g];
+      }
+    }
+  };
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     // every per-TOA operand of this j: all requested together, up front - a load issued between the Box-Muller chains is waited for
     // on the spot
-    const int i = start + min(tbase + 16 * j, count - 1);
+    const int i = start + min(toa(j), count - 1);
     const double wgt = has_gw ? pl.gw_w[i] : 0.0;
     pta_f64x2_a8 y[4];
+    // (WIDE: a bracket index is not negative - zero-extended where it is used, it stays one register across the red-noise product)
+    const int64_t jlo = jl4[j];
     if (has_gw) {  // GWB: both bracket samples of the mixed grid series in one 16-byte load (red_noise.py:286-287)
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        y[g] = *reinterpret_cast<const pta_f64x2_a8 *>(pl.gw_G + ((int64_t)(rb + rq[g]) * P + a) * pl.gw_npts + jl4[j]);
+        y[g] = *reinterpret_cast<const pta_f64x2_a8 *>(pl.gw_G + ((int64_t)(rb + rq[g]) * P + a) * pl.gw_npts + jlo);
     }
     const double wa = has_wn ? (wn_single ? pl.wn_c[i] : pl.wn_a[i]) : 0.0, wb = (has_wn && !wn_single) ? pl.wn_b[i] : 0.0;
     const uint32_t pair = (uint32_t)pl.idx_in_psr[i];
     const double ec = has_ec ? pl.ecorr_toa[i] : 0.0;
     const int e = has_ec ? pl.epoch_of[i] : 0;
     const double det = pl.det ? pl.det[i] : 0.0;
-    if (j > 0) {
+    if (!WIDE && j > 0) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) out[(int64_t)(rb + rq[g]) * ld_out + pend_i] = pend[g];
     }
+    if (WIDE && j == 2) store_half(0);  // likewise behind the loads of the step that follows
     double v[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) v[g] = acc[j][g];
@@ -382,12 +442,21 @@ __global__ __launch_bounds__(PTA_ENGINE_TILE, SINGLE ? 3 : 4) void k_engine_synt
       }
 #endif
     }
+    if (WIDE) {  // back into the accumulator: everything is stored after the last step
 #pragma unroll
-    for (int g = 0; g < 4; ++g) pend[g] = v[g] + det;
-    pend_i = i;
+      for (int g = 0; g < 4; ++g) acc[j][g] = v[g] + det;
+    } else {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pend[g] = v[g] + det;
+      pend_i = i;
+    }
   }
+  if (WIDE) {
+    store_half(2);
+  } else {
 #pragma unroll
-  for (int g = 0; g < 4; ++g) out[(int64_t)(rb + rq[g]) * ld_out + pend_i] = pend[g];
+    for (int g = 0; g < 4; ++g) out[(int64_t)(rb + rq[g]) * ld_out + pend_i] = pend[g];
+  }
 }
 
 // the instance of k_engine_synth_mfma for a launch
@@ -435,10 +504,10 @@ extern "C" int pta_engine_synth(const pta_engine_plan *plan_host, uint64_t seed,
     const unsigned pad = variant >= 100 ? (unsigned)(variant - 100) * 1024u : 0u;
     const int64_t total = (int64_t)pta_cdiv(R, ENG_MR) * p.n_tiles, nwg = ((total + 7) >> 3) << 3;
     PTA_REQUIRE(nwg < (1LL << 31), PTA_E_ARG, "pta_engine_synth: %lld workgroups exceed one launch", (long long)nwg);
-    // the 32-bit lane offsets of the red-noise loop: up to ((K - 1) ldf + 255) 8 from a tile's first design-matrix entry, R P K 8
-    // into the coefficients
+    // the 32-bit lane offsets of the red-noise loop: up to ((K - 1) ldf + 255) 8 from a tile's first design-matrix entry (the 16-byte
+    // loads end inside the same tile; 24 bytes more are allowed for), R P K 8 into the coefficients
     const bool noidx = variant == 2 || (copies && ((variant - 16) & 16));
-    const bool rnidx = !noidx && p.rn_k > 0 && p.ldf < (1LL << 28) && ((int64_t)p.rn_k * p.ldf + PTA_ENGINE_TILE) * 8 < (1LL << 32) &&
+    const bool rnidx = !noidx && p.rn_k > 0 && p.ldf < (1LL << 28) && ((int64_t)p.rn_k * p.ldf + PTA_ENGINE_TILE) * 8 + 24 < (1LL << 32) &&
                        (int64_t)R * p.n_psr * p.rn_k * 8 < (1LL << 32);
     const bool generic = variant == 2 || (copies && ((variant - 16) & 32));
     const bool all = !generic && p.gw_npts > 0 && (p.wn_a || p.wn_c) && p.ecorr_toa;

@@ -12,8 +12,14 @@ element of k_engine_synth_mfma<false> go.  No GPU needed: hipcc --save-temps for
     k_gwb_czt<true, false, FUSE, false> is counted for the fused step 15, each of the bits 16 / 32 / 64 alone, the default and all three, with
     the twiddle and butterfly pieces those bits remove compiled on their own like the pieces of the draw.
 
-Writes profiles/r13_isa_instruction_classes.txt (r03_isa_instruction_classes.txt is the table of the kernel as it was in round 3).  The PMC
-figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of profiles/r06_pmc.json."""
+  * RNIDX = true (unless SINGLE) also means two pairs of adjacent TOAs per lane: in a full tile the red-noise loop loads the design matrix
+    16 bytes at a time (the loop copies with 9 memory instructions per trip; the copies with 15 serve a tile cut short), and the results
+    leave as 16-byte stores.  The copy for complete plans (ALL = true, the one the bench workload runs) is listed and estimated as well,
+    and every instance's registers, scratch and LDS, for this build and for the library's own (with the per-TOA ECORR path).
+
+Writes profiles/r17_isa_instruction_classes.txt (r13_isa_instruction_classes.txt is the table before the adjacent-TOA mapping,
+r03_isa_instruction_classes.txt the kernel as it was in round 3).  The PMC figure to compare with is SQ_INSTS_VALU / (R * n_toa / 64) of
+profiles/r17_synth_wide.json."""
 import collections
 import os
 import re
@@ -160,16 +166,29 @@ def main():
         old_rn = [r for r in old_rows if r[2] and r[1]["mfma"] > 0]
         # ... and with scalar row offsets (RNIDX = true, default): two copies of the loop, K % 4 == 0 (fewer VALU: the bench's K = 60) and K % 4 != 0
         name = next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb1ELb0E"))
-        rows = kernel_rows(name, "k_engine_synth_mfma<false, false, true>")
-        new_rn = sorted((r for r in rows if r[2] and r[1]["mfma"] > 0), key=lambda r: r[1]["valu"])
+        rows = kernel_rows(name, "k_engine_synth_mfma<false, false, true, false>")
+        all_rows = kernel_rows(next(k for k in kb if k.startswith("_Z19k_engine_synth_mfmaILb0ELb0ELb1ELb1E")),
+                               "k_engine_synth_mfma<false, false, true, true> (the copy for complete plans: the bench workload's)")
+        # four copies of the loop: 16-byte loads (full tile: fewer memory instructions) or 8-byte loads (tile cut short), K % 4 == 0 or not
+        def loops(rs):
+            rn = [r for r in rs if r[2] and r[1]["mfma"] > 0]
+            wide = sorted((r for r in rn if r[1]["vmem"] == min(x[1]["vmem"] for x in rn)), key=lambda r: r[1]["valu"])
+            narrow = sorted((r for r in rn if r not in wide), key=lambda r: r[1]["valu"])
+            return rn, wide, narrow
+        rn_all, new_rn, narrow_rn = loops(rows)
         rep.append("")
-        rep.append("red-noise MFMA loop, per trip of 12 bins (3 K-steps, 15 loads):")
-        for title, r in [("per-lane 64-bit index products (before; synth_variant 2)", old_rn[0]), ("scalar row offsets, K % 4 == 0 (default)", new_rn[0]),
-                         ("scalar row offsets, K % 4 != 0 (tail clamp)", new_rn[-1])]:
-            rep.append(f"  {title:58s} {r[0]:10s} valu {r[1]['valu']:3d} salu {r[1]['salu']:3d}   {mix(r[3])}")
-        rep.append(f"  static VALU of the kernel, per thread: {sum(r[1]['valu'] for r in old_rows)} before, {sum(r[1]['valu'] for r in rows)} after (after holds both copies of the loop)")
-        tail_valu = new_rn[-1][1]["valu"] if len(new_rn) > 1 else 0
-        rows = [r for r in rows if not (len(new_rn) > 1 and r[0] == new_rn[-1][0])]   # the dynamic estimate below takes the K % 4 == 0 copy
+        rep.append("red-noise MFMA loop, per trip of 12 bins (3 K-steps):")
+        for title, r in [("per-lane 64-bit index products (synth_variant 2), 8-byte loads", old_rn[0]),
+                         ("scalar row offsets, K % 4 == 0, 8-byte loads (tile cut short)", narrow_rn[0]),
+                         ("scalar row offsets, K % 4 != 0, 8-byte loads (tile cut short)", narrow_rn[-1]),
+                         ("scalar row offsets, K % 4 == 0, 16-byte loads (default)", new_rn[0]),
+                         ("scalar row offsets, K % 4 != 0, 16-byte loads", new_rn[-1])]:
+            rep.append(f"  {title:66s} {r[0]:10s} valu {r[1]['valu']:3d} salu {r[1]['salu']:3d} vmem {r[1]['vmem']:3d}   {mix(r[3])}")
+        rep.append(f"  static VALU of the kernel, per thread: {sum(r[1]['valu'] for r in old_rows)} (synth_variant 2), {sum(r[1]['valu'] for r in rows)} (default; holds all four copies of the loop)")
+        keep = new_rn[0][0]
+        rows = [r for r in rows if not (r in rn_all and r[0] != keep)]   # the dynamic estimate below takes the copy the bench workload runs
+        rn_a, wide_a, _ = loops(all_rows)
+        all_rows = [r for r in all_rows if not (r in rn_a and r[0] != wide_a[0][0])]
         # dynamic estimate: loops = blocks that branch back to themselves.  Identify them by content: the staging loop holds the
         # Philox multiplies (v_mad_u64_u32) and LDS writes but no MFMA; the red-noise loop holds MFMAs
         stag = [r for r in rows if r[2] and r[1]["mfma"] == 0 and r[1]["valu"] > 50]
@@ -192,6 +211,33 @@ def main():
         rep.append("per Gaussian pair: Philox 46 (20 of them v_mad_u64_u32 at half rate), uniforms 10, -2 ln u 22, sqrt 10, sin / cos 26, products 2")
         old_dyn = sum(r[1]["valu"] for r in old_rows if not r[2]) + sum(r[1]["valu"] for r in old_rows if r[2] and r[1]["mfma"] == 0 and r[1]["valu"] > 50) * t_stag + old_rn[0][1]["valu"] * t_rn
         rep.append(f"the same estimate with the per-lane index products: {old_dyn:.0f} per wave, {old_dyn / 16.0:.1f} per output element ({100 * (old_dyn - dyn) / old_dyn:.1f} % more)")
+        a_once = sum(r[1]["valu"] for r in all_rows if not r[2])
+        a_stag = sum(r[1]["valu"] for r in all_rows if r[2] and r[1]["mfma"] == 0 and r[1]["valu"] > 50)
+        a_rn = sum(r[1]["valu"] for r in all_rows if r[2] and r[1]["mfma"] > 0)
+        a_dyn = a_once + a_stag * t_stag + a_rn * t_rn
+        a_mem = sum(r[1]["vmem"] for r in all_rows if not r[2]) + sum(r[1]["vmem"] for r in all_rows if r[2] and r[1]["mfma"] > 0) * t_rn
+        rep.append(f"the copy for complete plans: straight-line {a_once} + staging loop {a_stag} x {t_stag:.2f} + red-noise loop {a_rn} x {t_rn:.0f} = {a_dyn:.0f} per wave, "
+                   f"{a_dyn / 16.0:.1f} per output element; global-memory instructions per wave (both store paths and the loop prologues of all copies counted): {a_mem:.0f}")
+        # ---- every instance's resources, in this build and in the library's own
+        def resources(asm):
+            meta = open(asm).read()
+            out = {}
+            for m in re.finditer(r"\.amdhsa_kernel (_Z19k_engine_synth_mfmaILb(\d)ELb(\d)ELb(\d)ELb(\d)E\S*)(.*?)\.end_amdhsa_kernel", meta, re.S):
+                g = lambda key: int(re.search(key + r"\s+(\d+)", m.group(6)).group(1))
+                out[tuple(int(m.group(i)) for i in (2, 3, 4, 5))] = (g("amdhsa_next_free_vgpr"), g("amdhsa_next_free_sgpr"), g("amdhsa_private_segment_fixed_size"),
+                                                                    g("amdhsa_group_segment_fixed_size"))
+            return out
+        res_tab = resources(os.path.join(d, "pta_engine_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"))
+        os.makedirs(os.path.join(d, "lib"))
+        subprocess.check_call([HIPCC] + FLAGS + [os.path.join(CSRC, "pta_engine_kernels.hip"), "-o", os.path.join(d, "lib", "eng.o")], cwd=os.path.join(d, "lib"),
+                              stderr=subprocess.DEVNULL)
+        res_lib = resources(os.path.join(d, "lib", "pta_engine_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"))
+        rep.append("")
+        rep.append("k_engine_synth_mfma<FAST, SINGLE, RNIDX, ALL>: next free VGPR / next free SGPR / scratch bytes per lane / LDS bytes (128 VGPRs = 4 workgroups per CU; SINGLE is compiled for 3)")
+        rep.append("FAST SINGLE RNIDX ALL    this table's build (staged-ECORR path only)    the library's build")
+        for key in sorted(res_tab):
+            a, b = res_tab[key], res_lib[key]
+            rep.append(f"   {key[0]}      {key[1]}     {key[2]}   {key[3]}    {a[0]:4d} / {a[1]:3d} / {a[2]:3d} / {a[3]:6d}                      {b[0]:4d} / {b[1]:3d} / {b[2]:3d} / {b[3]:6d}")
         # ---- the chirp-z kernel
         rep.append("")
         rep.append("k_gwb_czt<true, false, FUSE, false>: static counts per thread (FUSE & 64 holds the full AND the pruned last butterfly: a launch runs one of them)")
@@ -220,7 +266,7 @@ def main():
         rep.append(f"removed per thread: bit 16 {tw_own} (last pass reuses the first pass's set), bit 32 {2 * tw_own} + {2 * (tw_own - prod)} (s = 8 sets complete from LDS, s = 64 sets four products "
                    f"from LDS), bit 64 {full - out01} + the post-chirp products and exec-masked store blocks of outputs 2..7; the table fill ({tw_own} + 8 in waves 0 and 1) and "
                    f"{2 * 7 + 2 * 3} ds_read_b128 per thread are added")
-    path = os.path.join(ROOT, "profiles", "r13_isa_instruction_classes.txt")
+    path = os.path.join(ROOT, "profiles", "r17_isa_instruction_classes.txt")
     open(path, "w").write("\n".join(rep) + "\n")
     print("\n".join(rep))
 
