@@ -184,6 +184,7 @@ ENGINE_TILE = 256   # PTA_ENGINE_TILE
 ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX
 CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 CW_CATALOG_NPAR = (16, 8, 8)  # by mode: PTA_CW_CATALOG_NPAR_EVOLVE, PTA_CW_CATALOG_NPAR_FOLDED (phase_approx, monochromatic)
+OS_CMAX = 64         # PTA_OS_CMAX
 OSM_KMAX = 128       # PTA_OSM_KMAX
 LNL_KMAX = 128       # PTA_LNL_KMAX
 LNL_MMAX = 16        # PTA_LNL_MMAX

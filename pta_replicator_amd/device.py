@@ -23,6 +23,13 @@ def f64(x, device=None):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64)), device=device or require_gpu())
 
 
+def as_f64(x):
+    """contiguous float64 device tensor from a tensor (any device or dtype) or an array-like."""
+    if hasattr(x, "data_ptr"):
+        return x.to(device=require_gpu(), dtype=torch.float64).contiguous()
+    return f64(x)
+
+
 def i32(x, device=None):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.int32)), device=device or require_gpu())
 
@@ -45,6 +52,11 @@ def ptr(t):
         return ctypes.c_void_p(0)
     assert t.is_contiguous()
     return ctypes.c_void_p(t.data_ptr())
+
+
+def row_ptr(t, lo):
+    """raw device pointer of t[lo] along the first axis (None -> None)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr() + lo * t.stride(0) * t.element_size())
 
 
 def hptr(a):

@@ -471,28 +471,26 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             self.tdgw_plan.z, self.tdgw_plan.ld_z, self.tdgw_plan.blk_zoff = None, 0, None   # (generate_td may have pointed it at a deviate buffer)
         s = dv.stream_ptr()
         P = self.P
-
-        def at(t, lo, per_row):
-            return None if t is None else ctypes.c_void_p(t.data_ptr() + 8 * lo * per_row)
+        at = dv.row_ptr
         for lo in range(0, R, step):
             n = min(step, R - lo)
-            optr = ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0))
+            optr = at(out, lo)
             h = None
             if dev is not None:
                 h = _lib.EngineHyper()
                 if self.plan.rn_k:
                     h.rn_f, h.rn_tspan = hy["rn_f"].data_ptr(), hy["rn_tspan"].data_ptr()
-                    h.rn_log10_A, h.rn_gamma = at(dev["rn_log10_A"], lo, P), at(dev["rn_gamma"], lo, P)
+                    h.rn_log10_A, h.rn_gamma = at(dev["rn_log10_A"], lo), at(dev["rn_gamma"], lo)
                 if gw_theta:
                     h.ld_gw_scale, h.ws_scale = self.grid["Nf"], ws["scale"].data_ptr()
-                    h.gw_log10_A, h.gw_gamma = at(dev["gwb_log10_A"], lo, 1), at(dev["gwb_gamma"], lo, 1)
+                    h.gw_log10_A, h.gw_gamma = at(dev["gwb_log10_A"], lo), at(dev["gwb_gamma"], lo)
                     h.gw_f, h.gw_hcf0 = hy["gw_f"].data_ptr(), hy["gw_hcf0"].data_ptr()
                     c = self._gw
                     h.gw_turnover, h.gw_f0, h.gw_beta, h.gw_power = int(bool(c["turnover"])), float(c["f0"]), float(c["beta"]), float(c["power"])
                 if spec is not None:   # the scale row from the realisation's own spectrum, queued ahead of the launch sequence
                     Nf, M = self.grid["Nf"], spec.shape[1]
                     _lib.call("pta_gwb_spectrum_scale_user", dv.ptr(hy["spec_seg"]), dv.ptr(hy["spec_dx"]), dv.ptr(hy["spec_dxp"]),
-                              dv.ptr(hy["gw_hcf0"]), Nf, M, n, at(spec, lo, M), M, dv.ptr(ws["scale"]), Nf, s)
+                              dv.ptr(hy["gw_hcf0"]), Nf, M, n, at(spec, lo), M, dv.ptr(ws["scale"]), Nf, s)
                     h.gw_scale, h.ld_gw_scale = ws["scale"].data_ptr(), Nf
             if not grid_mode:
                 args = (self.seed, r0 + lo, n, optr, out.stride(0), s)
@@ -527,27 +525,31 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         {gwb_log10_A, gwb_gamma: [R] or None, rn_log10_A, rn_gamma: [R, P] or None, gwb_log10_hc: [R, M] or None, its columns in
         ascending node frequency}.  Pulsars without red noise get NaN amplitudes (mask_unconfigured=False: theta of sample_theta, which
         has them already)."""
-        def f64(x):
-            if hasattr(x, "data_ptr"):
-                return x.to(device=dv.require_gpu(), dtype=torch.float64).contiguous()
-            return dv.f64(np.ascontiguousarray(x, dtype=np.float64))
         dev = dict.fromkeys(_hyper.ALL_KEYS)
         if _hyper.SPEC_KEY in th:
-            y = f64(th[_hyper.SPEC_KEY])
-            order = self._hyper_tables()["spec_order"]
-            dev[_hyper.SPEC_KEY] = y if order is None else y.index_select(1, order).contiguous()
+            dev[_hyper.SPEC_KEY] = self._spec_theta_device(th)
         if any(k in th for k in _hyper.GWB_KEYS):
             for k, conf in (("gwb_log10_A", self._gw["A"]), ("gwb_gamma", self._gw["g"])):
-                dev[k] = f64(th[k]) if k in th else torch.full((R,), float(conf), dtype=torch.float64, device=dv.require_gpu())
+                dev[k] = dv.as_f64(th[k]) if k in th else torch.full((R,), float(conf), dtype=torch.float64, device=dv.require_gpu())
         if any(k in th for k in _hyper.RN_KEYS) and self.plan.rn_k:
-            conf = _hyper.configured_rn(self._rn)
-            for k, c in zip(_hyper.RN_KEYS, conf):
-                dev[k] = f64(th[k]) if k in th else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
-            none = self._hyper_tables()["rn_none"]
-            if mask_unconfigured and len(none):   # configured without red noise: keeps none (amp_fixed row is zero)
-                dev["rn_log10_A"] = dev["rn_log10_A"].clone()
-                dev["rn_log10_A"][:, none] = float("nan")
+            self._rn_theta_device(th, R, dev, mask_unconfigured)
         return dev
+
+    def _spec_theta_device(self, th):
+        """theta's gwb_log10_hc -> [R, M] on the device, its columns in ascending node frequency"""
+        y = dv.as_f64(th[_hyper.SPEC_KEY])
+        order = self._hyper_tables()["spec_order"]
+        return y if order is None else y.index_select(1, order).contiguous()
+
+    def _rn_theta_device(self, th, R, dev, mask_unconfigured=True):
+        """dev's rn_log10_A and rn_gamma [R, P] from validated theta, a key not given filled with the configured values; pulsars
+        configured without red noise get NaN amplitudes (mask_unconfigured)"""
+        for k, c in zip(_hyper.RN_KEYS, _hyper.configured_rn(self._rn)):
+            dev[k] = dv.as_f64(th[k]) if k in th else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
+        none = self._hyper_tables()["rn_none"]
+        if mask_unconfigured and len(none):   # configured without red noise: keeps none (amp_fixed row is zero)
+            dev["rn_log10_A"] = dev["rn_log10_A"].clone()
+            dev["rn_log10_A"][:, none] = float("nan")
 
     def _hyper_tables(self):
         """theta-independent device tables of the hyper path, built once per prepare(): GWB frequency grid and configured hcf,
@@ -596,17 +598,12 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             return self._cw_catalog_apply(cw, R, out, accumulate)
         if not self._prepared:
             self.prepare()
-        dev = dv.require_gpu()
         P = self.P
-
-        def col(x, shape):
-            t = x.to(device=dev, dtype=torch.float64) if hasattr(x, "data_ptr") else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev)
-            return t.reshape(shape)
         amp = _cw.amp_key(cw)
-        cols = [col(cw[amp if c == "amp" else "cw_" + c], (R, 1)) for c in _cw.COLUMNS]
+        cols = [dv.as_f64(cw[amp if c == "amp" else "cw_" + c]).reshape(R, 1) for c in _cw.COLUMNS]
         has_pd = _cw.PDIST_KEY in cw
         if has_pd:
-            cols.append(col(cw[_cw.PDIST_KEY], (R, P)))
+            cols.append(dv.as_f64(cw[_cw.PDIST_KEY]).reshape(R, P))
         src = torch.cat(cols, dim=1).contiguous()
         conf, tb = self._cw, self._cw_tables()
         step = min(R, self.max_batch(hyper=True, cw=True))
@@ -636,19 +633,14 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             self.prepare()
         dev = dv.require_gpu()
         P, S = self.P, _cw.n_sources(cw)
-
-        def col(x, shape, dtype=torch.float64):
-            if hasattr(x, "data_ptr"):
-                t = x.to(device=dev, dtype=dtype)
-            else:
-                t = torch.as_tensor(np.asarray(x, dtype=np.float64 if dtype is torch.float64 else np.int32), device=dev)
-            return t.reshape(shape)
         amp = _cw.amp_key(cw)
-        src = torch.stack([col(cw[amp if c == "amp" else "cw_" + c], (R, S)) for c in _cw.COLUMNS], dim=2).contiguous()   # [R, S, 8]
+        src = torch.stack([dv.as_f64(cw[amp if c == "amp" else "cw_" + c]).reshape(R, S) for c in _cw.COLUMNS], dim=2).contiguous()   # [R, S, 8]
         has_pd = _cw.PDIST_KEY in cw
         conf, tb = self._cw, self._cw_tables()
-        pdist = col(cw[_cw.PDIST_KEY], (R, P)).contiguous() if has_pd else tb["pdist"]
-        count = col(cw[_cw.COUNT_KEY], (R,), torch.int32).contiguous() if _cw.COUNT_KEY in cw else None
+        pdist = dv.as_f64(cw[_cw.PDIST_KEY]).reshape(R, P) if has_pd else tb["pdist"]
+        count = cw.get(_cw.COUNT_KEY)
+        if count is not None:
+            count = (count.to(device=dev, dtype=torch.int32) if hasattr(count, "data_ptr") else dv.i32(count)).reshape(R).contiguous()
         mode = _cw.mode(conf)
         npar = _lib.CW_CATALOG_NPAR[mode]
         step = min(R, self.max_batch(hyper=True, cw=S))

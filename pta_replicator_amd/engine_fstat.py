@@ -17,6 +17,9 @@ output mode they are computed in.
 The noise weights are the configured ones (white noise + ECORR + red noise, optionally the GWB auto-term, timing model
 marginalised): a statistic matched to per-realisation noise parameters theta is out of scope, as are the pulsar term and frequency
 evolution across the data span.
+
+The argument checks, the host noise model, the rows and state checks and the chunked generation loop with its rows buffer are
+engine_stats.StatisticsMixin's, shared with the optimal statistic and the likelihood.
 """
 import ctypes
 
@@ -27,9 +30,10 @@ from . import _cw, _lib, device as dv
 from . import f_statistic as fst
 from . import optimal_statistic as ost
 from ._position import ra_dec
+from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 
-class FStatisticMixin:
+class FStatisticMixin(StatisticsMixin):
     def prepare_f_statistic(self, freqs, sky=None, timing_model="spin", gwb_auto=None, components=14, gamma=13. / 3.):
         """W, G^-1 (and with a sky grid phi, M^-1) of the array under the configured noise model (white noise + ECORR + red noise,
         optionally the GWB auto-term), uploaded once.  Returns self.
@@ -43,10 +47,8 @@ class FStatisticMixin:
         out of scope.  A frequency at which a pulsar's sin / cos pair is not constrained (one the spin-down fit absorbs) is refused."""
         f = fst.check_freqs(freqs)
         sky = fst.check_sky(sky)
-        if timing_model not in ("spin", "astrometric", None):
-            raise ValueError(f"timing_model={timing_model!r} must be 'spin', 'astrometric' or None")
-        if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
-            raise ValueError(f"components={components!r}: an integer 1 .. 32")
+        check_timing_model(timing_model)
+        check_components(components, columns="")
         J = len(f)
         if 2 * J > _lib.FSTAT_CMAX:
             raise ValueError(f"{J} frequencies: one preparation holds at most {_lib.FSTAT_CMAX // 2}")
@@ -54,35 +56,18 @@ class FStatisticMixin:
             raise ValueError("the coherent Fe statistic needs at least two pulsars; Fp alone (sky=None) works for one")
         if sky is not None and self.P > _lib.FSTAT_PMAX:
             raise ValueError(f"the Fe kernel holds at most {_lib.FSTAT_PMAX} pulsars, got {self.P}")
-        if self._wn is None:
-            raise ValueError("the F-statistic needs measurement noise (set_white_noise): without it the noise covariance is singular")
+        self._stats_need_noise("the F-statistic")
         if 2 * J * self.n_toa * 8 > int(self.workspace_bytes):
             raise ValueError(f"the projection operator [2 J = {2 * J}, n_toa = {self.n_toa}] takes {2 * J * self.n_toa * 8} bytes, more than "
                              f"workspace_bytes = {int(self.workspace_bytes)}: use fewer frequencies per preparation or raise workspace_bytes")
-        gw_lA = None
-        if gwb_auto is None:
-            gw_lA = float(self._gw["A"]) if self._gw is not None else None
-        elif gwb_auto is False:
-            pass
-        elif isinstance(gwb_auto, (bool, np.bool_)):
-            raise ValueError("gwb_auto: None, a log10 amplitude, or False")
-        else:
-            gw_lA = float(gwb_auto)
-        if not self._prepared:
-            self.prepare()
-        from .simulate import timing_design_matrix
+        gw_lA = self._stats_gwb_auto(gwb_auto)
+        toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
         P = self.P
-        toas = [m * 86400.0 for m in self.mjd]
-        wa, wb = self.d_wn_a.cpu().numpy(), self.d_wn_b.cpu().numpy()
-        sigma2 = [wa[self.off[a]:self.off[a + 1]] ** 2 + wb[self.off[a]:self.off[a + 1]] ** 2 for a in range(P)]
-        epoch_of = ecorr = None
-        if self._ec is not None:
-            epoch_of, ecorr = self.epoch_of, self.ecorrvec
         F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]     # the low-rank part of C_a: red noise, then the GWB auto-term
-        if self.plan.rn_k:
+        if F_rn is not None:
             for a in range(P):
-                F_low[a].append(self._rn_basis_host(a))
-                phi_low[a].append(self.rn_amp[a] ** 2)
+                F_low[a].append(F_rn[a])
+                phi_low[a].append(phi_rn[a])
         if gw_lA is not None:
             T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
             S = ost.unit_spectrum(int(components), T, float(gamma))
@@ -90,7 +75,6 @@ class FStatisticMixin:
                 F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
                 phi_low[a].append(10.0 ** (2 * gw_lA) * S)
         low = bool(F_low[0])
-        M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
         phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs]) if sky is not None else None
         plan = fst.prepare(toas, sigma2, f, phat=phat, sky=sky, epoch_of=epoch_of, ecorr=ecorr,
                            F_rn=[np.concatenate(x, axis=1) for x in F_low] if low else None,
@@ -102,11 +86,7 @@ class FStatisticMixin:
         return self
 
     def _fs_state(self, what, sky_max=False):
-        st = getattr(self, "_fs", None)
-        if st is None:
-            raise ValueError(f"{what}: the F-statistic is not prepared (prepare_f_statistic first)")
-        if not self._prepared or st["engine_plan"] is not self.plan:
-            raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_f_statistic(): call it again")
+        st = self._stats_state("_fs", "the F-statistic", "prepare_f_statistic", what)
         if sky_max and st["phi"] is None:
             raise ValueError(f"{what}: sky_max=True needs a sky grid (prepare_f_statistic(freqs, sky=...))")
         return st
@@ -148,16 +128,15 @@ class FStatisticMixin:
         _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, 2 * J, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
                   dv.ptr(Q), P * 2 * J, s)
         fp = out["fp"]
-        _lib.call("pta_fstat_fp", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["Ginv"]), ctypes.c_void_p(fp.data_ptr() + 8 * lo * J), J, s)
+        _lib.call("pta_fstat_fp", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["Ginv"]), dv.row_ptr(fp, lo), J, s)
         if st["phi"] is None:
             return
         if sky_max:
             _lib.call("pta_fstat_fe", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]), None, 0,
-                      ctypes.c_void_p(out["fe_max"].data_ptr() + 8 * lo * J), J, ctypes.c_void_p(out["fe_arg"].data_ptr() + 4 * lo * J), J,
-                      dv.ptr(ws["pv"]), dv.ptr(ws["pa"]), s)
+                      dv.row_ptr(out["fe_max"], lo), J, dv.row_ptr(out["fe_arg"], lo), J, dv.ptr(ws["pv"]), dv.ptr(ws["pa"]), s)
         else:
             _lib.call("pta_fstat_fe", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]),
-                      ctypes.c_void_p(out["fe"].data_ptr() + 8 * lo * J * S), J * S, None, 0, None, 0, None, None, s)
+                      dv.row_ptr(out["fe"], lo), J * S, None, 0, None, 0, None, None, s)
 
     def f_statistic(self, rows, sky_max=False):
         """Fp and Fe of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
@@ -168,13 +147,7 @@ class FStatisticMixin:
         are the caller's result and lie outside that budget: the full map takes R J S 8 bytes, and sky_max=True is the way to stay
         small."""
         st = self._fs_state("f_statistic", sky_max)
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
-            raise ValueError("rows must be a float64 device tensor")
-        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
-        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
-            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
-        R = int(rows.shape[0])
+        R = self._stats_check_rows(rows)
         out = self._fs_out(st, R, sky_max)
         step = self._fs_chunk(st, R, sky_max, with_rows=False)
         for lo in range(0, R, step):
@@ -193,23 +166,7 @@ class FStatisticMixin:
             raise ValueError(f"generate_f_statistic: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
         hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
         chunk = max(1, min(chunk, self._fs_chunk(st, R, sky_max, with_rows=True)))
-        buf = getattr(self, "_fs_rows", None)
-        if buf is None or buf.shape[0] < chunk:
-            self._fs_rows = None
-            buf = self._fs_rows = dv.empty((chunk, self.n_toa))
         out = self._fs_out(st, R, sky_max)
-
-        def rows_of(part, lo, n):
-            return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
-        for lo in range(0, R, chunk):
-            n = min(chunk, R - lo)
-            rows = buf[:n]
-            if td:
-                self.generate_td(n, r0=r0 + lo, out=rows)
-                if cw:
-                    self._cw_apply(rows_of(cw, lo, n), n, rows)
-            else:
-                self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
-            self._fs_state("generate_f_statistic")     # generate_td / generate may have (re)prepared the engine
+        for lo, n, rows in self._stats_generate_chunks(lambda: self._fs_state("generate_f_statistic"), R, r0, hyper, cw, td, chunk):
             self._fs_launch(rows, n, lo, out)
         return self._fs_result(st, out)

@@ -16,18 +16,18 @@ ln L.  A (realisation, grid point) value is bit-identical whatever chunks, rows 
 
 The model is the matched optimal statistic's: white noise, ECORR and the timing model are fixed, the timing model is marginalised
 with a flat prior, red noise sits on the red-noise columns and a common uncorrelated process with the GWB spectrum on the 2 n_f
-columns of the array-wide Fourier basis.
+columns of the array-wide Fourier basis.  The grid goes to the device as the matched statistic's theta does, and the rest of the host
+front (argument checks, host noise model, rows and state checks, blocked projection, the chunked generation loop with its rows
+buffer) is shared too: engine_stats.StatisticsMixin.
 """
 import ctypes
 
-import numpy as np
-import torch
-
 from . import _cw, _hyper, _lib, device as dv
 from . import optimal_statistic as ost
+from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 
-class LikelihoodMixin:
+class LikelihoodMixin(StatisticsMixin):
     def prepare_likelihood(self, components=14, gamma=13. / 3., timing_model="spin", gwb_auto=None):
         """Operands of ln L(r | theta) under the configured noise model, uploaded once.  Works for a single pulsar; needs no ORFs.
 
@@ -35,37 +35,15 @@ class LikelihoodMixin:
         where the grid gives none; timing_model: "spin", "astrometric" or None; gwb_auto: None = the configured GWB amplitude if a
         GWB is set, else no common process; a float = that log10_A; False = off (gwb_* grid keys are then refused).
         K = red-noise columns + 2 n_f <= 128."""
-        if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
-            raise ValueError(f"components={components!r}: an integer 1 .. 32 (2 n_f <= 64 columns)")
-        if timing_model not in ("spin", "astrometric", None):
-            raise ValueError(f"timing_model={timing_model!r} must be 'spin', 'astrometric' or None")
-        if self._wn is None:
-            raise ValueError("the likelihood needs measurement noise (set_white_noise): without it the noise covariance is singular")
-        gw_lA = None
-        if gwb_auto is None:
-            gw_lA = float(self._gw["A"]) if self._gw is not None else None
-        elif gwb_auto is False:
-            pass
-        elif isinstance(gwb_auto, (bool, np.bool_)):
-            raise ValueError("gwb_auto: None, a log10 amplitude, or False")
-        else:
-            gw_lA = float(gwb_auto)
+        check_components(components)
+        check_timing_model(timing_model)
+        self._stats_need_noise("the likelihood")
+        gw_lA = self._stats_gwb_auto(gwb_auto)
         K_rn = 2 * self._rn["components"] if self._rn is not None else 0
         if K_rn + 2 * int(components) > _lib.LNL_KMAX:
             raise ValueError(f"K = {K_rn} red-noise columns + {2 * int(components)} common-process columns exceeds the kernel limit of "
                              f"{_lib.LNL_KMAX}")
-        if not self._prepared:
-            self.prepare()
-        from .simulate import timing_design_matrix
-        P = self.P
-        toas = [m * 86400.0 for m in self.mjd]
-        wa, wb = self.d_wn_a.cpu().numpy(), self.d_wn_b.cpu().numpy()
-        sigma2 = [wa[self.off[a]:self.off[a + 1]] ** 2 + wb[self.off[a]:self.off[a + 1]] ** 2 for a in range(P)]
-        epoch_of = ecorr = None
-        if self._ec is not None:
-            epoch_of, ecorr = self.epoch_of, self.ecorrvec
-        F_rn = [self._rn_basis_host(a) for a in range(P)] if self.plan.rn_k else None
-        M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
+        toas, sigma2, epoch_of, ecorr, F_rn, _, M = self._stats_noise_model(timing_model)
         if M is not None and max(x.shape[1] for x in M) > _lib.LNL_MMAX:
             raise ValueError(f"the timing model has more than {_lib.LNL_MMAX} columns")
         plan = ost.prepare_lnl(toas, sigma2, components=int(components), epoch_of=epoch_of, ecorr=ecorr, F_rn=F_rn, M=M)
@@ -84,12 +62,7 @@ class LikelihoodMixin:
         return ost.theta_grid(P=self.P, **axes)
 
     def _lnl_state(self, what):
-        st = getattr(self, "_lnl", None)
-        if st is None:
-            raise ValueError(f"{what}: the likelihood is not prepared (prepare_likelihood first)")
-        if not self._prepared or st["engine_plan"] is not self.plan:
-            raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_likelihood(): call it again")
-        return st
+        return self._stats_state("_lnl", "the likelihood", "prepare_likelihood", what)
 
     def _lnl_check_grid(self, st, grid):
         """(theta, G): the grid validated as G noise models (_hyper.check_theta_os with G in place of R), host only.  cw_* keys are
@@ -113,7 +86,7 @@ class LikelihoodMixin:
     def _lnl_grid_device(self, st, th, G):
         """contiguous float64 device tensors of the grid as pta_os_matched_prior reads them (the matched OS's rules: keys not given are
         filled with the configured red noise / the prepared common process, pulsars without red noise get NaN amplitudes)"""
-        return self._os_matched_theta({"matched": {"gw": st["gw"], "K_rn": st["K_rn"]}}, th, G, "log_likelihood")
+        return self._stats_theta_device(st["gw"], st["K_rn"], th, G)
 
     def _lnl_chunks(self, st, R, G, per_pulsar, with_rows, chunk=None):
         """(realisations, grid points) per launch sequence: b, the operators (P K^2 8 bytes per grid point) and ln det of a grid chunk,
@@ -150,23 +123,18 @@ class LikelihoodMixin:
             ws = st["ws"] = dict(Rc=Rc, Gc=Gc, q=dv.empty((Rc, P * Kt)), r0=dv.empty((Rc, P)), b=dv.empty((Gc, P * K)), Lt=dv.empty((Gc, P * K * K)),
                                  logdet=dv.empty((Gc, P)), lp=dv.empty((Gc * P * Rc,)) if need_lp else None)
             out["factored"] = None
-        s = dv.stream_ptr()
-        blk = 64                                   # PTA_OS_CMAX operator rows per pta_os_project call
-        for k0 in range(0, Kt, blk):
-            _lib.call("pta_os_project", ctypes.c_void_p(st["Vt"].data_ptr() + 8 * k0 * self.n_toa), self.n_toa, min(blk, Kt - k0), dv.ptr(st["off"]), P,
-                      ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n, ctypes.c_void_p(ws["q"].data_ptr() + 8 * P * k0), P * Kt, s)
+        s, blk = dv.stream_ptr(), _lib.OS_CMAX
+        self._stats_project(st["Vt"], Kt, st["off"], rows, n, ws["q"])
         _lib.call("pta_lnl_quad", ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n, dv.ptr(st["off"]), P, dv.ptr(st["dinv"]), dv.ptr(st["psr_ep"]),
                   dv.ptr(st["ep_ptr"]), dv.ptr(st["ep_idx"]), dv.ptr(st["ep_g"]), dv.ptr(ws["q"]), P * Kt, blk, K, m, dv.ptr(st["Ht"]), self.n_toa, dv.ptr(ws["r0"]), s)
         hy = self._hyper_tables() if K_rn else {}
-
-        def at(x, g0, per_row):
-            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * g0 * per_row)
+        at = dv.row_ptr
         for g0 in range(0, G, Gc):
             ng = min(Gc, G - g0)
             if out["factored"] != (g0, ng):         # one grid chunk in all: its factors serve every realisation chunk of the call
                 _lib.call("pta_os_matched_prior", ng, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
-                          dv.ptr(st["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], g0, P), at(dev["rn_gamma"], g0, P), st["T"],
-                          at(dev["gw_log10_A"], g0, 1), at(dev["gw_gamma"], g0, 1), dv.ptr(st["s"]), dv.ptr(ws["b"]), s)
+                          dv.ptr(st["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], g0), at(dev["rn_gamma"], g0), st["T"],
+                          at(dev["gw_log10_A"], g0), at(dev["gw_gamma"], g0), dv.ptr(st["s"]), dv.ptr(ws["b"]), s)
                 _lib.call("pta_lnl_factor", dv.ptr(st["A"]), P, K, C, ng, dv.ptr(ws["b"]), dv.ptr(ws["Lt"]), dv.ptr(ws["logdet"]), s)
                 out["factored"] = (g0, ng) if Gc >= G else None
             if out["lp"] is None:
@@ -188,15 +156,9 @@ class LikelihoodMixin:
         {"lnl_pulsar": [R, P, G]} (device tensors, views with free strides); lnl is the sum of lnl_pulsar over the pulsars in
         ascending order.  G and R are cut into chunks that keep the workspace within workspace_bytes."""
         st = self._lnl_state("log_likelihood")
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
-            raise ValueError("rows must be a float64 device tensor")
-        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
-        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
-            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
+        R = self._stats_check_rows(rows)
         th, G = self._lnl_check_grid(st, grid)
         dev = self._lnl_grid_device(st, th, G)
-        R = int(rows.shape[0])
         out = self._lnl_out(R, G, per_pulsar)
         Rc, Gc = self._lnl_chunks(st, R, G, per_pulsar, with_rows=False)
         for lo in range(0, R, Rc):
@@ -216,23 +178,7 @@ class LikelihoodMixin:
         hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
         dev = self._lnl_grid_device(st, th, G)
         Rc, Gc = self._lnl_chunks(st, R, G, per_pulsar, with_rows=True, chunk=chunk)
-        buf = getattr(self, "_lnl_rows", None)
-        if buf is None or buf.shape[0] < Rc:
-            self._lnl_rows = None
-            buf = self._lnl_rows = dv.empty((Rc, self.n_toa))
         out = self._lnl_out(R, G, per_pulsar)
-
-        def rows_of(part, lo, n):
-            return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
-        for lo in range(0, R, Rc):
-            n = min(Rc, R - lo)
-            rows = buf[:n]
-            if td:
-                self.generate_td(n, r0=r0 + lo, out=rows)
-                if cw:
-                    self._cw_apply(rows_of(cw, lo, n), n, rows)
-            else:
-                self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
-            self._lnl_state("generate_lnl")     # generate_td / generate may have (re)prepared the engine
+        for lo, n, rows in self._stats_generate_chunks(lambda: self._lnl_state("generate_lnl"), R, r0, hyper, cw, td, Rc):
             self._lnl_launch(rows, n, lo, dev, Rc, Gc, out)
         return self._lnl_result(out)

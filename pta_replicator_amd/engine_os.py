@@ -25,18 +25,21 @@ with sigma (and sigma_pair) per realisation.
 power of every Fourier bin per ORF, a2 = F^-1 b ("full") or b_k / F_kk ("narrowband"), without a spectral shape.  The front is the
 same (pta_os_project, or project / prior / solve with theta); the pair stage is pta_os_pairs_pf (F fixed, its inverse prepared on the
 host at the first call) or pta_os_matched_pairs_pf (F accumulated and solved per realisation in LDS).
+
+The argument checks, the host noise model, the rows and state checks, theta on the device, the blocked projection and the chunked
+generation loop with its rows buffer are engine_stats.StatisticsMixin's, shared with the likelihood and the F-statistic.
 """
 import ctypes
 
 import numpy as np
-import torch
 
 from . import _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from ._position import ra_dec
+from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 
-class OptimalStatisticMixin:
+class OptimalStatisticMixin(StatisticsMixin):
     def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None, matched=False):
         """W, Z, den and ORF weights of the array under the configured noise model (white noise + ECORR + red noise, optionally the
         GWB auto-term), uploaded once.
@@ -46,10 +49,8 @@ class OptimalStatisticMixin:
         gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False = off.
         matched: also prepare the OS under per-realisation noise parameters (optimal_statistic(theta=...), generate_os(matched=True)):
         K = red-noise columns + 2 n_f <= 128."""
-        if isinstance(components, bool) or not isinstance(components, (int, np.integer)) or not 1 <= int(components) <= 32:
-            raise ValueError(f"components={components!r}: an integer 1 .. 32 (2 n_f <= 64 columns)")
-        if timing_model not in ("spin", "astrometric", None):
-            raise ValueError(f"timing_model={timing_model!r} must be 'spin', 'astrometric' or None")
+        check_components(components)
+        check_timing_model(timing_model)
         orfs = tuple(orfs) if not isinstance(orfs, str) else (orfs,)
         if not 1 <= len(orfs) <= 8:
             raise ValueError(f"{len(orfs)} ORFs: one call evaluates 1 .. 8")
@@ -60,36 +61,14 @@ class OptimalStatisticMixin:
                 raise ValueError(f"a user ORF must be a finite [{self.P}, {self.P}] array, got shape {np.shape(o)}")
         if self.P < 2:
             raise ValueError("the cross-correlation OS needs at least two pulsars")
-        if self._wn is None:
-            raise ValueError("the OS needs measurement noise (set_white_noise): without it the noise covariance is singular")
-        gw_lA = None                       # log10 amplitude of the GWB auto-term, None = no auto-term
-        if gwb_auto is None:
-            gw_lA = float(self._gw["A"]) if self._gw is not None else None
-        elif gwb_auto is False:
-            pass
-        elif isinstance(gwb_auto, (bool, np.bool_)):
-            raise ValueError("gwb_auto: None, a log10 amplitude, or False")
-        else:
-            gw_lA = float(gwb_auto)
+        self._stats_need_noise("the OS")
+        gw_lA = self._stats_gwb_auto(gwb_auto)
         amp2 = 0.0 if gw_lA is None else 10.0 ** (2 * gw_lA)
         K_rn = 2 * self._rn["components"] if self._rn is not None else 0
         if matched and K_rn + 2 * int(components) > _lib.OSM_KMAX:
             raise ValueError(f"matched=True: K = {K_rn} red-noise columns + {2 * int(components)} OS columns exceeds the kernel limit of "
                              f"{_lib.OSM_KMAX}")
-        if not self._prepared:
-            self.prepare()
-        from .simulate import timing_design_matrix
-        P = self.P
-        toas = [m * 86400.0 for m in self.mjd]
-        wa, wb = self.d_wn_a.cpu().numpy(), self.d_wn_b.cpu().numpy()
-        sigma2 = [wa[self.off[a]:self.off[a + 1]] ** 2 + wb[self.off[a]:self.off[a + 1]] ** 2 for a in range(P)]
-        epoch_of = ecorr = F_rn = phi_rn = None
-        if self._ec is not None:
-            epoch_of, ecorr = self.epoch_of, self.ecorrvec
-        if self.plan.rn_k:
-            F_rn = [self._rn_basis_host(a) for a in range(P)]
-            phi_rn = [self.rn_amp[a] ** 2 for a in range(P)]
-        M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
+        toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
         pos = []
         for p in self.psrs:
             ra, dec = ra_dec(p, default=(0.0, 0.0))
@@ -102,8 +81,7 @@ class OptimalStatisticMixin:
                         zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None, matched=None)
         if matched:
             mp = ost.prepare_matched(toas, sigma2, np.array(pos), components=int(components), gamma=float(gamma), orfs=orfs,
-                                     epoch_of=epoch_of, ecorr=ecorr, F_rn=[self._rn_basis_host(a) for a in range(P)] if self.plan.rn_k else None,
-                                     M=M)
+                                     epoch_of=epoch_of, ecorr=ecorr, F_rn=F_rn, M=M)
             m = dict(plan=mp, K=mp.K, K_rn=mp.K_rn, nz=mp.C * (mp.C + 1) // 2, Vt=dv.f64(mp.Vt()), A=dv.f64(mp.A), s=dv.f64(mp.s), S=dv.f64(mp.S),
                      G=dv.f64(mp.G), G2=dv.f64(mp.G ** 2), T=mp.T, gw=None if gw_lA is None else (gw_lA, float(gamma)), ws=None, rn_phi=None)
             if mp.K_rn:
@@ -111,24 +89,8 @@ class OptimalStatisticMixin:
             self._os["matched"] = m
         return self
 
-    def _rn_basis_host(self, a):
-        """the red-noise basis [N_a, K] prepare() put on the device (pta_rn_basis: sin / cos of 2 pi f t per mode, t = TDB seconds;
-        libstempo convention: cos / sin of t - t[0])."""
-        t = self.tdb_s[a]
-        f = self.rn_freqs[a]
-        lib_conv = self._rn["libstempo"]
-        arg = 2 * np.pi * ((t - t[0]) if lib_conv else t)[:, None] * f[None, :]
-        F = np.empty((len(t), 2 * len(f)))
-        F[:, 0::2], F[:, 1::2] = (np.cos(arg), np.sin(arg)) if lib_conv else (np.sin(arg), np.cos(arg))
-        return F
-
     def _os_state(self, what):
-        st = getattr(self, "_os", None)
-        if st is None:
-            raise ValueError(f"{what}: the optimal statistic is not prepared (prepare_optimal_statistic first)")
-        if not self._prepared or st["engine_plan"] is not self.plan:
-            raise ValueError(f"{what}: the engine was re-configured or re-prepared since prepare_optimal_statistic(): call it again")
-        return st
+        return self._stats_state("_os", "the optimal statistic", "prepare_optimal_statistic", what)
 
     def optimal_statistic(self, rows, pairs=False, theta=None):
         """OS of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
@@ -142,7 +104,7 @@ class OptimalStatisticMixin:
         configured with a userSpec, the statistic prepared with the GW auto-term) the GW auto-term of row r follows its own spectrum;
         the broadband template S(gamma) stays the prepared one."""
         st = self._os_state("optimal_statistic")
-        R = self._os_check_rows(rows)
+        R = self._stats_check_rows(rows)
         if theta is not None:
             dev = self._os_matched_theta(st, theta, R, "optimal_statistic")
             out = self._os_matched_out(st, R, pairs)
@@ -153,15 +115,6 @@ class OptimalStatisticMixin:
         out = {"A2": dv.empty((R, st["n_orf"])), "rho": dv.empty((R, len(st["plan"].den))) if pairs else None}
         self._os_launch(rows, R, out["A2"], out["rho"])
         return self._os_result(st, out["A2"], out["rho"])
-
-    def _os_check_rows(self, rows):
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.device.type != "cuda":
-            raise ValueError("rows must be a float64 device tensor")
-        if rows.dim() != 2 or rows.shape[1] != self.n_toa or rows.shape[0] < 1:
-            raise ValueError(f"rows must be [R >= 1, {self.n_toa}], got {tuple(rows.shape)}")
-        if rows.stride(1) != 1 or rows.stride(0) < self.n_toa:
-            raise ValueError(f"rows must have unit column stride and row stride >= {self.n_toa}, got strides {rows.stride()}")
-        return int(rows.shape[0])
 
     def _os_result(self, st, A2, rho):
         res = {"A2": A2, "snr": A2 / st["sigma"], "sigma": st["sigma"], "names": list(st["names"])}
@@ -175,10 +128,8 @@ class OptimalStatisticMixin:
         P, C = self.P, st["C"]
         if st["Y"] is None or st["Y"].shape[0] < R:
             st["Y"] = dv.empty((R, P * C))
-        Y = st["Y"]
-        _lib.call("pta_os_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), R,
-                  dv.ptr(Y), P * C, dv.stream_ptr())
-        return Y
+        self._stats_project(st["Wt"], C, st["off"], rows, R, st["Y"])
+        return st["Y"]
 
     def _os_launch(self, rows, R, A2, rho):
         """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream"""
@@ -225,63 +176,22 @@ class OptimalStatisticMixin:
         return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho)
 
     def _os_generate_chunks(self, what, st, R, r0, hyper, cw, td, chunk):
-        """realisations r0 .. r0+R-1 generated chunk by chunk into the reused [chunk, n_toa] buffer (the chunk cut so that rows and Y
-        stay within workspace_bytes): yields (lo, n, rows [n, n_toa]) per chunk"""
+        """_stats_generate_chunks with the chunk cut so that rows and Y stay within workspace_bytes"""
         per_real = 8 * (self.n_toa + self.P * st["C"])
         chunk = max(1, min(chunk, R, int(self.workspace_bytes) // per_real))
-        buf = getattr(self, "_os_rows", None)
-        if buf is None or buf.shape[0] < chunk:
-            self._os_rows = None
-            buf = self._os_rows = dv.empty((chunk, self.n_toa))
-
-        def rows_of(part, lo, n):
-            return None if part is None else {k: v[lo:lo + n] for k, v in part.items()}
-        for lo in range(0, R, chunk):
-            n = min(chunk, R - lo)
-            rows = buf[:n]
-            if td:
-                self.generate_td(n, r0=r0 + lo, out=rows)
-                if cw:
-                    self._cw_apply(rows_of(cw, lo, n), n, rows)
-            else:
-                self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
-            self._os_state(what)     # generate_td / generate may have (re)prepared the engine
-            yield lo, n, rows
+        return self._stats_generate_chunks(lambda: self._os_state(what), R, r0, hyper, cw, td, chunk)
 
     # ---- the OS under per-realisation noise parameters ----
     def _os_matched_theta(self, st, theta, R, what):
-        """theta validated as the OS's noise model (_hyper.check_theta_os) -> contiguous float64 device tensors {rn_log10_A, rn_gamma:
-        [R, P] or None (every pulsar as configured), gw_log10_A, gw_gamma: [R] or None (no GW auto-term)}; keys not given are filled
-        with the configured red noise / the prepared auto-term, pulsars configured without red noise get NaN amplitudes.  With
+        """theta validated as the OS's noise model (_hyper.check_theta_os) -> the device tensors of _stats_theta_device.  With
         gwb_log10_hc [R, M] (an engine configured with a userSpec; needs the GW auto-term) the GW columns of realisation r are weighted
-        with its own spectrum instead: gw_log10_hc [R, M], columns in ascending node frequency (pta_os_matched_prior_spec).  The
-        broadband template S(gamma) of the statistic stays the prepared one."""
+        with its own spectrum (pta_os_matched_prior_spec) instead of (gwb_log10_A, gwb_gamma).  The broadband template S(gamma) of the
+        statistic stays the prepared one."""
         m = st["matched"]
         if m is None:
             raise ValueError(f"{what}: theta needs prepare_optimal_statistic(matched=True)")
         th = _hyper.check_theta_os(theta, R, self.P, self._rn, m["gw"] is not None, gw=self._gw)
-        gpu = dv.require_gpu()
-
-        def f64(x):
-            if hasattr(x, "data_ptr"):
-                return x.to(device=gpu, dtype=torch.float64).contiguous()
-            return dv.f64(np.ascontiguousarray(x, dtype=np.float64))
-        dev = dict.fromkeys(("rn_log10_A", "rn_gamma", "gw_log10_A", "gw_gamma", "gw_log10_hc"))
-        if _hyper.SPEC_KEY in th:
-            order, _ = _hyper.spec_nodes(self._gw["userSpec"])
-            y = f64(th[_hyper.SPEC_KEY])
-            dev["gw_log10_hc"] = y if np.array_equal(order, np.arange(len(order))) else y.index_select(1, dv.i64(order)).contiguous()
-        elif m["gw"] is not None:
-            for k, key, conf in (("gw_log10_A", "gwb_log10_A", m["gw"][0]), ("gw_gamma", "gwb_gamma", m["gw"][1])):
-                dev[k] = f64(th[key]) if key in th else torch.full((R,), conf, dtype=torch.float64, device=gpu)
-        if any(k in th for k in _hyper.RN_KEYS) and m["K_rn"]:
-            for k, c in zip(_hyper.RN_KEYS, _hyper.configured_rn(self._rn)):
-                dev[k] = f64(th[k]) if k in th else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
-            none = self._hyper_tables()["rn_none"]
-            if len(none):
-                dev["rn_log10_A"] = dev["rn_log10_A"].clone()
-                dev["rn_log10_A"][:, none] = float("nan")
-        return dev
+        return self._stats_theta_device(m["gw"], m["K_rn"], th, R)
 
     def _os_matched_chunk(self, st, R, with_rows):
         """realisations per launch sequence: q and b [P, K], X [P, C], Z [P, C (C + 1) / 2] (and the generated rows) of a chunk within
@@ -312,25 +222,20 @@ class OptimalStatisticMixin:
             m["ws"] = None
             ws = m["ws"] = dict(n=n, q=dv.empty((n, P * K)), b=dv.empty((n, P * K)), X=dv.empty((n, P * C)), Z=dv.empty((n, P * nz)))
         s = dv.stream_ptr()
-        blk = 64                                   # PTA_OS_CMAX columns per pta_os_project call
-        for k0 in range(0, K, blk):
-            _lib.call("pta_os_project", ctypes.c_void_p(m["Vt"].data_ptr() + 8 * k0 * self.n_toa), self.n_toa, min(blk, K - k0), dv.ptr(st["off"]), P,
-                      ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n, ctypes.c_void_p(ws["q"].data_ptr() + 8 * P * k0), P * K, s)
-
-        def at(x, per_row):
-            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * per_row)
+        self._stats_project(m["Vt"], K, st["off"], rows, n, ws["q"])
+        at = dv.row_ptr
         hy = self._hyper_tables() if K_rn else {}
         if dev["gw_log10_hc"] is not None:
             sp = self._os_matched_spec_tables(m, C)
             M = dev["gw_log10_hc"].shape[1]
             _lib.call("pta_os_matched_prior_spec", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
-                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], dv.ptr(sp[0]), dv.ptr(sp[1]),
-                      dv.ptr(sp[2]), M, at(dev["gw_log10_hc"], M), M, dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
+                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], lo), at(dev["rn_gamma"], lo), m["T"], dv.ptr(sp[0]), dv.ptr(sp[1]),
+                      dv.ptr(sp[2]), M, at(dev["gw_log10_hc"], lo), M, dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
         else:
             _lib.call("pta_os_matched_prior", n, P, K_rn, C, dv.ptr(hy["rn_f"]) if K_rn else None, dv.ptr(hy["rn_tspan"]) if K_rn else None,
-                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], P), at(dev["rn_gamma"], P), m["T"], at(dev["gw_log10_A"], 1),
-                      at(dev["gw_gamma"], 1), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
-        _lib.call("pta_os_matched_solve", dv.ptr(m["A"]), P, K, C, n, dv.ptr(ws["b"]), dv.ptr(ws["q"]), P * K, blk, dv.ptr(m["S"]), dv.ptr(m["s"]),
+                      dv.ptr(m["rn_phi"]) if K_rn else None, at(dev["rn_log10_A"], lo), at(dev["rn_gamma"], lo), m["T"], at(dev["gw_log10_A"], lo),
+                      at(dev["gw_gamma"], lo), dv.ptr(m["s"]), dv.ptr(ws["b"]), s)
+        _lib.call("pta_os_matched_solve", dv.ptr(m["A"]), P, K, C, n, dv.ptr(ws["b"]), dv.ptr(ws["q"]), P * K, _lib.OS_CMAX, dv.ptr(m["S"]), dv.ptr(m["s"]),
                   dv.ptr(ws["X"]), dv.ptr(ws["Z"]), s)
         self._os_theta_keep = dev   # the launches above read these buffers asynchronously
         return ws
@@ -353,12 +258,10 @@ class OptimalStatisticMixin:
         ws = self._os_matched_front(rows, n, dev, lo)
         npairs = len(st["plan"].den)
         A2, sg, rho, sp = out["A2"], out["sigma"], out["rho"], out["sigma_pair"]
-
-        def row(x):
-            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * x.stride(0))
+        row = dv.row_ptr
         _lib.call("pta_os_matched_pairs", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), self.P, st["C"], n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
-                  dv.ptr(m["G2"]), st["n_orf"], row(A2), A2.stride(0), row(sg), sg.stride(0), row(rho), row(sp), rho.stride(0) if rho is not None else 0,
-                  dv.stream_ptr())
+                  dv.ptr(m["G2"]), st["n_orf"], row(A2, lo), A2.stride(0), row(sg, lo), sg.stride(0), row(rho, lo), row(sp, lo),
+                  rho.stride(0) if rho is not None else 0, dv.stream_ptr())
 
     # ---- the per-frequency OS: the spectrum per realisation ----
     def _os_spectrum_check(self, what, st, mode, theta, matched):
@@ -405,21 +308,19 @@ class OptimalStatisticMixin:
         st = self._os
         P, C, n_orf = self.P, st["C"], st["n_orf"]
         npairs = len(st["plan"].den)
-
-        def row(x):
-            return None if x is None else ctypes.c_void_p(x.data_ptr() + 8 * lo * x.stride(0))
+        row = dv.row_ptr
         a2 = out["a2"]
         if dev is None:
             sp = self._os_spectrum_state(st)
             Y = self._os_project(rows, n)
             _lib.call("pta_os_pairs_pf", dv.ptr(Y), P * C, P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(sp["G"]), n_orf,
-                      dv.ptr(sp["op"][mode]), mode, row(a2), a2.stride(0), dv.stream_ptr())
+                      dv.ptr(sp["op"][mode]), mode, row(a2, lo), a2.stride(0), dv.stream_ptr())
             return
         m = st["matched"]
         ws = self._os_matched_front(rows, n, dev, lo)
         sg, fi = out["sigma"], out["fisher"]
         _lib.call("pta_os_matched_pairs_pf", dv.ptr(ws["X"]), dv.ptr(ws["Z"]), P, C, n, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(m["G"]),
-                  dv.ptr(m["G2"]), n_orf, mode, row(a2), a2.stride(0), row(sg), sg.stride(0), row(fi), fi.stride(0) if fi is not None else 0,
+                  dv.ptr(m["G2"]), n_orf, mode, row(a2, lo), a2.stride(0), row(sg, lo), sg.stride(0), row(fi, lo), fi.stride(0) if fi is not None else 0,
                   dv.stream_ptr())
 
     def _os_spectrum_result(self, st, out, mode, matched, fisher):
@@ -449,7 +350,7 @@ class OptimalStatisticMixin:
         what = "optimal_statistic_spectrum"
         st = self._os_state(what)
         mode = self._os_spectrum_check(what, st, mode, theta, theta is not None)
-        R = self._os_check_rows(rows)
+        R = self._stats_check_rows(rows)
         matched = theta is not None
         if not matched:
             self._os_spectrum_state(st)

@@ -158,9 +158,7 @@ def prepare(toas_s, sigma2, freqs, phat=None, sky=None, epoch_of=None, ecorr=Non
     if sky is not None and P < 2:
         raise ValueError("the coherent Fe statistic needs at least two pulsars (M_js is singular for one); Fp alone works without a sky "
                          "grid")
-
-    def pick(x, a):
-        return None if x is None else x[a]
+    pick = ost.pick
     W, G, white = [], np.zeros((P, J, 2, 2)), np.zeros((P, J, 2))
     ones = np.ones(2 * J)
     for a in range(P):

@@ -145,18 +145,7 @@ def pulsar_operator(sigma2, F, S, epoch_of=None, ecorr=None, F_rn=None, phi_rn=N
     nf2 = F.shape[1]
     PF = CiG[:, :nf2]
     if M is not None:
-        CiM = CiG[:, nf2:]
-        A = M.T @ CiM
-        A = 0.5 * (A + A.T)
-        dg = np.sqrt(np.abs(np.diag(A)))
-        if not np.all(dg > 0):
-            raise ValueError("M^T C^-1 M is singular: a timing-model column vanishes on this pulsar's TOAs")
-        An = A / dg[:, None] / dg[None, :]
-        ev = np.linalg.eigvalsh(An)
-        if ev[0] <= 1e-12 * ev[-1]:
-            raise ValueError(f"M^T C^-1 M is singular (condition {ev[-1] / max(ev[0], 1e-300):.3g}): the pulsar's TOAs do not "
-                             "constrain its timing model")
-        PF = PF - CiM @ (np.linalg.solve(An, (M.T @ PF) / dg[:, None]) / dg[:, None])
+        PF = timing_projection(M, CiG[:, nf2:], PF, "C^-1")[0]
     rs = np.sqrt(S)
     W = (PF * rs[None, :]).T / s
     Z = rs[:, None] * (F.T @ PF) * rs[None, :] / s
@@ -165,6 +154,47 @@ def pulsar_operator(sigma2, F, S, epoch_of=None, ecorr=None, F_rn=None, phi_rn=N
 
 def _cho_solve(L, B):
     return np.linalg.solve(L.T, np.linalg.solve(L, B))
+
+
+def timing_projection(M, CiM, X, inv):
+    """(X - C^-1 M (M^T C^-1 M)^-1 M^T X, Bn, dg): the timing model M [N, m] projected out of X = C^-1 Y [N, k], given CiM = C^-1 M;
+    Bn = M^T C^-1 M over dg dg^T (unit diagonal), dg the square roots of its diagonal.  A singular M^T C^-1 M is refused; inv names
+    the inverse in the message ("C^-1", or "N^-1" where C holds white noise and ECORR only)."""
+    B = M.T @ CiM
+    B = 0.5 * (B + B.T)
+    dg = np.sqrt(np.abs(np.diag(B)))
+    if not np.all(dg > 0):
+        raise ValueError(f"M^T {inv} M is singular: a timing-model column vanishes on this pulsar's TOAs")
+    Bn = B / dg[:, None] / dg[None, :]
+    ev = np.linalg.eigvalsh(Bn)
+    if ev[0] <= 1e-12 * ev[-1]:
+        raise ValueError(f"M^T {inv} M is singular (condition {ev[-1] / max(ev[0], 1e-300):.3g}): the pulsar's TOAs do not "
+                         "constrain its timing model")
+    return X - CiM @ (np.linalg.solve(Bn, (M.T @ X) / dg[:, None]) / dg[:, None]), Bn, dg
+
+
+def pick(x, a):
+    """entry a of a per-pulsar list, None where the list itself is None"""
+    return None if x is None else x[a]
+
+
+def array_basis(toas_s, components, T=None, F_rn=None):
+    """(nf, T, K_rn, U) - the prelude of prepare / prepare_matched / prepare_lnl: components checked, T = the span of the whole array
+    where None, K_rn = the widest red-noise basis of F_rn (0 for None) held to K_rn + 2 nf <= MATCHED_KMAX, and per pulsar
+    U = [F_rn | F] [N_a, K_rn + 2 nf] (a zero block where a pulsar has no red-noise basis)."""
+    if not 1 <= int(components) <= 32:
+        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
+    nf = int(components)
+    if T is None:
+        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
+    K_rn = 0 if F_rn is None else max([0] + [f.shape[1] for f in F_rn if f is not None])
+    if K_rn + 2 * nf > MATCHED_KMAX:
+        raise ValueError(f"K = K_rn + 2 n_f = {K_rn} + {2 * nf} exceeds the limit of {MATCHED_KMAX} columns per pulsar")
+    U = []
+    for a, t in enumerate(toas_s):
+        Fr = pick(F_rn, a)
+        U.append(np.concatenate([np.zeros((len(t), K_rn)) if Fr is None else Fr, fourier_basis(t, nf, T)], axis=1))
+    return nf, T, K_rn, U
 
 
 class OSPlan:
@@ -198,23 +228,14 @@ def prepare(toas_s, sigma2, pos, components=14, gamma=13. / 3., orfs=ORF_NAMES, 
     """OSPlan of an array: per-pulsar lists toas_s [s], sigma2, epoch_of / ecorr (entries None = no ECORR), F_rn / phi_rn (None = no
     red noise), M (None = no timing model); pos [P, 3] unit vectors; T = span of the whole array (default: from toas_s)."""
     P = len(toas_s)
-    if not 1 <= int(components) <= 32:
-        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
-    nf = int(components)
-    if T is None:
-        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
+    nf, T, _, F = array_basis(toas_s, components, T)
     S = unit_spectrum(nf, T, gamma)
     pair_a, pair_b, cz = pair_geometry(pos)
     names, G = orf_weights(orfs, pair_a, pair_b, cz, P)
-
-    def pick(x, a):
-        return None if x is None else x[a]
     W, Z = [], np.zeros((P, 2 * nf, 2 * nf))
     for a in range(P):
-        F = fourier_basis(toas_s[a], nf, T)
-        Wa, Za = pulsar_operator(sigma2[a], F, S, pick(epoch_of, a), pick(ecorr, a), pick(F_rn, a), pick(phi_rn, a), gw_amp2, pick(M, a))
+        Wa, Z[a] = pulsar_operator(sigma2[a], F[a], S, pick(epoch_of, a), pick(ecorr, a), pick(F_rn, a), pick(phi_rn, a), gw_amp2, pick(M, a))
         W.append(Wa)
-        Z[a] = Za
     return OSPlan(W, Z, pair_a, pair_b, cz, names, G, S=S, T=float(T))
 
 
@@ -373,27 +394,24 @@ MATCHED_KMAX = 128   # K = K_rn + C of pta_os_matched_solve (PTA_OSM_KMAX)
 
 def matched_operator(sigma2, U, epoch_of=None, ecorr=None, M=None):
     """(V [K, N], A [K, K], s) of one pulsar: U [N, K] = [F_rn | F]; the other arguments as pulsar_operator's."""
+    return _matched_operator(sigma2, U, epoch_of, ecorr, M)[:3]
+
+
+def _matched_operator(sigma2, U, epoch_of, ecorr, M):
+    """matched_operator's (V, A, s), then what lnl_operator builds on: N'^-1 (_NoiseInverse) and, with a timing model, (N'^-1 M, Bn,
+    dg) of timing_projection (else None)"""
     sigma2 = np.asarray(sigma2, dtype=np.float64)
     if not np.all(sigma2 > 0):
         raise ValueError("white-noise variances must be positive")
     s = float(np.mean(sigma2))
     Ninv = _NoiseInverse(sigma2 / s, epoch_of, None if ecorr is None else np.asarray(ecorr, dtype=np.float64) ** 2 / s)
-    PU = Ninv(U)
+    PU, tm = Ninv(U), None
     if M is not None:
         NiM = Ninv(M)
-        B = M.T @ NiM
-        B = 0.5 * (B + B.T)
-        dg = np.sqrt(np.abs(np.diag(B)))
-        if not np.all(dg > 0):
-            raise ValueError("M^T N^-1 M is singular: a timing-model column vanishes on this pulsar's TOAs")
-        Bn = B / dg[:, None] / dg[None, :]
-        ev = np.linalg.eigvalsh(Bn)
-        if ev[0] <= 1e-12 * ev[-1]:
-            raise ValueError(f"M^T N^-1 M is singular (condition {ev[-1] / max(ev[0], 1e-300):.3g}): the pulsar's TOAs do not "
-                             "constrain its timing model")
-        PU = PU - NiM @ (np.linalg.solve(Bn, (M.T @ PU) / dg[:, None]) / dg[:, None])
+        PU, Bn, dg = timing_projection(M, NiM, PU, "N^-1")
+        tm = (NiM, Bn, dg)
     A = U.T @ PU
-    return np.ascontiguousarray(PU.T), 0.5 * (A + A.T), s
+    return np.ascontiguousarray(PU.T), 0.5 * (A + A.T), s, Ninv, tm
 
 
 class MatchedPlan:
@@ -423,27 +441,13 @@ def prepare_matched(toas_s, sigma2, pos, components=14, gamma=13. / 3., orfs=ORF
     """MatchedPlan of an array; arguments as prepare()'s, without the prior variances (they come per realisation).  F_rn: None (no
     pulsar has red noise: K_rn = 0) or a per-pulsar list of [N_a, K_rn] bases (an entry None = a zero block)."""
     P = len(toas_s)
-    if not 1 <= int(components) <= 32:
-        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
-    nf = int(components)
-    if T is None:
-        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
-    K_rn = 0 if F_rn is None else max([0] + [f.shape[1] for f in F_rn if f is not None])
-    if K_rn + 2 * nf > MATCHED_KMAX:
-        raise ValueError(f"K = K_rn + 2 n_f = {K_rn} + {2 * nf} exceeds the limit of {MATCHED_KMAX} columns per pulsar")
+    nf, T, K_rn, U = array_basis(toas_s, components, T, F_rn)
     S = unit_spectrum(nf, T, gamma)
     pair_a, pair_b, cz = pair_geometry(pos)
     names, G = orf_weights(orfs, pair_a, pair_b, cz, P)
-
-    def pick(x, a):
-        return None if x is None else x[a]
     V, A, s = [], np.zeros((P, K_rn + 2 * nf, K_rn + 2 * nf)), np.zeros(P)
     for a in range(P):
-        F = fourier_basis(toas_s[a], nf, T)
-        Fr = pick(F_rn, a)
-        if Fr is None:
-            Fr = np.zeros((len(toas_s[a]), K_rn))
-        Va, A[a], s[a] = matched_operator(sigma2[a], np.concatenate([Fr, F], axis=1), pick(epoch_of, a), pick(ecorr, a), pick(M, a))
+        Va, A[a], s[a] = matched_operator(sigma2[a], U[a], pick(epoch_of, a), pick(ecorr, a), pick(M, a))
         V.append(Va)
     return MatchedPlan(V, A, s, S, K_rn, pair_a, pair_b, cz, names, G, nf, T)
 
@@ -583,11 +587,10 @@ def lnl_operator(sigma2, U, epoch_of=None, ecorr=None, M=None):
     timing-model rows G; m = 0 without a timing model), Ht [m, N] (H^T, H G r = M beta_hat), dinv [N] = 1 / d, the epoch -> TOA lists ep_ptr [E + 1], ep_idx [sum of
     the epochs' sizes] (TOA indices within the pulsar, epochs in ascending order, TOAs of an epoch in TOA order; E = 0 without
     ECORR), ep_g [E], and the constant c."""
-    V, A, s = matched_operator(sigma2, U, epoch_of, ecorr, M)
-    d = np.asarray(sigma2, dtype=np.float64) / s
+    V, A, s, Ninv, tm = _matched_operator(sigma2, U, epoch_of, ecorr, M)
+    d = Ninv.d
     N = len(d)
     j = None if ecorr is None else np.asarray(ecorr, dtype=np.float64) ** 2 / s
-    Ninv = _NoiseInverse(d, epoch_of, j)
     logdet_N = N * np.log(s) + float(np.sum(np.log(d)))
     ep_ptr, ep_idx, ep_g = np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0)
     if Ninv.ep is not None:
@@ -600,11 +603,8 @@ def lnl_operator(sigma2, U, epoch_of=None, ecorr=None, M=None):
     Gt = Ht = np.zeros((0, N))
     c = logdet_N + (N - m) * np.log(2 * np.pi)
     if m:
-        NiM = Ninv(M)
-        B = M.T @ NiM
-        B = 0.5 * (B + B.T)
-        dg = np.sqrt(np.abs(np.diag(B)))                      # matched_operator has refused a singular B
-        Lb = np.linalg.cholesky(B / dg[:, None] / dg[None, :])
+        NiM, Bn, dg = tm                                      # matched_operator has refused a singular B
+        Lb = np.linalg.cholesky(Bn)
         Gt = np.linalg.solve(Lb, (NiM / dg[None, :]).T)
         Ht = np.linalg.solve(Lb, (M / dg[None, :]).T)
         c += 2 * float(np.sum(np.log(dg))) + 2 * float(np.sum(np.log(np.diag(Lb)))) - m * np.log(s)
@@ -660,25 +660,8 @@ class LnlPlan:
 
 def prepare_lnl(toas_s, sigma2, components=14, epoch_of=None, ecorr=None, F_rn=None, M=None, T=None):
     """LnlPlan of an array; arguments as prepare_matched()'s (no positions and no ORFs: the likelihood is a sum over pulsars)."""
-    P = len(toas_s)
-    if not 1 <= int(components) <= 32:
-        raise ValueError(f"components={components}: 1 .. 32 frequencies (2 n_f <= 64 columns)")
-    nf = int(components)
-    if T is None:
-        T = max(float(np.max(t)) for t in toas_s) - min(float(np.min(t)) for t in toas_s)
-    K_rn = 0 if F_rn is None else max([0] + [f.shape[1] for f in F_rn if f is not None])
-    if K_rn + 2 * nf > MATCHED_KMAX:
-        raise ValueError(f"K = K_rn + 2 n_f = {K_rn} + {2 * nf} exceeds the limit of {MATCHED_KMAX} columns per pulsar")
-
-    def pick(x, a):
-        return None if x is None else x[a]
-    ops = []
-    for a in range(P):
-        F = fourier_basis(toas_s[a], nf, T)
-        Fr = pick(F_rn, a)
-        if Fr is None:
-            Fr = np.zeros((len(toas_s[a]), K_rn))
-        ops.append(lnl_operator(sigma2[a], np.concatenate([Fr, F], axis=1), pick(epoch_of, a), pick(ecorr, a), pick(M, a)))
+    nf, T, K_rn, U = array_basis(toas_s, components, T, F_rn)
+    ops = [lnl_operator(sigma2[a], U[a], pick(epoch_of, a), pick(ecorr, a), pick(M, a)) for a in range(len(U))]
     return LnlPlan(ops, K_rn, nf, T)
 
 
