@@ -34,6 +34,34 @@ def relrms(a, b):
     return float(np.max(np.abs(a - b)) / rms)
 
 
+def host_draws(eng, r):
+    """The dict ReplicaEngine.dump_draws(r) returns, from the NumPy twin of the device's draws alone (oracle/philox_ref.py): no
+    number in it comes from the device."""
+    from oracle import philox_ref as ph
+    fast = bool(eng.rng_fast)
+    d = {}
+    if eng.plan.gw_npts:
+        Nf = eng.grid["Nf"]
+        d["gwb"] = np.stack([np.asarray(z0) + 1j * np.asarray(z1) for z0, z1 in
+                             (ph.normal_pairs(eng.seed, r, ph.stream_id(ph.STREAM_GWB, a), Nf, fast=fast) for a in range(eng.P))])
+    if eng.plan.rn_k:
+        d["rn"] = []
+        for a in range(eng.P):
+            z = np.empty(eng.K)
+            z[0::2], z[1::2] = ph.normal_pairs(eng.seed, r, ph.stream_id(ph.STREAM_RN, a), eng.K // 2, fast=fast)
+            d["rn"].append(z)
+    if eng.plan.wn_a:
+        d["wn"] = [ph.normal_pairs(eng.seed, r, ph.stream_id(ph.STREAM_WN, a), int(eng.counts[a]), fast=fast) for a in range(eng.P)]
+    if eng.plan.ecorr_toa:
+        d["ecorr"] = []
+        for a in range(eng.P):
+            ne = len(eng.ecorrvec[a])
+            z = np.empty(2 * ((ne + 1) // 2))
+            z[0::2], z[1::2] = ph.normal_pairs(eng.seed, r, ph.stream_id(ph.STREAM_ECORR, a), (ne + 1) // 2, fast=fast)
+            d["ecorr"].append(z[:ne])
+    return d
+
+
 def oracle_realisation(po, psrs, noise, draws, components=30, coarsegrain=0.1, gw_gamma=13. / 3.):
     """One realisation of bench.headline_array()-style inputs (per-backend EFAC / t2EQUAD / ECORR, per-pulsar RN, HD GWB)
     through the CPU oracle, on the deviates `draws` (shaped like ReplicaEngine.dump_draws()).  Returns one array per pulsar."""

@@ -9,6 +9,7 @@ import pytest
 from helpers import load
 from oracle import philox_ref
 from oracle import pta_oracle as po
+from synth_reference import box_muller_ld
 
 pytestmark = pytest.mark.gpu
 
@@ -93,11 +94,7 @@ def test_device_deviates_within_a_few_ulp_of_an_80_bit_box_muller(gpu):
     z = dv.empty((2 * npairs,))
     lib.call("pta_rng_fill_normal", seed, real, 1, sid, npairs, 1, dv.ptr(z), None, 2 * npairs, 0, gpu["s"])
     got = z.cpu().numpy()
-    u1, u2 = philox_ref.uniform_pairs(seed, real, sid, npairs)
-    rad = np.sqrt(L(-2) * np.log(u1.astype(L)))
-    q = np.rint(4 * u2); x = (u2.astype(L) - L(0.25) * q.astype(L)) * (L(2) * np.arccos(L(-1)))
-    sr, cr = np.sin(x), np.cos(x); k = q.astype(np.int64) & 3
-    refs = (rad * np.choose(k, [cr, -sr, -cr, sr]), rad * np.choose(k, [sr, cr, -sr, -cr]))
+    refs = box_muller_ld(*philox_ref.uniform_pairs(seed, real, sid, npairs))   # the 80-bit expression: tests/synth_reference.py
     worst = []
     for g, r in zip((got[0::2], got[1::2]), refs):
         e = (np.abs(g.astype(L) - r) / np.spacing(np.abs(r.astype(np.float64))).astype(L)).astype(np.float64)

@@ -6,7 +6,8 @@ clamped lane, a tile less or plus one TOA, a partial realisation group, a counte
 without a kernel, those of the retired prefetch and 3-per-CU instances among them, are refused.
 
 The host guard that sends a plan beyond the 32-bit lane offsets to the per-lane index products needs rn_k ldf 8 >= 2^32 (a design
-matrix of 4 GB): not reachable at a small shape.  The noidx bit of the variant runs the same loads."""
+matrix of 4 GB): tests/test_gpu_synth_direct.py::test_lane_offset_guard runs both sides of it, with a direct call, two or four bins and
+a leading dimension of 2^28 or 2^27, against the host reference.  The noidx bit of the variant runs the same loads."""
 import numpy as np
 import pytest
 

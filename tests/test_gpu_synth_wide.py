@@ -88,3 +88,40 @@ def test_rows_eight_byte_aligned(psrs):
         for variant in (0, 16, 48):
             assert torch.equal(bufs[variant][:, 3:3 + n], ref[:, 3:3 + n]), (R, variant)
             assert bool(torch.isnan(bufs[variant][:, :3]).all()) and bool(torch.isnan(bufs[variant][:, 3 + n:]).all()), (R, variant)
+
+
+@pytest.mark.parametrize("components", [29, 30])
+def test_engine_against_the_oracle_on_host_only_draws(psrs, components):
+    """prepare()'s tables, the kernel and the Philox twin tied together at these shapes with no device-drawn number in the reference:
+    the draws of realisations 2^32 - 3 ... from oracle/philox_ref.py alone equal the dumped ones (to the bound of
+    test_rng_fill_matches_numpy_twin), and generate() agrees with the CPU oracle evaluated on them, per pulsar."""
+    from helpers import host_draws, relrms
+    from oracle import pta_oracle as po
+    eng = _engine(psrs, components)
+    P, R, r0 = len(COUNTS), 17, 2 ** 32 - 3
+    lA, gam = [None] + list(np.linspace(-14.3, -13.4, P - 1)), [None] + list(np.linspace(2.2, 4.4, P - 1))
+    efac, leq, lec = np.linspace(0.8, 1.4, P), np.linspace(-6.9, -6.1, P), np.linspace(-6.8, -6.2, P)
+    grid = po.gwb_grid([float(m.min()) for m in eng.mjd], [float(m.max()) for m in eng.mjd])
+    Mchol = np.linalg.cholesky(po.hd_orf_closed_form(po.psr_locs_equatorial([p.loc for p in psrs])))
+    C = po.gwb_spectrum(grid["f"], grid["dur"], grid["howml"], -14.2, 13. / 3.)
+    quant = [po.quantize(eng.mjd[a], dt=0.1) for a in range(P)]
+    out = eng.generate(R, r0=r0).cpu().numpy()
+    assert out.shape == (R, sum(COUNTS)) and np.all(np.isfinite(out))
+    for r in range(R):
+        d, dev = host_draws(eng, r0 + r), eng.dump_draws(r0 + r)
+        assert d.keys() == dev.keys() == {"gwb", "rn", "wn", "ecorr"}
+        assert d["gwb"].shape == dev["gwb"].shape and np.max(np.abs(d["gwb"] - dev["gwb"])) < 1e-13
+        for a in range(P):
+            assert d["rn"][a].shape == dev["rn"][a].shape and np.max(np.abs(d["rn"][a] - dev["rn"][a])) < 1e-13
+            assert d["ecorr"][a].shape == dev["ecorr"][a].shape and np.max(np.abs(d["ecorr"][a] - dev["ecorr"][a])) < 1e-13
+            for k in range(2):
+                assert d["wn"][a][k].shape == dev["wn"][a][k].shape and np.max(np.abs(d["wn"][a][k] - dev["wn"][a][k])) < 1e-13
+        res_gw, _ = po.gwb_dt(grid, Mchol, d["gwb"], C, [m * 86400 for m in eng.mjd])
+        for a in range(P):
+            n = COUNTS[a]
+            ref = po.measurement_noise_dt(eng.sigma_s[a], np.ones(n) * efac[a], np.ones(n) * 10 ** leq[a], *d["wn"][a])
+            epoch_of, ne, first, _ = quant[a]
+            ref = ref + po.jitter_dt(epoch_of, po.jitter_ecorr_vector(ne, first, lec[a]), d["ecorr"][a]) + res_gw[a]
+            if lA[a] is not None:
+                ref = ref + po.red_noise_dt(psrs[a].toas.table["tdbld"], lA[a], gam[a], d["rn"][a], components=components)
+            assert relrms(out[r, eng.off[a]:eng.off[a + 1]], ref) < 1e-10, (components, r, a)
