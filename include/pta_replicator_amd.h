@@ -52,7 +52,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform.  Field 1: the
  * nodes of a per-realisation GWB spectrum, pair j = node j; pta_hyper_uniform_field),
  * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform.  In a catalogue the
- * field is the source index s, pta_cw_catalog_uniform). */
+ * field is the source index s, pta_cw_catalog_uniform),
+ * 9 BWM (pulsar field 0: per-realisation burst-with-memory labels, pair j = label column, uniform u2; pta_bwm_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -544,6 +545,34 @@ int pta_engine_cw_catalog_params(const pta_cw_catalog_engine *cw_host, int R, vo
 int pta_engine_cw_catalog_add(const pta_engine_plan *plan_host, const pta_cw_catalog_engine *cw_host, int R, double *out, int64_t ld_out,
                               int accumulate, void *stream);
 
+/* ---------------------------------------------------------------- one burst with memory per realisation (ABI 8, additive) */
+/* out[r * 5 + j] = lo[j] + (hi[j] - lo[j]) u (one fma), u = uniform u2 of pair j of stream (BWM = 9, 0), realisation r0 + r.  Columns j:
+ * 0 cos_gwtheta, 1 gwphi, 2 log10_h, 3 psi, 4 t0_mjd.  lo / hi: device [5].                                                   */
+#define PTA_BWM_NSRC 5
+int pta_bwm_uniform(uint64_t seed, uint64_t r0, int R, const double *lo, const double *hi, double *out, void *stream);
+
+/* The burst of every realisation of a batch (deterministic.py:822-884 with one burst per realisation).  Device pointers.        */
+typedef struct {
+  int32_t n_psr;              /* P */
+  const double *phat;         /* [n_psr x 3] pulsar unit vectors (ptheta = pi/2 - dec, pphi = ra) */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *src;          /* [R x ld_src] burst columns of realisation r0 + r (the layout of pta_bwm_uniform) */
+  int64_t ld_src;             /* >= PTA_BWM_NSRC */
+  double *coef;               /* [R x n_psr] pol * strain, written by pta_engine_bwm_params */
+  double *t0_s;               /* [R] burst epoch [s] = t0_mjd * 86400, written by pta_engine_bwm_params */
+} pta_bwm_engine;
+
+/* coef[r * P + a] = 10^log10_h (cos 2psi F+_a + sin 2psi Fx_a) and t0_s[r] = 86400 t0_mjd from src row r; sin(gwtheta) = sqrt((1 - c)
+ * (1 + c)) of the cos_gwtheta column.  One thread per (r, a).                                                                   */
+int pta_engine_bwm_params(const pta_bwm_engine *bwm_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= (toa_s[i] < t0_s[r] ? 0 : coef[r, a] * (toa_s[i] - t0_s[r])) for r < R, a the pulsar of TOA i (accumulate =
+ * 1 adds, 0 writes), over the plan's TOA tiles (tile_psr / tile_start / tile_count, n_tiles, n_psr, n_toa; nothing else of the plan is
+ * read).  Two adjacent TOAs per lane and 16-byte accesses wherever the row's address allows; out and ld_out need 8-byte alignment
+ * only.  Nothing outside the tiles' columns is touched.  No atomics.                                                            */
+int pta_engine_bwm_add(const pta_engine_plan *plan_host, const pta_bwm_engine *bwm_host, int R, double *out, int64_t ld_out, int accumulate,
+                       void *stream);
+
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,
  * which never forms an N_toa x N_toa object: SURVEY.md §0.2, App. A.1).
@@ -804,6 +833,21 @@ int pta_fstat_fp(const double *Q, int64_t ld_q, int P, int J, int R, const doubl
 int64_t pta_fstat_fe_tiles(int S);
 int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, const double *phi, int S, const double *Minv, double *fe, int64_t ld_fe,
                  double *fe_max, int64_t ld_max, int32_t *fe_arg, int64_t ld_arg, double *part_val, int32_t *part_arg, void *stream);
+
+/* ---- Earth-term burst-with-memory matched filter per realisation (ABI 8, additive) ----
+ * Definitions and the host preparation: pta_replicator_amd/bwm_statistic.py.  The projection is pta_fstat_project with the J ramp
+ * templates as operator rows, C = J rounded up to even (a zero row for the pad): Q[r * ld_q + a * C + j] = W_a[j] . r_a.
+ * pta_bwm_stat: phi[(a * S + s) * 2 + (0, 1)] = (F+, Fx); Minv[(j * S + s) * 3 + (0, 1, 2)] = the packed symmetric 2 x 2 M_js^-1
+ * (00, 01, 11).  2 <= P <= PTA_FSTAT_PMAX, J <= C <= PTA_FSTAT_CMAX.  N_rjs = sum_a phi_as q_raj is formed on the fp64 matrix cores (K =
+ * P in groups of four pulsars, ascending, one chain per output) and goes into A = M^-1 N and Fb = 1/2 N^T A in registers.  Two output
+ * modes, one per call: fb != NULL writes the full map fb[r * ld_fb + j * S + s] and, with amp != NULL (16-byte aligned, ld_amp even),
+ * the amplitude estimates amp[r * ld_amp + (j * S + s) * 2 + (0, 1)] = (h cos 2psi, h sin 2psi) (fb_max, fb_arg NULL); fb == NULL
+ * writes fb_max[r * ld_max + j] = max_s Fb and fb_arg[r * ld_arg + j] = the lowest sky index attaining it (amp NULL), reduced over 16
+ * sky points at a time into the workspaces part_val, part_arg [R * J * pta_fstat_fe_tiles(S)] and folded over those in ascending
+ * order - the map is never written.  No atomics: a value is the same bits in every mode, chunk and row slot.                        */
+int pta_bwm_stat(const double *Q, int64_t ld_q, int P, int C, int J, int R, const double *phi, int S, const double *Minv, double *fb,
+                 int64_t ld_fb, double *amp, int64_t ld_amp, double *fb_max, int64_t ld_max, int32_t *fb_arg, int64_t ld_arg, double *part_val,
+                 int32_t *part_arg, void *stream);
 
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays

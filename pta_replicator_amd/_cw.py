@@ -163,15 +163,21 @@ def _like(mask, v):
 
 
 def n_sources(cw):
-    """sources per realisation of validated CW keys: 0 without CW keys, 1 for [R] keys, S for a catalogue [R, S]."""
-    if not cw:
+    """sources per realisation of validated CW keys: 0 without CW keys, 1 for [R] keys, S for a catalogue [R, S].  The dict may hold
+    other deterministic keys (bwm_*) next to them, or alone."""
+    if not has_keys(cw):
         return 0
     shape = tuple(cw[SRC_KEYS[0]].shape)
     return int(shape[1]) if len(shape) == 2 else 1
 
 
 def is_catalog(cw):
-    return bool(cw) and len(tuple(cw[SRC_KEYS[0]].shape)) == 2
+    return has_keys(cw) and len(tuple(cw[SRC_KEYS[0]].shape)) == 2
+
+
+def has_keys(det):
+    """True if a dict of validated deterministic keys (cw_* and bwm_*) holds a CW source."""
+    return bool(det) and SRC_KEYS[0] in det
 
 
 def amp_key(cw):

@@ -87,6 +87,13 @@ class CwCatalogEngine(ctypes.Structure):
     ]
 
 
+class BwmEngine(ctypes.Structure):
+    """pta_bwm_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("phat", _P), ("toa_s", _P), ("src", _P), ("ld_src", c_int64), ("coef", _P), ("t0_s", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -146,6 +153,9 @@ _SIGNATURES = {
     "pta_cw_catalog_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P]),
     "pta_engine_cw_catalog_params": (c_int, [POINTER(CwCatalogEngine), c_int, _P]),
     "pta_engine_cw_catalog_add": (c_int, [POINTER(EnginePlan), POINTER(CwCatalogEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_bwm_uniform": (c_int, [c_uint64, c_uint64, c_int, _P, _P, _P, _P]),
+    "pta_engine_bwm_params": (c_int, [POINTER(BwmEngine), c_int, _P]),
+    "pta_engine_bwm_add": (c_int, [POINTER(EnginePlan), POINTER(BwmEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
@@ -169,6 +179,7 @@ _SIGNATURES = {
     "pta_fstat_fp": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     "pta_fstat_fe_tiles": (c_int64, [c_int]),
     "pta_fstat_fe": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, c_int, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "pta_bwm_stat": (c_int, [_P, c_int64, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "pta_gather_rank0":(c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
     "pta_dgemm": (c_int, [c_int, c_int, c_int, c_int, c_double, _P, c_int64, c_int64, _P, c_int64, c_double, _P, c_int64,
                           c_int, c_int, c_int64, c_int64, c_int64, c_int, _P]),

@@ -43,6 +43,11 @@ int pta_dgemm_launch(int transB, int M, int N, int K, double alpha, const double
 
 int pta_dgemm_tile_n(int M, int N, int K, int algo);
 
+// fold of the per-sub-tile sky maxima of pta_fstat_fe / pta_bwm_stat (pta_fstat_kernels.hip): part_val / part_arg [r][tile][j], n = R J
+// outputs, tiles folded in ascending order, strictly greater wins (the lowest index on ties)
+int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int64_t n, int ntile, int J, double *vmax, int64_t ld_max,
+                            int32_t *varg, int64_t ld_arg, hipStream_t stream);
+
 // ---- ragged batches (pta_potrf_ragged): matrices of different orders in END-ALIGNED virtual coordinates -------------------------
 // Every matrix of the batch is embedded in a virtual matrix of order E whose bottom-right corner it shares: virtual index i <-> real
 // index i - front[b], front[b] = E - n[b].  In these coordinates every panel boundary, trailing size and tile grid of the blocked

@@ -258,6 +258,15 @@ __global__ __launch_bounds__(256) void k_fstat_fe_reduce(const double *__restric
   fe_arg[r * ld_arg + j] = bi;
 }
 
+// internal launcher of the fold over the sub-tile maxima (declared in pta_common.h): shared with pta_bwm_stat, whose per-tile layout is the same
+int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int64_t n, int ntile, int J, double *vmax, int64_t ld_max,
+                            int32_t *varg, int64_t ld_arg, hipStream_t stream) {
+  hipLaunchKernelGGL(k_fstat_fe_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part_val, part_arg, n, ntile, J, vmax, ld_max, varg,
+                     ld_arg);
+  PTA_LAUNCH_CHECK();
+  return PTA_OK;
+}
+
 extern "C" int pta_fstat_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R,
                                  double *Q, int64_t ld_q, void *stream) {
   PTA_REQUIRE(Wt && psr_off && rows && Q, PTA_E_ARG, "pta_fstat_project: NULL argument");
@@ -354,10 +363,7 @@ extern "C" int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, 
 #undef PTA_FS_CASE
   PTA_LAUNCH_CHECK();
   if (maxmode) {
-    const int64_t n = (int64_t)R * J;
-    hipLaunchKernelGGL(k_fstat_fe_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part_val, part_arg, n, ntile, J, fe_max, ld_max,
-                       fe_arg, ld_arg);
-    PTA_LAUNCH_CHECK();
+    return pta_fstat_reduce_launch(part_val, part_arg, (int64_t)R * J, ntile, J, fe_max, ld_max, fe_arg, ld_arg, s);
   }
   return PTA_OK;
 }

@@ -24,12 +24,13 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _cw, _hyper, _lib, device as dv
+from . import _bwm, _cw, _hyper, _lib, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import white_noise as wn
 from ._position import ra_dec
 from .constants import DAY_IN_SEC, YEAR_IN_SEC
+from .engine_bwm import BwmStatisticMixin
 from .engine_fstat import FStatisticMixin
 from .engine_lnl import LikelihoodMixin
 from .engine_os import OptimalStatisticMixin
@@ -39,13 +40,14 @@ STREAM_GWB, STREAM_RN, STREAM_WN, STREAM_ECORR, STREAM_TD, STREAM_TDGW = 1, 2, 3
 STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_id(7, 0), pair = parameter column (_hyper.columns);
                    # stream_id(7, 1), pair = node: the per-realisation GWB spectrum (_hyper.SPEC_KEY)
 STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream_id(8, 0), pair = label column (_cw.COLUMNS)
+STREAM_BWM = 9     # per-realisation burst-with-memory labels (generate_sampled): stream_id(9, 0), pair = label column (_bwm.COLUMNS)
 
 
 def stream_id(kind, pulsar):
     return ((kind << 24) | (pulsar & 0xFFFFFF)) & 0xFFFFFFFF
 
 
-class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FStatisticMixin):
+class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FStatisticMixin, BwmStatisticMixin):
     def __init__(self, psrs, seed=0):
         # pulsars with the reference's SimulatedPulsar surface are used as they are; enterprise-style ones (toas [s] / toaerrs [s] /
         # flags / pos as plain arrays: what simulate.py:91-95 hands on) are wrapped once through simulate.from_enterprise
@@ -69,6 +71,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self._det = None
         self._delays = None
         self._cw = None      # one CW source per realisation (set_cw), parameters from theta / set_cw_prior
+        self._bwm = False    # one burst with memory per realisation (set_bwm), parameters from theta / set_bwm_prior
         self._prepared = False
         # frequency -> time transform of the GWB in throughput mode: "auto" = chirp-z FFT when it fits, else the MFMA DFT-GEMM
         self.gwb_transform = "auto"
@@ -128,6 +131,15 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         Adds nothing by itself; fixed sources of add_cgw / add_delays stay as they are, on top of it.  No prepare() needed."""
         self._cw = _cw.make_config(self.P, psrTerm, evolve, phase_approx, tref, pdist)
         self._cwt = None   # device tables of the previous configuration (_cw_tables)
+        return self
+
+    def set_bwm(self):
+        """one burst with memory PER REALISATION (the reference's add_gw_memory, deterministic.py:822-884, Earth term), its parameters
+        given by the bwm_* keys of theta (generate, generate_per_signal, generate_td, the generate_* statistics) or drawn from
+        set_bwm_prior() (generate_sampled): bwm_log10_h, bwm_cos_gwtheta, bwm_gwphi, bwm_psi (the reference's bwm_pol), bwm_t0_mjd, each
+        [R].  Adds nothing by itself; a fixed ramp of add_delays stays as it is, on top of it; a realisation may carry a CW source
+        (set_cw) and a burst together, but one burst only.  No prepare() needed."""
+        self._bwm = True
         return self
 
     def add_delays(self, delays):
@@ -428,24 +440,28 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         between the nodes, constant outside them); pta_gwb_spectrum_scale_user then fills the scale row.  With set_cw(), theta may also
         hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch, or a
         catalogue of S sources per realisation (the same keys with shape [R, S], optional cw_count [R]), summed over the sources and
-        added once by pta_engine_cw_catalog_add."""
+        added once by pta_engine_cw_catalog_add.  With set_bwm(), theta may hold one burst with memory per realisation (the five bwm_*
+        keys, pta_replicator_amd._bwm), added by pta_engine_bwm_add after the CW term."""
         hyper, cw = self._theta_parts(theta, R)
         return self._generate(R, r0, out, hyper, cw)
 
     def _theta_parts(self, theta, R, td=False, check_values=True):
-        """(hyper, cw): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
-        (_hyper.check_theta), None for the fixed-parameter path (no theta, or CW keys alone); cw: its CW keys (_cw.check_theta), {} if
-        none.  td=True: TD mode, which takes CW keys only.  check_values=False skips the value checks (theta drawn by sample_theta)."""
+        """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
+        (_hyper.check_theta), None for the fixed-parameter path (no theta, or deterministic keys alone); det: its deterministic keys,
+        the CW keys (_cw.check_theta) and the BWM keys (_bwm.check_theta) in one dict, {} if none.  td=True: TD mode, which takes
+        deterministic keys only.  check_values=False skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
             return None, {}
         rest, cw = _cw.split(theta)
-        if td and (rest or not cw):   # a deterministic term leaves the factored covariance as it is
+        rest, bwm = _bwm.split(rest)
+        if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
-                             "cw_* keys are): use generate(theta=...) or generate_sampled()")
-        cw = _cw.check_theta(cw, R, self.P, self._cw, check_values)
-        if cw and not rest:
-            return None, cw
-        return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), cw
+                             "cw_* and bwm_* keys are): use generate(theta=...) or generate_sampled()")
+        det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
+        det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
+        if det and not rest:
+            return None, det
+        return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
 
     def _generate(self, R, r0, out, hyper, cw, mask_unconfigured=True):
         """generate() for theta resolved by _theta_parts, one launch sequence per batch: pta_engine_generate (hyper None) or
@@ -518,7 +534,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             self.plan.gw_G = ws["G"].data_ptr()
         if dev is not None:
             self._theta_keep = dev   # the launches above read these buffers asynchronously
-        return self._cw_apply(cw, R, out) if cw else out
+        return self._det_apply(cw, R, out) if cw else out
 
     def _theta_device(self, th, R, mask_unconfigured=True):
         """validated theta -> contiguous float64 device tensors, keys not given filled with the configured values:
@@ -589,6 +605,55 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
             self._cwt = {"phat": dv.f64(phat), "pdist": dv.f64(self._cw["pdist"])}
         return self._cwt
+
+    def _det_apply(self, det, R, out):
+        """out[R, n_toa] += the deterministic terms of every row for the validated deterministic keys of theta (the second member of
+        _theta_parts): the CW term, then the burst with memory."""
+        if _cw.has_keys(det):
+            self._cw_apply(det, R, out)
+        if _bwm.has_keys(det):
+            self._bwm_apply(det, R, out)
+        return out
+
+    def _bwm_apply(self, det, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the burst-with-memory term of every row for validated theta `det` (row r = the burst of realisation
+        r0 + r): the [R, 5] label table -> pta_engine_bwm_params (coef [R, P], t0 [R]) -> pta_engine_bwm_add, in batches of max_batch().
+        The tables are R (P + 1) doubles and stay outside the workspace budget."""
+        if not self._prepared:
+            self.prepare()
+        P = self.P
+        src = torch.stack([dv.as_f64(det[k]).reshape(R) for k in _bwm.KEYS], dim=1).contiguous()   # [R, 5]
+        step = min(R, self.max_batch())
+        tab = getattr(self, "_bwm_tab", None)
+        if tab is None or tab[0].shape[0] < step:
+            self._bwm_tab = None
+            tab = self._bwm_tab = (dv.empty((step, P)), dv.empty((step,)))
+        b = _lib.BwmEngine()
+        b.n_psr, b.phat, b.toa_s = P, self._phat_device().data_ptr(), self.d_toa_s.data_ptr()
+        b.ld_src, b.coef, b.t0_s = src.stride(0), tab[0].data_ptr(), tab[1].data_ptr()
+        s = dv.stream_ptr()
+        for lo in range(0, R, step):
+            n = min(step, R - lo)
+            b.src = src.data_ptr() + 8 * lo * src.stride(0)
+            _lib.call("pta_engine_bwm_params", ctypes.byref(b), n, s)
+            _lib.call("pta_engine_bwm_add", ctypes.byref(self.plan), ctypes.byref(b), n, ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0)),
+                      out.stride(0), 1 if accumulate else 0, s)
+        self._bwm_keep = src   # the launches above read it asynchronously
+        return out
+
+    def _phat_device(self):
+        """pulsar unit vectors [P, 3] on the device (the reference's expression, deterministic.py:858), built once."""
+        if getattr(self, "_d_phat", None) is None:
+            self._d_phat = dv.f64(_cw.pulsar_vectors([ra_dec(p) for p in self.psrs]))
+        return self._d_phat
+
+    def set_bwm_prior(self, log10_h=None, t0_mjd=None, cos_gwtheta=None, gwphi=None, psi=None):
+        """uniform boxes (lo, hi) of the per-realisation burst of generate_sampled() (set_bwm configures it).  Required: log10_h and
+        t0_mjd.  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), psi (0, pi) (isotropic sky and polarisation).  Drawn from stream (9, 0),
+        pair = label column (_bwm.COLUMNS), independently of set_hyper_prior's and set_cw_prior's parameters."""
+        self._bwm_prior = _bwm.make_prior(log10_h=log10_h, t0_mjd=t0_mjd, cos_gwtheta=cos_gwtheta, gwphi=gwphi, psi=psi)
+        self._bwm_prior_dev = None
+        return self
 
     def _cw_apply(self, cw, R, out, accumulate=True):
         """out[R, n_toa] (+)= the CW term of every row for validated CW theta `cw` (row r = the source of realisation r0 + r): the
@@ -694,13 +759,15 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         (seed, r) like its residuals).  theta: {key: device tensor} of the sampled keys, gwb_* [R], rn_* [R, P] (NaN for pulsars
         without red noise) - the labels of the realisations.  A sampled spectrum comes back as gwb_log10_hc [R, M], node j drawn from
         stream (7, 1), pair j (pta_hyper_uniform_field), so the columns of stream (7, 0) and their labels do not move."""
-        prior, cw_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None)
-        if prior is None and cw_prior is None:
-            raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior first)")
+        prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None:
+            raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if prior is not None:
             _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
         if cw_prior is not None and self._cw is None:
             raise ValueError("generate_sampled: no per-realisation CW configured (set_cw)")
+        if bwm_prior is not None and not self._bwm:
+            raise ValueError("generate_sampled: no per-realisation burst with memory configured (set_bwm)")
         if not self._prepared:
             self.prepare()
         theta = self.sample_theta(R, r0)
@@ -709,12 +776,19 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
 
     def sample_theta(self, R, r0=0):
         """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses)."""
-        prior, cw_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None)
-        if prior is None and cw_prior is None:
-            raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior first)")
+        prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None:
+            raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
         theta = {}
+        if bwm_prior is not None:   # stream (9, 0): pair j = label column j, whatever else is sampled
+            if self._bwm_prior_dev is None:
+                self._bwm_prior_dev = [dv.f64(x) for x in _bwm.prior_bounds(bwm_prior)]
+            d_lo, d_hi = self._bwm_prior_dev
+            table = dv.empty((R, _bwm.N_SRC))
+            _lib.call("pta_bwm_uniform", self.seed, r0, R, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+            theta.update(_bwm.labels(table))
         if cw_prior is not None:   # stream (8, 0): pair j = label column j, whatever else is sampled
             if self._cw_prior_dev is None:
                 self._cw_prior_dev = [dv.f64(x) for x in _cw.prior_bounds(cw_prior, self.P)]
@@ -802,7 +876,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         function of (seed, realisation, stream, index), so running the fused kernel once per signal with the other inputs
         switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate(); with
         CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer; for a catalogue the
-        sum over its sources, pta_engine_cw_catalog_add)."""
+        sum over its sources, pta_engine_cw_catalog_add); with BWM keys 'bwm', the per-realisation burst-with-memory term alone
+        (pta_engine_bwm_add writing its own buffer)."""
         hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
@@ -833,8 +908,10 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             one("ecorr", ecorr_toa=keep[4], epoch_of=keep[5])
         if keep[6]:
             out["det"] = self.d_det.unsqueeze(0).expand(R, self.n_toa)
-        if cw:
+        if _cw.has_keys(cw):
             out["cw"] = self._cw_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
+        if _bwm.has_keys(cw):
+            out["bwm"] = self._bwm_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         return out
 
     def stream_to_host(self, total, chunk=480, r0=0):

@@ -1,0 +1,172 @@
+"""Earth-term burst-with-memory (BWM) matched filter of the ReplicaEngine's realisations, per realisation, on the device.
+
+``prepare_bwm_statistic(t0_mjd, sky)`` builds the realisation-independent operands on the host from the noise model ``prepare()`` holds
+(pta_replicator_amd/bwm_statistic.py: W_a = e_a^T P_a^-1 over the epoch grid, g_aj, the antenna patterns phi and M_js^-1) and uploads
+them once; ``bwm_statistic(rows)`` then costs per chunk of realisations
+
+    pta_fstat_project   Q[r, a, :] = W_a r_a                       the F-statistic's ragged grouped GEMM (fp64 MFMA), J columns (+ a pad)
+    pta_bwm_stat        Fb[r, j, s] = 1/2 N^T M_js^-1 N             N = sum_a phi_as q_raj on the matrix cores, never stored; the full
+                                                                   map (and A = M^-1 N), or (sky_max) its maximum and argmax per (r, j)
+
+and ``generate_bwm_statistic(R)`` runs generate / generate_td / generate(theta=...) chunk by chunk into one reused buffer with the
+statistic behind each chunk, keeping only the statistic.  A realisation's values are bit-identical whatever chunk, row or output mode
+they are computed in.
+
+The noise weights are the configured ones (white noise + ECORR + red noise, optionally the GWB auto-term, timing model marginalised).
+Out of scope: the pulsar term and the single-pulsar ramp statistic, a statistic matched to per-realisation theta, more than one burst
+per realisation, maximising over a continuous epoch.
+
+The argument checks, the host noise model, the rows and state checks and the chunked generation loop with its rows buffer are
+engine_stats.StatisticsMixin's, shared with the optimal statistic, the likelihood and the F-statistic.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _cw, _lib, device as dv
+from . import bwm_statistic as bst
+from . import f_statistic as fst
+from . import optimal_statistic as ost
+from ._position import ra_dec
+from .engine_stats import StatisticsMixin, check_components, check_timing_model
+
+
+class BwmStatisticMixin(StatisticsMixin):
+    def prepare_bwm_statistic(self, t0_mjd, sky, timing_model="spin", gwb_auto=None, components=14, gamma=13. / 3.):
+        """W, g (and phi, M^-1 on the sky grid) of the array under the configured noise model (white noise + ECORR + red noise,
+        optionally the GWB auto-term), uploaded once.  Returns self.
+
+        t0_mjd: [J] burst epochs (MJD, finite), the grid of theta's bwm_t0_mjd; sky: a (cos_gwtheta [S], gwphi [S]) pair, the sky grid
+        in the angles of theta's bwm_cos_gwtheta / bwm_gwphi (mandatory; needs at least two pulsars); timing_model: "spin",
+        "astrometric" or None; gwb_auto, components, gamma: the GWB auto-term of C_a, as in prepare_f_statistic.
+
+        A pulsar whose data do not constrain the ramp of an epoch (all its TOAs before it, or all after it so that the spin-down fit
+        absorbs the ramp) contributes nothing at that epoch; an epoch fewer than two pulsars are sensitive to is refused."""
+        t0 = bst.check_epochs(t0_mjd)
+        if sky is None:
+            raise ValueError("prepare_bwm_statistic: the sky grid is mandatory, sky = (cos_gwtheta [S], gwphi [S])")
+        sky = fst.check_sky(sky)
+        check_timing_model(timing_model)
+        check_components(components, columns="")
+        J = len(t0)
+        if J > _lib.FSTAT_CMAX - 1:
+            raise ValueError(f"{J} epochs: one preparation holds at most {_lib.FSTAT_CMAX - 1}")
+        if self.P < 2:
+            raise ValueError("the BWM statistic needs at least two pulsars")
+        if self.P > _lib.FSTAT_PMAX:
+            raise ValueError(f"the BWM statistic kernel holds at most {_lib.FSTAT_PMAX} pulsars, got {self.P}")
+        self._stats_need_noise("the BWM statistic")
+        C = J + (J & 1)
+        if C * self.n_toa * 8 > int(self.workspace_bytes):
+            raise ValueError(f"the projection operator [{C}, n_toa = {self.n_toa}] takes {C * self.n_toa * 8} bytes, more than "
+                             f"workspace_bytes = {int(self.workspace_bytes)}: use fewer epochs per preparation or raise workspace_bytes")
+        gw_lA = self._stats_gwb_auto(gwb_auto)
+        toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
+        P = self.P
+        F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]     # the low-rank part of C_a: red noise, then the GWB auto-term
+        if F_rn is not None:
+            for a in range(P):
+                F_low[a].append(F_rn[a])
+                phi_low[a].append(phi_rn[a])
+        if gw_lA is not None:
+            T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
+            S = ost.unit_spectrum(int(components), T, float(gamma))
+            for a in range(P):
+                F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
+                phi_low[a].append(10.0 ** (2 * gw_lA) * S)
+        low = bool(F_low[0])
+        phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
+        plan = bst.prepare(toas, sigma2, t0 * 86400.0, phat, sky, epoch_of=epoch_of, ecorr=ecorr,
+                           F_rn=[np.concatenate(x, axis=1) for x in F_low] if low else None,
+                           phi_rn=[np.concatenate(x) for x in phi_low] if low else None, M=M)
+        self._bs = dict(plan=plan, engine_plan=self.plan, J=J, C=plan.C, S=plan.S, Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), t0_mjd=dv.f64(t0),
+                        phi=dv.f64(plan.phi), Minv=dv.f64(plan.Minv_packed()), ntile=int(_lib.lib.pta_fstat_fe_tiles(plan.S)), ws=None)
+        return self
+
+    def _bs_state(self, what):
+        return self._stats_state("_bs", "the BWM statistic", "prepare_bwm_statistic", what)
+
+    @staticmethod
+    def _bs_modes(what, sky_max, amplitudes):
+        if sky_max and amplitudes:
+            raise ValueError(f"{what}: amplitudes=True needs the full map (sky_max=True keeps the maxima only)")
+
+    def _bs_chunk(self, st, R, sky_max, with_rows):
+        """realisations per launch sequence: Q [P, C], the per-tile maxima of sky_max (and the generated rows) within workspace_bytes.
+        The outputs (fb, amp or fb_max / fb_arg of all R realisations) are the call's result, not workspace."""
+        per_real = 8 * self.P * st["C"] + (12 * st["J"] * st["ntile"] if sky_max else 0) + (8 * self.n_toa if with_rows else 0)
+        return max(1, min(R, int(self.workspace_bytes) // per_real))
+
+    def _bs_out(self, st, R, sky_max, amplitudes):
+        J, S = st["J"], st["S"]
+        out = dict.fromkeys(("fb", "amp", "fb_max", "fb_arg"))
+        if sky_max:
+            out["fb_max"], out["fb_arg"] = dv.empty((R, J)), dv.empty((R, J), dtype=torch.int32)
+        else:
+            out["fb"] = dv.empty((R, J, S))
+            if amplitudes:
+                out["amp"] = dv.empty((R, J, S, 2))
+        return out
+
+    def _bs_result(self, st, out):
+        res = {k: v for k, v in out.items() if v is not None}
+        res["t0_mjd"] = st["t0_mjd"]
+        return res
+
+    def _bs_launch(self, rows, n, lo, out):
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: pta_fstat_project into the reused Q buffer,
+        then pta_bwm_stat - on the current stream"""
+        st = self._bs
+        P, J, C, S = self.P, st["J"], st["C"], st["S"]
+        sky_max = out["fb_max"] is not None
+        ws = st["ws"]
+        if ws is None or ws["n"] < n or (sky_max and ws["pv"] is None):
+            st["ws"] = None
+            ws = st["ws"] = dict(n=n, Q=dv.empty((n, P * C)), pv=dv.empty((n * J * st["ntile"],)) if sky_max else None,
+                                 pa=dv.empty((n * J * st["ntile"],), dtype=torch.int32) if sky_max else None)
+        s = dv.stream_ptr()
+        Q = ws["Q"]
+        _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
+                  dv.ptr(Q), P * C, s)
+        if sky_max:
+            _lib.call("pta_bwm_stat", dv.ptr(Q), P * C, P, C, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]), None, 0, None, 0,
+                      dv.row_ptr(out["fb_max"], lo), J, dv.row_ptr(out["fb_arg"], lo), J, dv.ptr(ws["pv"]), dv.ptr(ws["pa"]), s)
+        else:
+            _lib.call("pta_bwm_stat", dv.ptr(Q), P * C, P, C, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]), dv.row_ptr(out["fb"], lo), J * S,
+                      dv.row_ptr(out["amp"], lo), 2 * J * S, None, 0, None, 0, None, None, s)
+
+    def bwm_statistic(self, rows, sky_max=False, amplitudes=False):
+        """Fb of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
+        generate_td, generate_sampled, or the caller's own residuals).  Returns a dict of device tensors: fb [R, J, S] and t0_mjd [J];
+        with amplitudes=True also amp [R, J, S, 2], the amplitude estimates (h cos 2psi, h sin 2psi); with sky_max=True fb_max [R, J]
+        and fb_arg [R, J] (int32: the sky index of the maximum, the lowest on ties) instead - the map is then never written, and
+        amplitudes is refused.  The noise weights are the configured ones (no per-realisation theta).  Rows are processed in chunks that
+        keep the workspace (Q, the per-tile maxima of sky_max) within workspace_bytes; the returned tensors are the caller's result and
+        lie outside that budget."""
+        self._bs_modes("bwm_statistic", sky_max, amplitudes)
+        st = self._bs_state("bwm_statistic")
+        R = self._stats_check_rows(rows)
+        out = self._bs_out(st, R, sky_max, amplitudes)
+        step = self._bs_chunk(st, R, sky_max, with_rows=False)
+        for lo in range(0, R, step):
+            self._bs_launch(rows[lo:lo + step], min(step, R - lo), lo, out)
+        return self._bs_result(st, out)
+
+    def generate_bwm_statistic(self, R, r0=0, theta=None, td=False, chunk=1024, sky_max=False, amplitudes=False):
+        """Fb of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
+        td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations, bwm_* and cw_* keys included);
+        only the statistic is kept.  Same results as bwm_statistic(generate(R, r0, ...), sky_max, amplitudes), bit for bit, whatever
+        the chunk.  The chunk is cut so that the buffer and Q stay within workspace_bytes.  theta only shapes the data: the statistic's
+        noise weights stay the configured ones."""
+        self._bs_modes("generate_bwm_statistic", sky_max, amplitudes)
+        st = self._bs_state("generate_bwm_statistic")
+        R, r0, chunk = int(R), int(r0), int(chunk)
+        if R < 1 or chunk < 1 or r0 < 0:
+            raise ValueError(f"generate_bwm_statistic: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
+        hyper, det = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
+        chunk = max(1, min(chunk, self._bs_chunk(st, R, sky_max, with_rows=True)))
+        out = self._bs_out(st, R, sky_max, amplitudes)
+        for lo, n, rows in self._stats_generate_chunks(lambda: self._bs_state("generate_bwm_statistic"), R, r0, hyper, det, td, chunk):
+            self._bs_launch(rows, n, lo, out)
+        return self._bs_result(st, out)

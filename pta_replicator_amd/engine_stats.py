@@ -111,7 +111,8 @@ class StatisticsMixin:
                       rows.stride(0), n, ctypes.c_void_p(q.data_ptr() + 8 * P * k0), P * K, s)
 
     def _stats_generate_chunks(self, state, R, r0, hyper, cw, td, chunk):
-        """realisations r0 .. r0+R-1 generated chunk by chunk (generate_td with td, else _generate with theta's parts hyper / cw) into
+        """realisations r0 .. r0+R-1 generated chunk by chunk (generate_td with td, else _generate with theta's parts hyper / cw, cw =
+        its deterministic keys, cw_* and bwm_*) into
         the one [>= chunk, n_toa] rows buffer every statistic shares, grown on demand: yields (lo, n, rows [n, n_toa]) per chunk.
         state() re-validates the caller's prepared state after every chunk (generation may (re)prepare the engine)."""
         buf = getattr(self, "_stats_rows", None)
@@ -127,7 +128,7 @@ class StatisticsMixin:
             if td:
                 self.generate_td(n, r0=r0 + lo, out=rows)
                 if cw:
-                    self._cw_apply(rows_of(cw, lo, n), n, rows)
+                    self._det_apply(rows_of(cw, lo, n), n, rows)
             else:
                 self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
             state()

@@ -344,7 +344,7 @@ class TimeDomainMixin:
         and NOT the default (profiles/r04_bench_mid_round.json): 32.8 ms per 1024 realisations of the 68 x 5000 array in four pipelined
         chunks of 256 against 31.2 ms as one chunk - every chunk streams the 13.6 GB of factors again, and the preparation kernels are
         VALU work on the ALUs the matrix pipe shares, not idle time to fill."""
-        _, cw = self._theta_parts(theta, R, td=True)   # only CW keys, added after the batch
+        _, cw = self._theta_parts(theta, R, td=True)   # only deterministic keys (cw_*, bwm_*), added after the batch
         if not getattr(self, "_td_prepared", False) or not self._prepared:
             self.prepare_td()
         if out is None:
@@ -455,7 +455,7 @@ class TimeDomainMixin:
                       out.stride(0), s)
             if overlap:
                 ev_done[c & 1].record(main)
-        return self._cw_apply(cw, R, out) if cw else out
+        return self._det_apply(cw, R, out) if cw else out
 
     # ---------------------------------------------------------------- draws / replay ------------
     def dump_draws_td(self, r):
