@@ -315,6 +315,23 @@ int pta_gwb_spectrum_scale_user(const int32_t *seg, const double *dx, const doub
  * MFMA GEMM; 2: the generic VALU reference GEMM (cross-check)                                                       */
 int pta_gwb_mix(const double *Mchol, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant, void *stream);
 
+/* An ORF factor per realisation (ABI 8, additive): Mchol[r] = chol(2 sum_k clm[r * ld_clm + k] basis[k]), k < n_lm = (lmax + 1)^2 <= 81,
+ * the reference's add_gwb(clm=, lmax=) with a clm per realisation (red_noise.py:225-226, 235).  basis [n_lm, P, P] from pta_orf_basis;
+ * Mchol [R, P, P] row-major lower factors, upper triangles zero; info [R] int32.  The sum over k is pta_orf_combine's, so a row equal
+ * to a configured clm gives that configuration's ORF bit for bit.  A pivot that is not positive or not finite sets info[r] to its
+ * 1-based index (LAPACK's convention) and fills ALL of Mchol[r] with NaN; other realisations are unaffected (nothing is shared
+ * between realisations: no atomics, no reduction across them).  P <= 80: one launch, four realisations per workgroup (the basis is
+ * read once per workgroup), factored in LDS; P > 80: clm . basis by the batched GEMM, pta_potrf_batched_ex with
+ * PTA_POTRF_SUBSTITUTION | PTA_POTRF_ZERO_UPPER, and the same NaN fill.  P <= 4096, ld_clm >= n_lm.                              */
+int pta_gwb_orf_factor(const double *basis, int n_lm, int P, const double *clm, int64_t ld_clm, int R, double *Mchol, int32_t *info,
+                       void *stream);
+/* pta_gwb_mix with a factor per realisation: G[r,a,:] = sum_b Mchol[r * ld_m + a * P + b] G0[r,b,:], ld_m >= P * P doubles per
+ * realisation (the full square is read: upper triangles must hold zeros).  variant as pta_gwb_mix: 0 = the LDS kernel when P <= 80
+ * (the factor staged once per workgroup and reused over at least four 64-sample tiles of its realisation), else the batched MFMA
+ * GEMM; 1: always that GEMM; 2: the VALU reference GEMM.  R <= 65535 per call with variant 0 and P <= 80.                        */
+int pta_gwb_mix_batched(const double *Mchol, int64_t ld_m, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant,
+                        void *stream);
+
 /* jlo[i] = last j with ut[j] <= toa_s[i], clamped to [0, npts-2] (numpy.interp's bracket, which
  * scipy.interpolate.interp1d(kind="linear") delegates to; red_noise.py:286-287).           */
 int pta_gwb_bracket(const double *ut, int npts, const double *toa_s, int N, int32_t *jlo, void *stream);
@@ -461,10 +478,12 @@ typedef struct {
   const double *rn_tspan;     /* [n_psr] Tspan [s] */
   const double *rn_log10_A;   /* [R x n_psr] (NULL: configured red noise); NaN = configured amplitude of that pulsar */
   const double *rn_gamma;     /* [R x n_psr] */
+  const double *gw_mchol;     /* [R x ld_gw_mchol] ORF factor per realisation (pta_gwb_orf_factor); NULL = pta_engine_tables.Mchol for all */
+  int64_t ld_gw_mchol;        /* >= n_psr^2 */
 } pta_engine_hyper;
 
 /* pta_engine_generate with per-realisation theta: pta_engine_rn_coef_hyper -> pta_gwb_spectrum_scale -> pta_gwb_czt_scaled (or
- * pta_gwb_idft_rng_scaled) -> pta_gwb_mix -> pta_engine_synth (unchanged).  White noise, ECORR and deterministic signals as
+ * pta_gwb_idft_rng_scaled) -> pta_gwb_mix (pta_gwb_mix_batched with gw_mchol) -> pta_engine_synth (unchanged).  White noise, ECORR and deterministic signals as
  * configured in the plan.                                                                                                 */
 int pta_engine_generate_hyper(const pta_engine_plan *plan_host, const pta_engine_tables *tables_host, const pta_engine_hyper *hyper_host,
                               uint64_t seed, uint64_t r0, int R, double *out, int64_t ld_out, void *stream);

@@ -5,6 +5,7 @@ theta is a dict with any subset of
     gwb_log10_A, gwb_gamma   [R]      GWB amplitude / spectral index of realisation r0 + r
     rn_log10_A, rn_gamma     [R, P]   red-noise amplitude / spectral index of pulsar a in realisation r0 + r
     gwb_log10_hc             [R, M]   log10 characteristic strain of realisation r0 + r at the M nodes of the configured userSpec
+    gwb_clm                  [R, (lmax+1)^2]   angular power coefficients c_lm of realisation r0 + r, column k = l^2 + m + l
 as NumPy arrays or torch tensors.  A key that is not given keeps its configured value.  NaN in rn_log10_A means "this pulsar as
 configured" (amplitude and index); a pulsar configured without red noise keeps none whatever its entries say.
 """
@@ -19,7 +20,13 @@ KEYS = GWB_KEYS + RN_KEYS
 SPEC_KEY = "gwb_log10_hc"
 SPEC_FIELD = 1
 SPEC_MAX_NODES = 4096   # PTA_GWB_SPEC_MMAX: the nodes of one realisation are staged in LDS
-ALL_KEYS = KEYS + (SPEC_KEY,)
+# the per-realisation angular power distribution of an engine configured with set_gwb(lmax=L >= 1): row r replaces the configured clm
+# (ORF_r = 2 sum_k clm[r, k] basis[k], column order of correlated_basis).  Its l >= 1 columns are drawn from stream (7, CLM_FIELD),
+# pair = column; column 0 (c_00) stays as configured
+CLM_KEY = "gwb_clm"
+CLM_FIELD = 2
+ORF_INFO_KEY = "gwb_orf_info"   # label of sampled theta: info [R] of pta_gwb_orf_factor (0 = positive definite); no parameter
+ALL_KEYS = KEYS + (SPEC_KEY, CLM_KEY)
 
 
 def n_columns(P):
@@ -55,8 +62,34 @@ def check_config(keys, gw, rn, gwb_mode):
         if gwb_mode == "grid":
             raise ValueError(f"theta: {SPEC_KEY} needs gwb_mode='fourier' (the 'grid' factor is built for one spectrum)")
         spec_nodes(gw["userSpec"])
+    if CLM_KEY in keys:
+        if gw is None:
+            raise ValueError(f"theta: {CLM_KEY} given but no GWB is configured (set_gwb)")
+        if gw.get("no_correlations"):
+            raise ValueError(f"theta: {CLM_KEY} needs a correlated GWB (set_gwb(no_correlations=True) has no ORF to shape)")
+        if n_lm(gw) is None:
+            raise ValueError(f"theta: {CLM_KEY} needs a GWB configured with set_gwb(lmax=L), L >= 1 (lmax fixes the columns; at lmax = 0 the "
+                             "only coefficient is the amplitude)")
+        if gwb_mode == "grid":
+            raise ValueError(f"theta: {CLM_KEY} needs gwb_mode='fourier' (the 'grid' path mixes with the one configured ORF factor)")
     if keys & set(RN_KEYS) and rn is None:
         raise ValueError("theta: red-noise parameters given but no red noise is configured (set_red_noise)")
+
+
+def n_lm(gw):
+    """(lmax + 1)^2 of a GWB configuration that can carry gwb_clm per realisation (lmax >= 1, correlated), else None"""
+    if gw is None or gw.get("no_correlations") or int(gw.get("lmax") or 0) < 1:
+        return None
+    return (int(gw["lmax"]) + 1) ** 2
+
+
+def configured_clm(gw):
+    """the configured clm [n_lm] (the first n_lm entries, as the reference's sum reads them)"""
+    n = n_lm(gw)
+    c = np.asarray(gw["clm"], dtype=np.float64).ravel()
+    if len(c) < n:
+        raise IndexError(f"clm has {len(c)} coefficients but lmax={gw['lmax']} needs {n}")
+    return c[:n].copy()
 
 
 def spec_nodes(userSpec):
@@ -131,19 +164,21 @@ def check_theta(theta, R, P, gw, rn, gwb_mode, check_values=True):
     if not isinstance(theta, dict):
         raise ValueError("theta must be a dict of per-realisation parameters")
     check_config(theta.keys(), gw, rn, gwb_mode)
-    return _check_arrays(theta, R, P, rn, check_values, _n_nodes(gw))
+    return _check_arrays(theta, R, P, rn, check_values, _n_nodes(gw), n_lm(gw))
 
 
 def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True, gw=None):
     """validate theta as the noise model of the optimal statistic (optimal_statistic(theta=...), generate_os(matched=True)): keys,
     shapes and NaN rules of check_theta, without its gwb_mode restriction (the OS does not care how the GWB was generated).  GWB
     keys are refused when the OS was prepared without the GWB auto-term (gwb_auto false); cw_* keys are ignored (a deterministic
-    source is not part of the noise model).  gw: the engine's GWB configuration; given, the spectrum key gwb_log10_hc is accepted too
+    source is not part of the noise model, and so is gwb_clm: the auto-term stays the isotropic one).  gw: the engine's GWB configuration; given, the spectrum key gwb_log10_hc is accepted too
     (its nodes are the configured userSpec's; left out, as by the likelihood grid, the key is unknown).  Returns {key: array} of the
     GWB / red-noise keys."""
     from . import _cw
     theta, _ = _cw.split(theta)
-    known = KEYS if gw is None else ALL_KEYS
+    if gw is not None:
+        theta = {k: v for k, v in theta.items() if k not in (CLM_KEY, ORF_INFO_KEY)}
+    known = KEYS if gw is None else KEYS + (SPEC_KEY,)
     unknown = set(theta) - set(known)
     if unknown:
         raise ValueError(f"theta: unknown keys {sorted(unknown)} (expected a subset of {list(known)})")
@@ -160,19 +195,19 @@ def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True, gw=None):
     return _check_arrays(theta, R, P, rn, check_values, _n_nodes(gw))
 
 
-def _check_arrays(theta, R, P, rn, check_values, M=None):
+def _check_arrays(theta, R, P, rn, check_values, M=None, L=None):
     """shapes and values of theta's GWB / red-noise arrays (keys already checked against the configuration); M: nodes of the
-    configured userSpec (the columns of gwb_log10_hc)."""
+    configured userSpec (the columns of gwb_log10_hc); L: (lmax + 1)^2 of the configured GWB (the columns of gwb_clm)."""
     out = {}
     for k, v in theta.items():
         v = _as_array(k, v)
-        want = (R,) if k in GWB_KEYS else (R, M) if k == SPEC_KEY else (R, P)
+        want = (R,) if k in GWB_KEYS else (R, M) if k == SPEC_KEY else (R, L) if k == CLM_KEY else (R, P)
         if tuple(v.shape) != want:
             raise ValueError(f"theta[{k!r}]: shape {tuple(v.shape)}, expected {want}")
         out[k] = v
     if not check_values:
         return out
-    for k in GWB_KEYS + (SPEC_KEY,):
+    for k in GWB_KEYS + (SPEC_KEY, CLM_KEY):
         if k in out and not bool(_xp(out[k]).isfinite(out[k]).all()):
             raise ValueError(f"theta[{k!r}]: non-finite values")
     if "rn_log10_A" in out:
@@ -214,7 +249,7 @@ def prior_bounds(prior, P):
     lo, hi = np.zeros(n_columns(P)), np.zeros(n_columns(P))
     cols = columns(P)
     for k, (l, h) in prior.items():
-        if k == SPEC_KEY:   # its own table: spec_bounds
+        if k in (SPEC_KEY, CLM_KEY):   # their own tables: spec_bounds, clm_bounds
             continue
         c0, c1 = cols[k]
         lo[c0:c1], hi[c0:c1] = l, h
@@ -227,9 +262,20 @@ def spec_bounds(prior):
     return prior.get(SPEC_KEY)
 
 
-def make_prior(P, M=None, **boxes):
+def clm_bounds(prior, gw):
+    """lo, hi [n_lm] of pta_hyper_uniform_field(field = CLM_FIELD) for the gwb_clm boxes of a prior dict: pair j = column j of gwb_clm;
+    column 0 is the box [c_00, c_00) of the configured c_00 (lo + 0 u = c_00 exactly); None when clm is not sampled."""
+    if CLM_KEY not in prior:
+        return None
+    c00 = configured_clm(gw)[0]
+    l, h = prior[CLM_KEY]
+    return np.concatenate([[c00], l]), np.concatenate([[c00], h])
+
+
+def make_prior(P, M=None, L=None, **boxes):
     """validated {key: (lo [n], hi [n])} of set_hyper_prior: GWB keys take (lo, hi); RN keys (lo, hi) for all pulsars or [P, 2];
-    gwb_log10_hc (lo, hi) for all M nodes of the configured userSpec or [M, 2] (M None: no userSpec is configured)."""
+    gwb_log10_hc (lo, hi) for all M nodes of the configured userSpec or [M, 2] (M None: no userSpec is configured); gwb_clm (lo, hi)
+    for all L - 1 coefficients with l >= 1 or [L - 1, 2], L = (lmax + 1)^2 (None: no lmax >= 1 is configured)."""
     prior = {}
     for k, box in boxes.items():
         if box is None:
@@ -238,8 +284,10 @@ def make_prior(P, M=None, **boxes):
             raise ValueError(f"set_hyper_prior: unknown parameter {k!r} (expected one of {list(ALL_KEYS)})")
         if k == SPEC_KEY and M is None:
             raise ValueError(f"set_hyper_prior: {k} needs a GWB configured with a userSpec spectrum (its frequency column fixes the nodes)")
+        if k == CLM_KEY and L is None:
+            raise ValueError(f"set_hyper_prior: {k} needs a correlated GWB configured with set_gwb(lmax=L), L >= 1")
         b = np.asarray(box, dtype=np.float64)
-        n = 1 if k in GWB_KEYS else M if k == SPEC_KEY else P
+        n = 1 if k in GWB_KEYS else M if k == SPEC_KEY else L - 1 if k == CLM_KEY else P
         if b.shape == (2,):
             b = np.broadcast_to(b, (n, 2))
         if b.shape != (n, 2):

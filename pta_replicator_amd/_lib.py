@@ -66,7 +66,7 @@ class EngineHyper(ctypes.Structure):
     _fields_ = [
         ("gw_scale", _P), ("ld_gw_scale", c_int64), ("gw_log10_A", _P), ("gw_gamma", _P), ("gw_f", _P), ("gw_hcf0", _P),
         ("gw_turnover", c_int32), ("gw_f0", c_double), ("gw_beta", c_double), ("gw_power", c_double), ("ws_scale", _P),
-        ("rn_f", _P), ("rn_tspan", _P), ("rn_log10_A", _P), ("rn_gamma", _P),
+        ("rn_f", _P), ("rn_tspan", _P), ("rn_log10_A", _P), ("rn_gamma", _P), ("gw_mchol", _P), ("ld_gw_mchol", c_int64),
     ]
 
 
@@ -135,6 +135,8 @@ _SIGNATURES = {
     "pta_gwb_idft_rng_scaled": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, c_int, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
     "pta_gwb_spectrum_scale": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_double, c_double, c_double, _P, c_int64, _P]),
     "pta_gwb_mix": (c_int, [_P, c_int, _P, c_int, c_int, c_int64, _P, c_int, _P]),
+    "pta_gwb_orf_factor": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, _P, _P, _P]),
+    "pta_gwb_mix_batched": (c_int, [_P, c_int64, c_int, _P, c_int, c_int, c_int64, _P, c_int, _P]),
     "pta_gwb_bracket": (c_int, [_P, c_int, _P, c_int, _P, _P]),
     "pta_gwb_weights": (c_int, [_P, c_int, _P, _P, c_int, _P, _P]),
     "pta_gwb_interp": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_double, _P, c_int64, c_int, _P]),
@@ -196,6 +198,7 @@ ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX
 CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 CW_CATALOG_NPAR = (16, 8, 8)  # by mode: PTA_CW_CATALOG_NPAR_EVOLVE, PTA_CW_CATALOG_NPAR_FOLDED (phase_approx, monochromatic)
 OS_CMAX = 64         # PTA_OS_CMAX
+OS_NORF = 8          # PTA_OS_NORF: ORFs (weight rows) of one pta_os_pairs call
 OSM_KMAX = 128       # PTA_OSM_KMAX
 LNL_KMAX = 128       # PTA_LNL_KMAX
 LNL_MMAX = 16        # PTA_LNL_MMAX

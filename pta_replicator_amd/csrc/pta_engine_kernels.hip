@@ -533,6 +533,8 @@ extern "C" int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf
                                 double *G0, int64_t ldg, int variant, int rng_fast, void *stream);
 extern "C" int pta_gwb_mix(const double *Mchol, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant,
                            void *stream);
+extern "C" int pta_gwb_mix_batched(const double *Mchol, int64_t ld_m, int P, const double *G0, int R, int npts, int64_t ldg, double *G,
+                                   int variant, void *stream);
 
 // The stage chain of pta_engine_generate and pta_engine_generate_hyper, queued on `stream`: RN coefficients -> (spectrum scale) ->
 // GWB transform -> ORF mix -> fused synthesis.  hyper == NULL stands for a pta_engine_hyper whose members are all NULL; a NULL
@@ -584,7 +586,8 @@ static int engine_generate(const char *fn, const pta_engine_plan *plan_host, con
                                     p.rng_fast, stream);
     }
     if (rc != PTA_OK) return rc;
-    rc = pta_gwb_mix(tb.Mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream);
+    rc = h.gw_mchol ? pta_gwb_mix_batched(h.gw_mchol, h.ld_gw_mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream)
+                    : pta_gwb_mix(tb.Mchol, p.n_psr, tb.ws_G0, R, p.gw_npts, p.gw_npts, tb.ws_G, tb.mix_variant, stream);
     if (rc != PTA_OK) return rc;
     p.gw_G = tb.ws_G;
   }

@@ -27,6 +27,7 @@ import torch
 from . import _bwm, _cw, _hyper, _lib, device as dv
 from . import deterministic as det
 from . import red_noise as rn
+from . import spharmORFbasis as anis
 from . import white_noise as wn
 from ._position import ra_dec
 from .constants import DAY_IN_SEC, YEAR_IN_SEC
@@ -38,7 +39,8 @@ from .engine_td import TimeDomainMixin
 
 STREAM_GWB, STREAM_RN, STREAM_WN, STREAM_ECORR, STREAM_TD, STREAM_TDGW = 1, 2, 3, 4, 5, 6
 STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_id(7, 0), pair = parameter column (_hyper.columns);
-                   # stream_id(7, 1), pair = node: the per-realisation GWB spectrum (_hyper.SPEC_KEY)
+                   # stream_id(7, 1), pair = node: the per-realisation GWB spectrum (_hyper.SPEC_KEY);
+                   # stream_id(7, 2), pair = column: the per-realisation angular power coefficients (_hyper.CLM_KEY)
 STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream_id(8, 0), pair = label column (_cw.COLUMNS)
 STREAM_BWM = 9     # per-realisation burst-with-memory labels (generate_sampled): stream_id(9, 0), pair = label column (_bwm.COLUMNS)
 
@@ -296,6 +298,10 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             ORF = rn.gwb_orf_device(self.psrs, c["no_correlations"], c["clm"], c["lmax"])
             self.ORF = ORF.clone()
             self.d_M = rn.cholesky_device(ORF)
+            # the basis ORFs of a configuration that can carry a clm per realisation (theta's gwb_clm): pta_gwb_orf_factor's operand
+            self.d_orf_basis = None
+            if _hyper.n_lm(c) is not None:
+                self.d_orf_basis = anis.correlated_basis_device(rn.pulsar_locations(self.psrs), int(c["lmax"]))
             self.C = rn.gwb_spectrum(grid["f"], grid["dur"], c["howml"], c["A"], c["g"], c["turnover"], c["f0"], c["beta"],
                                      c["power"], c["userSpec"])
             self.ldt = rn.pad16(npts)
@@ -410,16 +416,21 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self.plan.rng_fast, self.plan.synth_variant = int(self.rng_fast), int(self.synth_variant)
         return ws
 
-    def max_batch(self, hyper=False, cw=False):
+    def max_batch(self, hyper=False, cw=False, clm=False):
         """realisations per launch sequence: the launch-grid limit of the mix / fused kernels (65536) and the workspace byte
         budget (coef + G0 + G per realisation: 0.68 MB at 68 pulsars, so 8 GiB hold 12 600 realisations; with per-realisation
         theta (hyper=True) also the GWB spectrum-scale row, 8 Nf bytes; with CW theta (cw=True) also the CW source row and the
         [P, 16] scalar table of pta_engine_cw_params; cw = S, an integer: a catalogue of S sources per realisation, S source rows
-        and the [P, S, 16] table of pta_engine_cw_catalog_params, whose one-launch index range R P S < 2^31 also bounds the batch)."""
+        and the [P, S, 16] table of pta_engine_cw_catalog_params, whose one-launch index range R P S < 2^31 also bounds the batch;
+        with gwb_clm in theta (clm=True) also the realisation's ORF factor [P, P] and its info word, and pta_gwb_mix_batched's one
+        workgroup row per realisation bounds the batch at 65535)."""
         per_real = 8 * self.P * ((self.K if self.plan.rn_k else 0) + 2 * self.plan.gw_npts)
         if hyper and self.plan.gw_npts:
             per_real += 8 * self.grid["Nf"]
         cap = 65536
+        if clm:
+            per_real += 8 * self.P * self.P + 4
+            cap = 65535
         if cw:
             S = 1 if cw is True else int(cw)
             if S < 1:
@@ -441,7 +452,12 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         hold one CW source per realisation (cw_* keys, pta_replicator_amd._cw), added by pta_engine_cw_add after the batch, or a
         catalogue of S sources per realisation (the same keys with shape [R, S], optional cw_count [R]), summed over the sources and
         added once by pta_engine_cw_catalog_add.  With set_bwm(), theta may hold one burst with memory per realisation (the five bwm_*
-        keys, pta_replicator_amd._bwm), added by pta_engine_bwm_add after the CW term."""
+        keys, pta_replicator_amd._bwm), added by pta_engine_bwm_add after the CW term.  On an engine configured with set_gwb(lmax=L >= 1)
+        (correlated, gwb_mode "fourier") theta may hold gwb_clm [R, (L+1)^2]: row r replaces the configured clm for realisation r0 + r
+        (column k = l^2 + m + l, correlated_basis' order), with the reference's semantics, ORF_r = 2 sum_k clm_r[k] basis[k],
+        M_r = chol(ORF_r), G_r = M_r G0_r: pta_gwb_orf_factor fills the factors ahead of each batch and pta_gwb_mix_batched mixes with
+        them.  A row whose ORF is not positive definite raises numpy.linalg.LinAlgError after the call's last batch (its realisation
+        is all NaN).  The key combines freely with every other one."""
         hyper, cw = self._theta_parts(theta, R)
         return self._generate(R, r0, out, hyper, cw)
 
@@ -452,6 +468,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         deterministic keys only.  check_values=False skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
             return None, {}
+        if _hyper.ORF_INFO_KEY in theta:   # a label of sampled theta, no parameter
+            theta = {k: v for k, v in theta.items() if k != _hyper.ORF_INFO_KEY}
         rest, cw = _cw.split(theta)
         rest, bwm = _bwm.split(rest)
         if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
@@ -463,19 +481,27 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             return None, det
         return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
 
-    def _generate(self, R, r0, out, hyper, cw, mask_unconfigured=True):
+    def _generate(self, R, r0, out, hyper, cw, mask_unconfigured=True, raise_orf=True):
         """generate() for theta resolved by _theta_parts, one launch sequence per batch: pta_engine_generate (hyper None) or
         pta_engine_generate_hyper (red-noise coefficients with sqrt(prior) per realisation -> spectrum scale -> scaled GWB transform ->
         mix -> the unchanged fused synthesis); gwb_mode "grid" queues the same stages one by one, the grid factor's product as the GWB
-        transform.  Then the CW term of cw.  mask_unconfigured: as in _theta_device."""
+        transform.  With gwb_clm in hyper pta_gwb_orf_factor is queued ahead of each batch and the mix reads its factors; info of the whole
+        call [R] is read once after the last batch and a non-zero entry raises LinAlgError (raise_orf=False: left in self._orf_info,
+        the label of generate_sampled).  Then the CW term of cw.  mask_unconfigured: as in _theta_device."""
         if not self._prepared:
             self.prepare()
         dev = None if hyper is None else self._theta_device(hyper, R, mask_unconfigured)
         if out is None:
             out = dv.empty((R, self.n_toa))
-        step = self.max_batch(hyper=hyper is not None, cw=_cw.n_sources(cw))
+        clm = None if dev is None else dev[_hyper.CLM_KEY]
+        step = self.max_batch(hyper=hyper is not None, cw=_cw.n_sources(cw), clm=clm is not None)
         ws = self.workspace(min(R, step))
         hy = None if dev is None else self._hyper_tables()
+        info = None
+        if clm is not None:
+            if "mchol" not in ws or ws["mchol"].shape[0] < ws["R"]:
+                ws["mchol"] = dv.empty((ws["R"], self.P, self.P))
+            info = self._orf_info = dv.zeros((R,), dtype=torch.int32)
         gw_theta = dev is not None and dev["gwb_log10_A"] is not None
         spec = None if dev is None else dev[_hyper.SPEC_KEY]
         if (gw_theta or spec is not None) and ("scale" not in ws or ws["scale"].shape[0] < ws["R"]):
@@ -508,6 +534,10 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
                     _lib.call("pta_gwb_spectrum_scale_user", dv.ptr(hy["spec_seg"]), dv.ptr(hy["spec_dx"]), dv.ptr(hy["spec_dxp"]),
                               dv.ptr(hy["gw_hcf0"]), Nf, M, n, at(spec, lo), M, dv.ptr(ws["scale"]), Nf, s)
                     h.gw_scale, h.ld_gw_scale = ws["scale"].data_ptr(), Nf
+                if clm is not None:    # the ORF factor of every realisation of the batch, queued ahead of the launch sequence
+                    _lib.call("pta_gwb_orf_factor", dv.ptr(self.d_orf_basis), clm.shape[1], P, at(clm, lo), clm.stride(0), n, dv.ptr(ws["mchol"]),
+                              ctypes.c_void_p(info.data_ptr() + 4 * lo), s)
+                    h.gw_mchol, h.ld_gw_mchol = ws["mchol"].data_ptr(), P * P
             if not grid_mode:
                 args = (self.seed, r0 + lo, n, optr, out.stride(0), s)
                 if h is None:
@@ -534,16 +564,22 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             self.plan.gw_G = ws["G"].data_ptr()
         if dev is not None:
             self._theta_keep = dev   # the launches above read these buffers asynchronously
+        if info is not None and raise_orf:
+            bad = torch.nonzero(info).flatten()
+            if bad.numel():
+                raise np.linalg.LinAlgError(f"Matrix is not positive definite (gwb_clm of realisation {r0 + int(bad[0])}: its ORF)")
         return self._det_apply(cw, R, out) if cw else out
 
     def _theta_device(self, th, R, mask_unconfigured=True):
         """validated theta -> contiguous float64 device tensors, keys not given filled with the configured values:
         {gwb_log10_A, gwb_gamma: [R] or None, rn_log10_A, rn_gamma: [R, P] or None, gwb_log10_hc: [R, M] or None, its columns in
-        ascending node frequency}.  Pulsars without red noise get NaN amplitudes (mask_unconfigured=False: theta of sample_theta, which
+        ascending node frequency, gwb_clm: [R, n_lm] or None}.  Pulsars without red noise get NaN amplitudes (mask_unconfigured=False: theta of sample_theta, which
         has them already)."""
         dev = dict.fromkeys(_hyper.ALL_KEYS)
         if _hyper.SPEC_KEY in th:
             dev[_hyper.SPEC_KEY] = self._spec_theta_device(th)
+        if _hyper.CLM_KEY in th:
+            dev[_hyper.CLM_KEY] = dv.as_f64(th[_hyper.CLM_KEY])
         if any(k in th for k in _hyper.GWB_KEYS):
             for k, conf in (("gwb_log10_A", self._gw["A"]), ("gwb_gamma", self._gw["g"])):
                 dev[k] = dv.as_f64(th[k]) if k in th else torch.full((R,), float(conf), dtype=torch.float64, device=dv.require_gpu())
@@ -743,14 +779,20 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self._cw_prior_dev = None
         return self
 
-    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None):
+    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None):
         """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array;
         gwb_log10_hc (needs set_gwb(userSpec=U [M, 2])): (lo, hi) for every node or [M, 2], box j for row j of U as given - a free
-        spectrum per realisation.  Parameters left out keep their configured values.  No prepare() needed after a change."""
-        self._prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma, rn_log10_A=rn_log10_A,
-                                        rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc)
+        spectrum per realisation.  gwb_clm (needs set_gwb(lmax=L >= 1)): (lo, hi) for every c_lm with l >= 1 or [(L+1)^2 - 1, 2], box j for
+        column j + 1 of gwb_clm - a sky per realisation; c_00 stays as configured.  The ORF 2 sum_k c_k basis[k] is positive
+        semidefinite when the power sum_lm c_lm Y_lm is positive over the sky, which every box with
+        sum_{l>=1} |c_lm| max|Y_lm| <= c_00 Y_00 guarantees (real harmonics: Y_00 = 1 / sqrt(4 pi), max|Y_1m| = sqrt(3 / 4 pi)); a
+        wider box may draw skies that are not, which come back flagged (generate_sampled).  Parameters left out keep their configured
+        values.  No prepare() needed after a change."""
+        self._prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
+                                        rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
         self._prior_dev = None   # device copy of the boxes, uploaded by the next sample_theta()
         self._spec_prior_dev = None
+        self._clm_prior_dev = None
         return self
 
     def generate_sampled(self, R, r0=0, out=None):
@@ -758,7 +800,10 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         (pta_hyper_uniform: uniform u2 of stream (7, 0), pair = parameter column, so theta of realisation r is a pure function of
         (seed, r) like its residuals).  theta: {key: device tensor} of the sampled keys, gwb_* [R], rn_* [R, P] (NaN for pulsars
         without red noise) - the labels of the realisations.  A sampled spectrum comes back as gwb_log10_hc [R, M], node j drawn from
-        stream (7, 1), pair j (pta_hyper_uniform_field), so the columns of stream (7, 0) and their labels do not move."""
+        stream (7, 1), pair j (pta_hyper_uniform_field), so the columns of stream (7, 0) and their labels do not move.  A sampled sky
+        comes back as gwb_clm [R, n_lm] (columns l >= 1 from stream (7, 2), pair = column; column 0 the configured c_00) with
+        gwb_orf_info [R] int32: 0, or the 1-based pivot at which the row's ORF stopped being positive definite - such a realisation is
+        all NaN and flagged, not raised."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         if prior is None and cw_prior is None and bwm_prior is None:
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
@@ -770,12 +815,30 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             raise ValueError("generate_sampled: no per-realisation burst with memory configured (set_bwm)")
         if not self._prepared:
             self.prepare()
-        theta = self.sample_theta(R, r0)
+        theta = self._sample_theta(R, r0, orf_info=False)
         hyper, cw = self._theta_parts(theta, R, check_values=False)
-        return self._generate(R, r0, out, hyper, cw, mask_unconfigured=False), theta
+        out = self._generate(R, r0, out, hyper, cw, mask_unconfigured=False, raise_orf=False)
+        if _hyper.CLM_KEY in theta:
+            theta[_hyper.ORF_INFO_KEY] = self._orf_info
+        return out, theta
 
     def sample_theta(self, R, r0=0):
-        """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses)."""
+        """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses).  With a gwb_clm
+        prior also gwb_orf_info [R] int32 (pta_gwb_orf_factor's info of every drawn sky; generate() and the statistics skip the key)."""
+        return self._sample_theta(R, r0, orf_info=True)
+
+    def _orf_info_of(self, clm):
+        """info [R] int32 of pta_gwb_orf_factor for clm [R, n_lm] on the device, factored batch by batch into a scratch buffer"""
+        R, P = clm.shape[0], self.P
+        step = min(R, self.max_batch(hyper=True, clm=True))
+        scratch, info = dv.empty((step, P, P)), dv.zeros((R,), dtype=torch.int32)
+        for lo in range(0, R, step):
+            _lib.call("pta_gwb_orf_factor", dv.ptr(self.d_orf_basis), clm.shape[1], P, dv.row_ptr(clm, lo), clm.stride(0), min(step, R - lo),
+                      dv.ptr(scratch), ctypes.c_void_p(info.data_ptr() + 4 * lo), dv.stream_ptr())
+        torch.cuda.current_stream().synchronize()   # scratch dies with the call
+        return info
+
+    def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         if prior is None and cw_prior is None and bwm_prior is None:
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
@@ -812,8 +875,19 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             _lib.call("pta_hyper_uniform_field", self.seed, r0, R, nodes.shape[1], _hyper.SPEC_FIELD, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(nodes),
                       dv.stream_ptr())
             theta[_hyper.SPEC_KEY] = nodes
-            if len(prior) == 1:
-                return theta
+        box = _hyper.clm_bounds(prior, self._gw)
+        if box is not None:        # stream (7, 2): pair j = column j of gwb_clm (column 0: the configured c_00)
+            if getattr(self, "_clm_prior_dev", None) is None:
+                self._clm_prior_dev = [dv.f64(x) for x in box]
+            d_lo, d_hi = self._clm_prior_dev
+            clm = dv.empty((R, d_lo.shape[0]))
+            _lib.call("pta_hyper_uniform_field", self.seed, r0, R, clm.shape[1], _hyper.CLM_FIELD, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(clm),
+                      dv.stream_ptr())
+            theta[_hyper.CLM_KEY] = clm
+            if orf_info:
+                theta[_hyper.ORF_INFO_KEY] = self._orf_info_of(clm)
+        if not any(k in prior for k in _hyper.KEYS):
+            return theta
         if self._prior_dev is None:
             self._prior_dev = [dv.f64(x) for x in _hyper.prior_bounds(prior, self.P)]
         table = self._uniform_table("pta_hyper_uniform", self._prior_dev, R, r0)
@@ -881,7 +955,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
-        step = self.max_batch(hyper=theta is not None, cw=_cw.n_sources(cw))
+        step = self.max_batch(hyper=theta is not None, cw=_cw.n_sources(cw), clm=hyper is not None and _hyper.CLM_KEY in hyper)
         if R > step:
             raise ValueError(f"generate_per_signal: at most {step} realisations per call (one workspace batch)")
         total = self._generate(R, r0, None, hyper, cw)       # also fills the workspace (coefficients, mixed GWB grid series)

@@ -35,12 +35,15 @@ import numpy as np
 
 from . import _hyper, _lib, device as dv
 from . import optimal_statistic as ost
+from . import red_noise as rn
+from . import spharmORFbasis as anis
 from ._position import ra_dec
 from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 
 class OptimalStatisticMixin(StatisticsMixin):
-    def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None, matched=False):
+    def prepare_optimal_statistic(self, components=14, gamma=13. / 3., orfs=ost.ORF_NAMES, timing_model="spin", gwb_auto=None, matched=False,
+                                  anisotropy_lmax=None):
         """W, Z, den and ORF weights of the array under the configured noise model (white noise + ECORR + red noise, optionally the
         GWB auto-term), uploaded once.
 
@@ -48,8 +51,22 @@ class OptimalStatisticMixin(StatisticsMixin):
         orfs: names "hd", "monopole", "dipole" or [P, P] arrays (at most 8); timing_model: "spin", "astrometric" or None;
         gwb_auto: None = the configured GWB amplitude if a GWB is set, else no GW term in C_a; a float = that log10_A; False = off.
         matched: also prepare the OS under per-realisation noise parameters (optimal_statistic(theta=...), generate_os(matched=True)):
-        K = red-noise columns + 2 n_f <= 128."""
+        K = red-noise columns + 2 n_f <= 128.
+        anisotropy_lmax = L (0 .. 8): also prepare the JOINT fit of the (L+1)^2 spherical-harmonic basis ORFs Gamma_k,ab =
+        basis[k][a, b] (spharmORFbasis.correlated_basis, the code the generation's ORF = 2 sum_k c_k basis[k] is built from, so that
+        E[rho_ab] = A^2 sum_k c_k Gamma_k,ab exactly): optimal_statistic(rows) and generate_os(R) then also return a2clm [R, n_lm], the
+        estimates of A^2 c_lm (a2clm[:, 0] / sqrt(4 pi) is the isotropic A^2 of the joint fit), clm_sigma [n_lm] and clm_cov
+        [n_lm, n_lm] (optimal_statistic.joint_weights; pta_os_pairs with the joint weights, 8 rows per call).  Needs at least
+        (L+1)^2 pairs.  The fixed-noise statistic only: not together with matched=True, and the per-frequency OS does not carry it."""
         check_components(components)
+        if anisotropy_lmax is not None:
+            if isinstance(anisotropy_lmax, bool) or not isinstance(anisotropy_lmax, (int, np.integer)) or not 0 <= anisotropy_lmax <= anis.LMAX_SUPPORTED:
+                raise ValueError(f"anisotropy_lmax={anisotropy_lmax!r}: an integer 0 .. {anis.LMAX_SUPPORTED}")
+            if matched:
+                raise ValueError("anisotropy_lmax: the joint spherical-harmonic fit belongs to the fixed-noise statistic (not with matched=True)")
+            if self.P * (self.P - 1) // 2 < (int(anisotropy_lmax) + 1) ** 2:
+                raise ValueError(f"anisotropy_lmax={anisotropy_lmax}: the joint fit of {(int(anisotropy_lmax) + 1) ** 2} ORFs needs at least as many "
+                                 f"pulsar pairs, got {self.P * (self.P - 1) // 2}")
         check_timing_model(timing_model)
         orfs = tuple(orfs) if not isinstance(orfs, str) else (orfs,)
         if not 1 <= len(orfs) <= 8:
@@ -78,7 +95,11 @@ class OptimalStatisticMixin(StatisticsMixin):
         self._os = dict(plan=plan, engine_plan=self.plan, C=plan.C, n_orf=len(plan.names), names=plan.names,
                         Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), pa=dv.i32(plan.pair_a), pb=dv.i32(plan.pair_b),
                         wt=dv.f64(plan.weights), den=dv.f64(plan.den), sigma=dv.f64(plan.sigma), sigma_pair=dv.f64(plan.sigma_pair),
-                        zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None, matched=None)
+                        zeta=dv.f64(plan.zeta), pairs=dv.i64(np.stack([plan.pair_a, plan.pair_b], axis=1)), Y=None, matched=None, aniso=None)
+        if anisotropy_lmax is not None:
+            basis = anis.correlated_basis_device(rn.pulsar_locations(self.psrs), int(anisotropy_lmax)).cpu().numpy()
+            Wj, cov, sig = ost.joint_weights(basis[:, plan.pair_a, plan.pair_b], plan.den)
+            self._os["aniso"] = dict(lmax=int(anisotropy_lmax), n_lm=len(sig), Wj_host=Wj, Wj=dv.f64(Wj), cov=dv.f64(cov), sigma=dv.f64(sig))
         if matched:
             mp = ost.prepare_matched(toas, sigma2, np.array(pos), components=int(components), gamma=float(gamma), orfs=orfs,
                                      epoch_of=epoch_of, ecorr=ecorr, F_rn=F_rn, M=M)
@@ -96,7 +117,8 @@ class OptimalStatisticMixin(StatisticsMixin):
         """OS of every realisation of rows [R, n_toa] (a float64 device tensor with unit column stride: any output of generate,
         generate_td, generate_sampled, or the caller's own residuals).  Returns a dict of device tensors: A2 [R, n_orf], snr [R, n_orf],
         sigma [n_orf], names (list); with pairs=True also rho [R, n_pairs] (= num / den), sigma_pair [n_pairs], zeta [n_pairs] and
-        pairs [n_pairs, 2] (a < b, row-major upper triangle).
+        pairs [n_pairs, 2] (a < b, row-major upper triangle).  Prepared with anisotropy_lmax: also a2clm [R, n_lm], clm_sigma [n_lm] and
+        clm_cov [n_lm, n_lm], the joint spherical-harmonic fit (not with theta: ValueError).
 
         theta (needs prepare_optimal_statistic(matched=True)): per-realisation noise parameters as generate(theta=...) takes them;
         row r is then weighted with the noise model of theta[r] (keys not given and NaN red-noise amplitudes: as configured / as
@@ -106,6 +128,7 @@ class OptimalStatisticMixin(StatisticsMixin):
         st = self._os_state("optimal_statistic")
         R = self._stats_check_rows(rows)
         if theta is not None:
+            self._os_no_aniso(st, "optimal_statistic(theta=...)")
             dev = self._os_matched_theta(st, theta, R, "optimal_statistic")
             out = self._os_matched_out(st, R, pairs)
             step = self._os_matched_chunk(st, R, with_rows=False)
@@ -113,14 +136,25 @@ class OptimalStatisticMixin(StatisticsMixin):
                 self._os_matched_launch(rows[lo:lo + step], min(step, R - lo), dev, lo, out)
             return self._os_matched_result(st, out)
         out = {"A2": dv.empty((R, st["n_orf"])), "rho": dv.empty((R, len(st["plan"].den))) if pairs else None}
-        self._os_launch(rows, R, out["A2"], out["rho"])
-        return self._os_result(st, out["A2"], out["rho"])
+        a2clm = self._os_aniso_out(st, R)
+        self._os_launch(rows, R, out["A2"], out["rho"], a2clm)
+        return self._os_result(st, out["A2"], out["rho"], a2clm)
 
-    def _os_result(self, st, A2, rho):
+    def _os_result(self, st, A2, rho, a2clm=None):
         res = {"A2": A2, "snr": A2 / st["sigma"], "sigma": st["sigma"], "names": list(st["names"])}
         if rho is not None:
             res.update(rho=rho, sigma_pair=st["sigma_pair"], zeta=st["zeta"], pairs=st["pairs"])
+        if a2clm is not None:
+            res.update(a2clm=a2clm, clm_sigma=st["aniso"]["sigma"], clm_cov=st["aniso"]["cov"])
         return res
+
+    def _os_aniso_out(self, st, R):
+        return None if st["aniso"] is None else dv.empty((R, st["aniso"]["n_lm"]))
+
+    def _os_no_aniso(self, st, what):
+        if st["aniso"] is not None:
+            raise ValueError(f"{what}: the statistic was prepared with anisotropy_lmax, and the joint spherical-harmonic fit (a2clm) belongs "
+                             "to the fixed-noise statistic alone: prepare without it")
 
     def _os_project(self, rows, R):
         """pta_os_project of rows [R, n_toa] into the reused Y buffer [>= R, P * C], on the current stream"""
@@ -131,8 +165,9 @@ class OptimalStatisticMixin(StatisticsMixin):
         self._stats_project(st["Wt"], C, st["off"], rows, R, st["Y"])
         return st["Y"]
 
-    def _os_launch(self, rows, R, A2, rho):
-        """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream"""
+    def _os_launch(self, rows, R, A2, rho, a2clm=None):
+        """pta_os_project into the reused Y buffer, then pta_os_pairs into A2 (and rho) - both on the current stream; a2clm [R, n_lm]:
+        then pta_os_pairs again with the joint weights, _lib.OS_NORF rows of them per call"""
         st = self._os
         P, C = self.P, st["C"]
         Y = self._os_project(rows, R)
@@ -141,6 +176,11 @@ class OptimalStatisticMixin(StatisticsMixin):
         _lib.call("pta_os_pairs", dv.ptr(Y), P * C, P, C, R, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.ptr(st["wt"]), st["n_orf"],
                   ctypes.c_void_p(A2.data_ptr()), A2.stride(0), dv.ptr(st["den"]) if rho is not None else None,
                   ctypes.c_void_p(rho.data_ptr()) if rho is not None else None, rho.stride(0) if rho is not None else 0, s)
+        if a2clm is not None:
+            Wj = st["aniso"]["Wj"]
+            for k0 in range(0, Wj.shape[0], _lib.OS_NORF):
+                _lib.call("pta_os_pairs", dv.ptr(Y), P * C, P, C, R, dv.ptr(st["pa"]), dv.ptr(st["pb"]), npairs, dv.row_ptr(Wj, k0),
+                          min(_lib.OS_NORF, Wj.shape[0] - k0), ctypes.c_void_p(a2clm.data_ptr() + 8 * k0), a2clm.stride(0), None, None, 0, s)
 
     def generate_os(self, R, r0=0, theta=None, td=False, chunk=1024, pairs=False, matched=False):
         """OS of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
@@ -150,7 +190,8 @@ class OptimalStatisticMixin(StatisticsMixin):
 
         matched=True (needs theta and prepare_optimal_statistic(matched=True)): every chunk's statistic is evaluated under the theta
         it was generated with - optimal_statistic(generate(R, r0, theta=theta), theta=theta), bit for bit; rows, q, b, X and Z of a
-        chunk stay within workspace_bytes."""
+        chunk stay within workspace_bytes.  The matched noise model ignores theta's gwb_clm as it ignores cw_*: its GW auto-term stays the
+        isotropic one.  Prepared with anisotropy_lmax the result also has a2clm, clm_sigma and clm_cov (not with matched=True)."""
         st = self._os_state("generate_os")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:
@@ -158,6 +199,7 @@ class OptimalStatisticMixin(StatisticsMixin):
         hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
         mdev = None
         if matched:
+            self._os_no_aniso(st, "generate_os(matched=True)")
             if theta is None:
                 raise ValueError("generate_os: matched=True needs theta (the noise parameters every realisation is evaluated under)")
             mdev = self._os_matched_theta(st, theta, R, "generate_os")
@@ -168,12 +210,13 @@ class OptimalStatisticMixin(StatisticsMixin):
         else:
             A2 = dv.empty((R, st["n_orf"]))
             rho = dv.empty((R, len(st["plan"].den))) if pairs else None
+        a2clm = None if matched else self._os_aniso_out(st, R)
         for lo, n, rows in self._os_generate_chunks("generate_os", st, R, r0, hyper, cw, td, chunk):
             if matched:
                 self._os_matched_launch(rows, n, mdev, lo, mout)
             else:
-                self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n])
-        return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho)
+                self._os_launch(rows, n, A2[lo:lo + n], None if rho is None else rho[lo:lo + n], None if a2clm is None else a2clm[lo:lo + n])
+        return self._os_matched_result(st, mout) if matched else self._os_result(st, A2, rho, a2clm)
 
     def _os_generate_chunks(self, what, st, R, r0, hyper, cw, td, chunk):
         """_stats_generate_chunks with the chunk cut so that rows and Y stay within workspace_bytes"""

@@ -312,6 +312,26 @@ def _scaled_cholesky(F):
     return Fs, L, dinv, ok
 
 
+def joint_weights(G, den):
+    """(Wj [n, n_pairs], cov [n, n], sigma [n]): the generalised-least-squares fit of n ORFs AT ONCE to the pair numerators of the
+    fixed-noise statistic.  With E[num_p] = den_p sum_k x_k G[k, p] and Var(num_p) = den_p (uncorrelated pairs), the estimate is
+    x = F^-1 G num, F = G diag(den) G^T, Cov(x) = F^-1: x = num @ Wj.T with Wj = F^-1 G.  For the spherical-harmonic basis ORFs
+    G[k] = basis[k][a, b] (spharmORFbasis.correlated_basis, the generation's own code) x_k estimates A^2 c_lm.  F is solved
+    Jacobi-scaled (_scaled_cholesky).  Refuses fewer pairs than ORFs and an F that is not positive definite (to rounding)."""
+    G, den = np.asarray(G, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    n, n_pairs = G.shape
+    if n_pairs < n:
+        raise ValueError(f"the joint fit of {n} ORFs needs at least as many pulsar pairs, got {n_pairs}")
+    F = (G * den[None, :]) @ G.T
+    _, L, dinv, ok = (x[0] for x in _scaled_cholesky(F[None]))
+    # (the scaled F has a unit diagonal: a squared pivot at rounding level means ORFs that are collinear on this array's pairs)
+    if not bool(ok) or not np.all(np.isfinite(L)) or np.min(np.diagonal(L)) ** 2 < 1e-13:
+        raise ValueError(f"the joint fit of {n} ORFs is singular for this array (F = G diag(den) G^T is not positive definite)")
+    Minv = np.linalg.solve(L, np.eye(n))            # L^-1 of the scaled factor
+    cov = dinv[:, None] * (Minv.T @ Minv) * dinv[None, :]
+    return cov @ G, cov, np.sqrt(np.diagonal(cov))
+
+
 def spectrum_solve(F, b, mode="full", form="cholesky"):
     """(a2 [..., n_f], sigma) of F [..., n_f, n_f] and b [..., n_f] (leading axes broadcast; sigma has F's).  form "cholesky" is
     what the device evaluates (M = L^-1 of the scaled factor, a2 = d^-1/2 M^T M d^-1/2 b); "solve" goes through np.linalg.solve / inv

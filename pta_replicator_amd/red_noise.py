@@ -204,11 +204,17 @@ def gwb_orf_device(psrs, no_correlations=False, clm=(np.sqrt(4.0 * np.pi),), lma
     P = len(psrs)
     if no_correlations:
         return dv.f64(np.diag(np.ones(P) * 2))
+    return anis.orf_from_locations(pulsar_locations(psrs), clm, lmax)
+
+
+def pulsar_locations(psrs):
+    """psrlocs [P, 2] = (phi, colatitude) of the pulsars as the ORF basis takes them (red_noise.py:200-210)"""
+    P = len(psrs)
     psrlocs = np.zeros((P, 2))
     for ii in range(P):
         psrlocs[ii] = ra_dec(psrs[ii], default=(0.0, 0.0))   # no location: stays (0, 0), like red_noise.py:203
     psrlocs[:, 1] = np.pi / 2.0 - psrlocs[:, 1]
-    return anis.orf_from_locations(psrlocs, clm, lmax)
+    return psrlocs
 
 
 def cholesky_device(A, flags=0, auto_substitution=True):
