@@ -50,7 +50,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * deviate is Philox-4x32-10(key = seed, counter = (pair, stream, realisation)) + Box-Muller.
  * stream ids: (kind << 24) | pulsar, kind = 1 GWB, 2 RN, 3 WN, 4 ECORR, 5 TD (N_a x N_a factor), 6 TDGW (GWB grid factor),
  * 7 HYPER (pulsar field 0: per-realisation hyperparameters, pair j = parameter column, uniform u2; pta_hyper_uniform.  Field 1: the
- * nodes of a per-realisation GWB spectrum, pair j = node j; pta_hyper_uniform_field),
+ * nodes of a per-realisation GWB spectrum, pair j = node j; pta_hyper_uniform_field.  Fields 3, 4, 5: per-realisation EFAC, log10
+ * EQUAD and log10 ECORR, pair j = white-noise / ECORR group j; pta_hyper_uniform_field),
  * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform.  In a catalogue the
  * field is the source index s, pta_cw_catalog_uniform),
  * 9 BWM (pulsar field 0: per-realisation burst-with-memory labels, pair j = label column, uniform u2; pta_bwm_uniform). */
@@ -591,6 +592,50 @@ int pta_engine_bwm_params(const pta_bwm_engine *bwm_host, int R, void *stream);
  * only.  Nothing outside the tiles' columns is touched.  No atomics.                                                            */
 int pta_engine_bwm_add(const pta_engine_plan *plan_host, const pta_bwm_engine *bwm_host, int R, double *out, int64_t ld_out, int accumulate,
                        void *stream);
+
+/* ---------------------------------------------------------------- white-noise parameters per realisation (ABI 8, additive) */
+/* EFAC / EQUAD / ECORR of every (realisation, group) of a batch; a group is a (pulsar, backend flag) pair, groups ordered pulsar-major,
+ * so the groups of one pulsar are contiguous.  The fused synthesis runs without the terms given here (plan.wn_a / wn_b, plan.ecorr_toa /
+ * epoch_of NULL) and pta_engine_wn_add redraws their deviates - same stream, same counter - with the realisation's own amplitudes
+ * (white_noise.py:105-109, :182).  Device pointers.                                                                              */
+#define PTA_WN_HYPER_GMAX 16  /* groups of one pulsar (of either kind) pta_engine_wn_add can stage */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_wn;               /* G_wn: EFAC / EQUAD groups, the columns of ea / eb */
+  int32_t n_ec;               /* G_ec: ECORR groups, the columns of ec */
+  int32_t tnequad;            /* 1: eb = equad, 0: eb = efac equad */
+  int32_t max_per_psr;        /* the caller's bound on the groups of one pulsar, of either kind: <= PTA_WN_HYPER_GMAX */
+  const double *sigma;        /* [n_toa] TOA errors [s] */
+  const int32_t *wn_group;    /* [n_toa] EFAC / EQUAD group of the TOA, -1 = none (amplitudes 0) */
+  const int32_t *ec_group;    /* [n_toa] ECORR group of the TOA's epoch, -1 = none (amplitude 0) */
+  const int32_t *wn_psr0;     /* [n_psr + 1] first EFAC / EQUAD group of every pulsar */
+  const int32_t *ec_psr0;     /* [n_psr + 1] first ECORR group of every pulsar */
+  const double *efac_conf;    /* [n_wn] configured efac */
+  const double *equad_conf;   /* [n_wn] configured equad [s] (0 = none) */
+  const double *ecorr_conf;   /* [n_ec] configured ecorr [s] */
+  const double *efac;         /* [R x ld_efac] labels of realisation r0 + r, NaN = as configured; NULL = all as configured */
+  int64_t ld_efac;
+  const double *log10_equad;  /* [R x ld_equad] likewise */
+  int64_t ld_equad;
+  const double *log10_ecorr;  /* [R x ld_ecorr] likewise */
+  int64_t ld_ecorr;
+  double *ea;                 /* [R x n_wn] efac, written by pta_engine_wn_params; NULL (with eb) = no EFAC / EQUAD term */
+  double *eb;                 /* [R x n_wn] efac 10^log10_equad, or 10^log10_equad with tnequad */
+  double *ec;                 /* [R x n_ec] 10^log10_ecorr; NULL = no ECORR term */
+} pta_engine_wn_hyper;
+
+/* The amplitude tables of R realisations from the labels and the configured values (ea, eb where ea is given, ec where ec is).  One
+ * thread per (r, group); every pow of the path is here.                                                                          */
+int pta_engine_wn_params(const pta_engine_wn_hyper *wn_host, int R, void *stream);
+
+/* out[r * ld_out + i] = (out[r * ld_out + i] + (ea[r, g(i)] sigma[i] z1 + eb[r, g(i)] z2)) + ec[r, h(i)] z_e for r < R (accumulate = 1;
+ * 0 writes the terms alone), over the plan's TOA tiles (tile_*, n_tiles, n_psr, n_toa, idx_in_psr, epoch_of and rng_fast are read,
+ * nothing else of the plan).  (z1, z2) = pair idx_in_psr[i] of stream (WN, a), z_e = deviate epoch_of[i] of stream (ECORR, a) of
+ * realisation r0 + r: the deviates of pta_engine_synth.  A term whose table is NULL is left out.  Two adjacent TOAs per lane and
+ * 16-byte accesses wherever the row's address allows; out and ld_out need 8-byte alignment only.  Nothing outside the tiles' columns
+ * is touched.  No atomics.                                                                                                       */
+int pta_engine_wn_add(const pta_engine_plan *plan_host, const pta_engine_wn_hyper *wn_host, uint64_t seed, uint64_t r0, int R, double *out,
+                      int64_t ld_out, int accumulate, void *stream);
 
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,

@@ -94,6 +94,17 @@ class BwmEngine(ctypes.Structure):
     ]
 
 
+class WnHyper(ctypes.Structure):
+    """pta_engine_wn_hyper (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_wn", c_int32), ("n_ec", c_int32), ("tnequad", c_int32), ("max_per_psr", c_int32),
+        ("sigma", _P), ("wn_group", _P), ("ec_group", _P), ("wn_psr0", _P), ("ec_psr0", _P),
+        ("efac_conf", _P), ("equad_conf", _P), ("ecorr_conf", _P),
+        ("efac", _P), ("ld_efac", c_int64), ("log10_equad", _P), ("ld_equad", c_int64), ("log10_ecorr", _P), ("ld_ecorr", c_int64),
+        ("ea", _P), ("eb", _P), ("ec", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -158,6 +169,8 @@ _SIGNATURES = {
     "pta_bwm_uniform": (c_int, [c_uint64, c_uint64, c_int, _P, _P, _P, _P]),
     "pta_engine_bwm_params": (c_int, [POINTER(BwmEngine), c_int, _P]),
     "pta_engine_bwm_add": (c_int, [POINTER(EnginePlan), POINTER(BwmEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_engine_wn_params": (c_int, [POINTER(WnHyper), c_int, _P]),
+    "pta_engine_wn_add": (c_int, [POINTER(EnginePlan), POINTER(WnHyper), c_uint64, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
@@ -197,6 +210,7 @@ ENGINE_TILE = 256   # PTA_ENGINE_TILE
 ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX
 CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 CW_CATALOG_NPAR = (16, 8, 8)  # by mode: PTA_CW_CATALOG_NPAR_EVOLVE, PTA_CW_CATALOG_NPAR_FOLDED (phase_approx, monochromatic)
+WN_HYPER_GMAX = 16   # PTA_WN_HYPER_GMAX
 OS_CMAX = 64         # PTA_OS_CMAX
 OS_NORF = 8          # PTA_OS_NORF: ORFs (weight rows) of one pta_os_pairs call
 OSM_KMAX = 128       # PTA_OSM_KMAX

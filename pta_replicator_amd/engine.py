@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _cw, _hyper, _lib, device as dv
+from . import _bwm, _cw, _hyper, _lib, _wn_hyper, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -40,7 +40,8 @@ from .engine_td import TimeDomainMixin
 STREAM_GWB, STREAM_RN, STREAM_WN, STREAM_ECORR, STREAM_TD, STREAM_TDGW = 1, 2, 3, 4, 5, 6
 STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_id(7, 0), pair = parameter column (_hyper.columns);
                    # stream_id(7, 1), pair = node: the per-realisation GWB spectrum (_hyper.SPEC_KEY);
-                   # stream_id(7, 2), pair = column: the per-realisation angular power coefficients (_hyper.CLM_KEY)
+                   # stream_id(7, 2), pair = column: the per-realisation angular power coefficients (_hyper.CLM_KEY);
+                   # stream_id(7, 3 .. 5), pair = group: the per-realisation EFAC, log10 EQUAD and log10 ECORR (_wn_hyper.FIELD)
 STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream_id(8, 0), pair = label column (_cw.COLUMNS)
 STREAM_BWM = 9     # per-realisation burst-with-memory labels (generate_sampled): stream_id(9, 0), pair = label column (_bwm.COLUMNS)
 
@@ -155,6 +156,16 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self._prepared = False
 
     # ---------------------------------------------------------------- helpers -------------------
+    @property
+    def wn_groups(self):
+        """[(pulsar index, flag or None)]: the white-noise groups, the columns of theta's wn_efac / wn_log10_equad (_wn_hyper)"""
+        return _wn_hyper.wn_groups(self.P, self._wn)
+
+    @property
+    def ecorr_groups(self):
+        """[(pulsar index, flag or None)]: the ECORR groups, the columns of theta's wn_log10_ecorr (_wn_hyper)"""
+        return _wn_hyper.ecorr_groups(self.P, self._ec)
+
     def _flag_array(self, a, flagid):
         return np.array([f[flagid] for f in self.psrs[a].toas.table["flags"].data])
 
@@ -163,6 +174,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         dev = dv.require_gpu()
         self._ws = None  # tables of a previous prepare() point at replaced buffers
         self._hy = None  # and the hyper path's tables describe the previous configuration
+        self._wnh = None  # and so do the group tables of the per-realisation white noise
         self._td_prepared = False  # and so do the dense factors of TD mode
         self._gw_grid_ready = False
         s = dv.stream_ptr()
@@ -243,7 +255,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         if self._ec is not None:
             c = self._ec
             ep_all, ec_all = np.zeros(N, dtype=np.int32), np.zeros(N)
-            self.epoch_of, self.ecorrvec = [], []
+            self.epoch_of, self.epoch_first, self.ecorrvec = [], [], []
             for a in range(P):
                 l10 = self._pick(c["log10_ecorr"], a)
                 flags = self._pick_flags(c["flags"], a)
@@ -264,6 +276,7 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
                     for ct, flag in enumerate(flags):
                         vec[flag == aveflags] = ecorr[ct]
                 self.epoch_of.append(epoch_of)
+                self.epoch_first.append(np.asarray(first))
                 self.ecorrvec.append(vec)
                 sl = slice(self.off[a], self.off[a + 1])
                 ep_all[sl] = epoch_of
@@ -457,26 +470,40 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         (column k = l^2 + m + l, correlated_basis' order), with the reference's semantics, ORF_r = 2 sum_k clm_r[k] basis[k],
         M_r = chol(ORF_r), G_r = M_r G0_r: pta_gwb_orf_factor fills the factors ahead of each batch and pta_gwb_mix_batched mixes with
         them.  A row whose ORF is not positive definite raises numpy.linalg.LinAlgError after the call's last batch (its realisation
-        is all NaN).  The key combines freely with every other one."""
+        is all NaN).  The key combines freely with every other one.  On an engine configured with set_white_noise / set_jitter
+        (wn_mode "reference") theta may hold the white-noise parameters of every group: wn_efac [R, G_wn], wn_log10_equad [R, G_wn],
+        wn_log10_ecorr [R, G_ec] (pta_replicator_amd._wn_hyper; the columns are engine.wn_groups / engine.ecorr_groups, (pulsar, flag)
+        pairs, pulsar-major).  Each entry replaces the configured value of its group for realisation r0 + r, NaN = as configured; a key
+        given alone leaves the other parameters as configured, tnequad keeps its configured meaning, and a TOA (or epoch) whose flag is
+        in no listed group keeps amplitude 0.  The fused launch then runs without the terms that have a key and pta_engine_wn_add
+        redraws the same deviates (same stream, same counter: dump_draws is unchanged) with the realisation's own amplitudes, ahead
+        of the CW / BWM terms.  Fixed-noise statistics evaluated on such realisations (generate_os and the other generate_* with these
+        keys in the generation theta) weight with the configured white noise, as they do for red-noise keys; as a statistic's noise
+        model (optimal_statistic(theta=), matched=True, likelihood grids), in TD mode and in wn_mode "single" the keys are refused."""
         hyper, cw = self._theta_parts(theta, R)
         return self._generate(R, r0, out, hyper, cw)
 
     def _theta_parts(self, theta, R, td=False, check_values=True):
         """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
-        (_hyper.check_theta), None for the fixed-parameter path (no theta, or deterministic keys alone); det: its deterministic keys,
-        the CW keys (_cw.check_theta) and the BWM keys (_bwm.check_theta) in one dict, {} if none.  td=True: TD mode, which takes
-        deterministic keys only.  check_values=False skips the value checks (theta drawn by sample_theta)."""
+        (_hyper.check_theta), None for the fixed-parameter path (no theta, or the keys of det alone); det: the keys whose terms are
+        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta) and the white-noise keys
+        (_wn_hyper.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
+        skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
             return None, {}
         if _hyper.ORF_INFO_KEY in theta:   # a label of sampled theta, no parameter
             theta = {k: v for k, v in theta.items() if k != _hyper.ORF_INFO_KEY}
-        rest, cw = _cw.split(theta)
+        rest, wnk = _wn_hyper.split(theta)   # ahead of _hyper.check_theta, whose key list stays the GWB / red-noise one
+        rest, cw = _cw.split(rest)
         rest, bwm = _bwm.split(rest)
+        if td:
+            _wn_hyper.refuse_td(wnk)
         if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
                              "cw_* and bwm_* keys are): use generate(theta=...) or generate_sampled()")
         det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
         det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
+        det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
         if det and not rest:
             return None, det
         return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
@@ -487,7 +514,9 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         mix -> the unchanged fused synthesis); gwb_mode "grid" queues the same stages one by one, the grid factor's product as the GWB
         transform.  With gwb_clm in hyper pta_gwb_orf_factor is queued ahead of each batch and the mix reads its factors; info of the whole
         call [R] is read once after the last batch and a non-zero entry raises LinAlgError (raise_orf=False: left in self._orf_info,
-        the label of generate_sampled).  Then the CW term of cw.  mask_unconfigured: as in _theta_device."""
+        the label of generate_sampled).  With white-noise keys in cw the fused launch runs on a private plan copy without the terms that have a
+        key, and pta_engine_wn_params + pta_engine_wn_add follow it batch by batch (_wn_add).  Then the CW / BWM terms of cw.
+        mask_unconfigured: as in _theta_device."""
         if not self._prepared:
             self.prepare()
         dev = None if hyper is None else self._theta_device(hyper, R, mask_unconfigured)
@@ -514,6 +543,15 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         s = dv.stream_ptr()
         P = self.P
         at = dv.row_ptr
+        plan = self._plan_for_mode()
+        wdev = None
+        if _wn_hyper.has_keys(cw):   # the terms that have a key leave the fused launch: a private plan copy, the shared one is never mutated
+            wdev = self._wn_theta_device(cw, R)
+            plan = _lib.EnginePlan.from_buffer_copy(self.plan)
+            if wdev["wn"]:
+                plan.wn_a = plan.wn_b = None
+            if wdev["ecorr"]:
+                plan.ecorr_toa = plan.epoch_of = None
         for lo in range(0, R, step):
             n = min(step, R - lo)
             optr = at(out, lo)
@@ -541,11 +579,13 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             if not grid_mode:
                 args = (self.seed, r0 + lo, n, optr, out.stride(0), s)
                 if h is None:
-                    _lib.call("pta_engine_generate", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), *args)
+                    _lib.call("pta_engine_generate", ctypes.byref(plan), ctypes.byref(ws["tables"]), *args)
                 else:
-                    _lib.call("pta_engine_generate_hyper", ctypes.byref(self._plan_for_mode()), ctypes.byref(ws["tables"]), ctypes.byref(h), *args)
+                    _lib.call("pta_engine_generate_hyper", ctypes.byref(plan), ctypes.byref(ws["tables"]), ctypes.byref(h), *args)
+                if wdev is not None:
+                    self._wn_add(wdev, lo, n, r0 + lo, optr, out.stride(0))
                 continue
-            pl = _lib.EnginePlan.from_buffer_copy(self._plan_for_mode())    # grid mode: RN theta only (check_config)
+            pl = _lib.EnginePlan.from_buffer_copy(plan)    # grid mode: RN theta only (check_config)
             if pl.rn_k:
                 if h is not None and h.rn_log10_A:
                     _lib.call("pta_engine_rn_coef_hyper", self.seed, r0 + lo, n, P, self.K, h.rn_f, h.rn_tspan, h.rn_log10_A, h.rn_gamma,
@@ -557,6 +597,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             _lib.call("pta_gwb_mix", dv.ptr(self.d_M), P, dv.ptr(ws["G0"]), n, pl.gw_npts, pl.gw_npts, dv.ptr(ws["G"]), int(self.mix_variant), s)
             pl.gw_G = ws["G"].data_ptr()
             _lib.call("pta_engine_synth", ctypes.byref(pl), self.seed, r0 + lo, n, optr, out.stride(0), s)
+            if wdev is not None:
+                self._wn_add(wdev, lo, n, r0 + lo, optr, out.stride(0))
         # per-kernel callers (bench.py, replay) read the workspace pointers from the plan
         if self.plan.rn_k:
             self.plan.rn_coef = ws["coef"].data_ptr()
@@ -564,6 +606,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             self.plan.gw_G = ws["G"].data_ptr()
         if dev is not None:
             self._theta_keep = dev   # the launches above read these buffers asynchronously
+        if wdev is not None:
+            self._wn_keep = wdev
         if info is not None and raise_orf:
             bad = torch.nonzero(info).flatten()
             if bad.numel():
@@ -650,6 +694,86 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         if _bwm.has_keys(det):
             self._bwm_apply(det, R, out)
         return out
+
+    def _wn_tables(self):
+        """theta-independent device tables of the per-realisation white noise, built once per prepare(): sigma [n_toa], the white-noise
+        group of every TOA and the ECORR group of every TOA's epoch (an epoch's flag is its first TOA's; -1 = in no group), the first
+        group of every pulsar, and the configured efac / equad [s] / ecorr [s] of every group as prepare() computed them."""
+        if self._wnh is not None:
+            return self._wnh
+        P, N = self.P, self.n_toa
+
+        def flags_of(conf, a, idx):
+            """flag values of TOAs idx of pulsar a; a pulsar that is its own group (flags None) reads no flags"""
+            if _wn_hyper._pick_flags(conf["flags"], a, P) is None:
+                return np.zeros(len(idx))
+            return self._flag_array(a, conf["flagid"])[idx]
+        t = {"sigma": dv.f64(np.concatenate(self.sigma_s)), "n_wn": 0, "n_ec": 0, "tnequad": 0, "max_per_psr": 1}
+        if self._wn is not None:
+            groups = self.wn_groups
+            grp = np.concatenate([_wn_hyper.toa_groups(groups, a, flags_of(self._wn, a, np.arange(int(self.counts[a])))) for a in range(P)])
+            efac, equad = _wn_hyper.configured_wn(P, self._wn)
+            psr0 = _wn_hyper.psr_offsets(P, groups)
+            t.update(n_wn=len(groups), wn_group=dv.i32(grp), wn_psr0=dv.i32(psr0), efac_conf=dv.f64(efac), equad_conf=dv.f64(equad),
+                     tnequad=int(self._wn["tnequad"]))
+            t["max_per_psr"] = max(t["max_per_psr"], int(np.diff(psr0).max()))
+        if self._ec is not None and self.ecorr_groups:
+            groups = self.ecorr_groups
+            grp = np.full(N, -1, dtype=np.int32)
+            for a in range(P):   # an epoch's flag is its first TOA's (white_noise.py:35)
+                of_epoch = _wn_hyper.toa_groups(groups, a, flags_of(self._ec, a, self.epoch_first[a]))
+                grp[self.off[a]:self.off[a + 1]] = of_epoch[self.epoch_of[a]]
+            psr0 = _wn_hyper.psr_offsets(P, groups)
+            t.update(n_ec=len(groups), ec_group=dv.i32(grp), ec_psr0=dv.i32(psr0), ecorr_conf=dv.f64(_wn_hyper.configured_ecorr(P, self._ec)))
+            t["max_per_psr"] = max(t["max_per_psr"], int(np.diff(psr0).max()))
+        self._wnh = t
+        return t
+
+    def _wn_theta_device(self, det, R):
+        """validated white-noise keys of theta -> {"efac", "equad", "log10_ecorr": contiguous float64 device tensor [R, G] or None (key
+        not given: as configured), "wn", "ecorr": whether the EFAC / EQUAD term and the ECORR term have a key}"""
+        get = lambda k: dv.as_f64(det[k]) if k in det else None   # noqa: E731
+        return {"efac": get(_wn_hyper.EFAC_KEY), "equad": get(_wn_hyper.EQUAD_KEY), "log10_ecorr": get(_wn_hyper.ECORR_KEY),
+                "wn": _wn_hyper.has_wn(det), "ecorr": _wn_hyper.has_ecorr(det)}
+
+    def _wn_add(self, wdev, lo, n, r_first, optr, ld_out, accumulate=True, wn=True, ecorr=True):
+        """rows lo .. lo+n-1 of theta's white-noise labels `wdev` (_wn_theta_device) -> pta_engine_wn_params (the amplitude tables ea, eb
+        [n, G_wn], ec [n, G_ec]) -> pta_engine_wn_add into the n rows at optr (realisations r_first ..): the EFAC / EQUAD term where
+        theta has one of its keys (and wn), the ECORR term where it has that key (and ecorr); accumulate=False writes the terms alone
+        (generate_per_signal).  The tables are n (2 G_wn + G_ec) doubles and stay outside the workspace budget, like the BWM tables."""
+        w = self._wn_struct(wdev, lo, n, wn, ecorr)
+        if w is None:
+            return
+        s = dv.stream_ptr()
+        _lib.call("pta_engine_wn_params", ctypes.byref(w), n, s)
+        _lib.call("pta_engine_wn_add", ctypes.byref(self.plan), ctypes.byref(w), self.seed, r_first, n, optr, ld_out, 1 if accumulate else 0, s)
+
+    def _wn_struct(self, wdev, lo, n, wn=True, ecorr=True):
+        """the pta_engine_wn_hyper of rows lo .. lo+n-1 of `wdev` with the terms asked for that theta has a key of (None: neither);
+        its amplitude tables are the engine's reused buffers, grown on demand"""
+        t = self._wn_tables()
+        wn, ecorr = wn and wdev["wn"], ecorr and wdev["ecorr"]
+        if not (wn or ecorr):
+            return None
+        tab = getattr(self, "_wn_amp", None)
+        if tab is None or tab[0].shape[0] < n or tab[0].shape[1] != t["n_wn"] or tab[2].shape[1] != t["n_ec"]:
+            self._wn_amp = None
+            tab = self._wn_amp = (dv.empty((n, t["n_wn"])), dv.empty((n, t["n_wn"])), dv.empty((n, t["n_ec"])))
+        w = _lib.WnHyper()
+        w.n_psr, w.n_wn, w.n_ec, w.tnequad, w.max_per_psr = self.P, t["n_wn"], t["n_ec"], t["tnequad"], t["max_per_psr"]
+        w.sigma = t["sigma"].data_ptr()
+        if wn:
+            w.wn_group, w.wn_psr0, w.efac_conf, w.equad_conf = (t[k].data_ptr() for k in ("wn_group", "wn_psr0", "efac_conf", "equad_conf"))
+            for name, ld, key in (("efac", "ld_efac", "efac"), ("log10_equad", "ld_equad", "equad")):
+                if wdev[key] is not None:
+                    setattr(w, name, dv.row_ptr(wdev[key], lo))
+                    setattr(w, ld, wdev[key].stride(0))
+            w.ea, w.eb = tab[0].data_ptr(), tab[1].data_ptr()
+        if ecorr:
+            w.ec_group, w.ec_psr0, w.ecorr_conf = (t[k].data_ptr() for k in ("ec_group", "ec_psr0", "ecorr_conf"))
+            w.log10_ecorr, w.ld_ecorr = dv.row_ptr(wdev["log10_ecorr"], lo), wdev["log10_ecorr"].stride(0)
+            w.ec = tab[2].data_ptr()
+        return w
 
     def _bwm_apply(self, det, R, out, accumulate=True):
         """out[R, n_toa] (+)= the burst-with-memory term of every row for validated theta `det` (row r = the burst of realisation
@@ -779,17 +903,25 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         self._cw_prior_dev = None
         return self
 
-    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None):
+    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None,
+                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None):
         """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array;
         gwb_log10_hc (needs set_gwb(userSpec=U [M, 2])): (lo, hi) for every node or [M, 2], box j for row j of U as given - a free
         spectrum per realisation.  gwb_clm (needs set_gwb(lmax=L >= 1)): (lo, hi) for every c_lm with l >= 1 or [(L+1)^2 - 1, 2], box j for
         column j + 1 of gwb_clm - a sky per realisation; c_00 stays as configured.  The ORF 2 sum_k c_k basis[k] is positive
         semidefinite when the power sum_lm c_lm Y_lm is positive over the sky, which every box with
         sum_{l>=1} |c_lm| max|Y_lm| <= c_00 Y_00 guarantees (real harmonics: Y_00 = 1 / sqrt(4 pi), max|Y_1m| = sqrt(3 / 4 pi)); a
-        wider box may draw skies that are not, which come back flagged (generate_sampled).  Parameters left out keep their configured
-        values.  No prepare() needed after a change."""
-        self._prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
-                                        rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
+        wider box may draw skies that are not, which come back flagged (generate_sampled).  wn_efac, wn_log10_equad (need
+        set_white_noise) and wn_log10_ecorr (needs set_jitter): (lo, hi) for every group or [G, 2], G = len(wn_groups) or
+        len(ecorr_groups), box j for group j.  Parameters left out keep their configured values.  No prepare() needed after a change."""
+        wn_prior = _wn_hyper.make_prior(len(self.wn_groups), len(self.ecorr_groups), wn_efac=wn_efac, wn_log10_equad=wn_log10_equad,
+                                        wn_log10_ecorr=wn_log10_ecorr) or None
+        prior = None   # (white-noise boxes alone are a prior; nothing at all is _hyper.make_prior's "no parameter given")
+        if wn_prior is None or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
+            prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
+                                      rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
+        self._prior, self._wn_prior = prior, wn_prior
+        self._wn_prior_dev = None
         self._prior_dev = None   # device copy of the boxes, uploaded by the next sample_theta()
         self._spec_prior_dev = None
         self._clm_prior_dev = None
@@ -803,12 +935,16 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         stream (7, 1), pair j (pta_hyper_uniform_field), so the columns of stream (7, 0) and their labels do not move.  A sampled sky
         comes back as gwb_clm [R, n_lm] (columns l >= 1 from stream (7, 2), pair = column; column 0 the configured c_00) with
         gwb_orf_info [R] int32: 0, or the 1-based pivot at which the row's ORF stopped being positive definite - such a realisation is
-        all NaN and flagged, not raised."""
+        all NaN and flagged, not raised.  Sampled white noise comes back as wn_efac, wn_log10_equad [R, G_wn] and wn_log10_ecorr
+        [R, G_ec], group j drawn from stream (7, 3), (7, 4), (7, 5), pair j: no other label or residual moves."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None:
+        wn_prior = getattr(self, "_wn_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None:
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if prior is not None:
             _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
+        if wn_prior is not None:
+            _wn_hyper.check_config(wn_prior.keys(), self.P, self._wn, self._ec, self.wn_mode)
         if cw_prior is not None and self._cw is None:
             raise ValueError("generate_sampled: no per-realisation CW configured (set_cw)")
         if bwm_prior is not None and not self._bwm:
@@ -840,7 +976,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
 
     def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None:
+        wn_prior = getattr(self, "_wn_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None:
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
@@ -864,6 +1001,18 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
                 d_lo, d_hi = self._cw_prior_dev
                 _lib.call("pta_cw_catalog_uniform", self.seed, r0, R, S, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(catalog), dv.stream_ptr())
             theta.update(_cw.labels(table, cw_prior, self.P, catalog))
+        if wn_prior is not None:   # streams (7, 3 .. 5): pair j = group j, whatever else is sampled
+            if self._wn_prior_dev is None:
+                self._wn_prior_dev = {k: [dv.f64(x) for x in box] for k, box in wn_prior.items()}
+            n_groups = {k: len(self.ecorr_groups if k == _wn_hyper.ECORR_KEY else self.wn_groups) for k in wn_prior}
+            for k, (d_lo, d_hi) in self._wn_prior_dev.items():
+                if d_lo.shape[0] != n_groups[k]:
+                    raise ValueError(f"sample_theta: the {k} boxes are for {d_lo.shape[0]} groups but the engine now has {n_groups[k]}: "
+                                     "call set_hyper_prior again")
+                labels = dv.empty((R, d_lo.shape[0]))
+                _lib.call("pta_hyper_uniform_field", self.seed, r0, R, labels.shape[1], _wn_hyper.FIELD[k], dv.ptr(d_lo), dv.ptr(d_hi),
+                          dv.ptr(labels), dv.stream_ptr())
+                theta[k] = labels
         if prior is None:
             return theta
         box = _hyper.spec_bounds(prior)
@@ -951,7 +1100,8 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
         switched off reproduces exactly the deviates of the combined pass.  theta: per-realisation parameters as in generate(); with
         CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer; for a catalogue the
         sum over its sources, pta_engine_cw_catalog_add); with BWM keys 'bwm', the per-realisation burst-with-memory term alone
-        (pta_engine_bwm_add writing its own buffer)."""
+        (pta_engine_bwm_add writing its own buffer); with white-noise keys (wn_efac / wn_log10_equad, wn_log10_ecorr) 'wn' and 'ecorr' are the
+        per-realisation terms (pta_engine_wn_add writing its own buffer)."""
         hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
@@ -976,10 +1126,20 @@ class ReplicaEngine(TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FSt
             one("rn", rn_k=keep[0])
         if keep[1]:
             one("gwb", gw_npts=keep[1])
-        if keep[2] or keep[7]:
+        wdev = self._wn_theta_device(cw, R) if _wn_hyper.has_keys(cw) else {"wn": False, "ecorr": False}
+
+        def one_wn(name, **term):   # a term with a key in theta: the per-realisation term, pta_engine_wn_add writing its own buffer
+            out[name] = dv.empty((R, self.n_toa))
+            self._wn_add(wdev, 0, R, r0, dv.ptr(out[name]), out[name].stride(0), accumulate=False, **term)
+        if wdev["wn"]:
+            one_wn("wn", ecorr=False)
+        elif keep[2] or keep[7]:
             one("wn", wn_a=keep[2], wn_b=keep[3], wn_c=keep[7])
-        if keep[4]:
+        if wdev["ecorr"]:
+            one_wn("ecorr", wn=False)
+        elif keep[4]:
             one("ecorr", ecorr_toa=keep[4], epoch_of=keep[5])
+        self._wn_keep = wdev
         if keep[6]:
             out["det"] = self.d_det.unsqueeze(0).expand(R, self.n_toa)
         if _cw.has_keys(cw):

@@ -186,12 +186,14 @@ class OptimalStatisticMixin(StatisticsMixin):
         """OS of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
         td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations, e.g. sample_theta(R, r0)); only
         the statistics are kept.  Same results as optimal_statistic(generate(R, r0, ...)), bit for bit, whatever the chunk.  The chunk
-        is cut so that the buffer stays within workspace_bytes.
+        is cut so that the buffer stays within workspace_bytes.  With white-noise keys (wn_efac, wn_log10_equad, wn_log10_ecorr) in theta
+        the realisations carry them and the statistic weights with the configured white noise, as it does for red-noise keys.
 
         matched=True (needs theta and prepare_optimal_statistic(matched=True)): every chunk's statistic is evaluated under the theta
         it was generated with - optimal_statistic(generate(R, r0, theta=theta), theta=theta), bit for bit; rows, q, b, X and Z of a
         chunk stay within workspace_bytes.  The matched noise model ignores theta's gwb_clm as it ignores cw_*: its GW auto-term stays the
-        isotropic one.  Prepared with anisotropy_lmax the result also has a2clm, clm_sigma and clm_cov (not with matched=True)."""
+        isotropic one; it refuses the white-noise keys (its per-TOA weights are built once, from the configured white noise).  Prepared
+        with anisotropy_lmax the result also has a2clm, clm_sigma and clm_cov (not with matched=True)."""
         st = self._os_state("generate_os")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:
