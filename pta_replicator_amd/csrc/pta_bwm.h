@@ -13,10 +13,6 @@
 #include <math.h>
 #include "pta_rng.h"
 
-// stream kind 9, next to the kinds of pta_rng.h (which bench.py hashes with the synthesis kernel's sources, so it stays as it is):
-// pulsar field 0 = the per-realisation burst labels, pair p = label column j, uniform u2
-#define PTA_STREAM_BWM 9u
-
 // columns of the per-realisation burst table (the labels, and the pairs of stream (BWM, 0) that draw them)
 #define PTA_BWM_COL_COS_GWTHETA 0
 #define PTA_BWM_COL_GWPHI 1
@@ -27,9 +23,7 @@
 
 // label column j of realisation `realisation` drawn uniformly from [lo, hi): stream (BWM, 0), pair j, u2 (the map of pta_cw_draw)
 PTA_HD double pta_bwm_draw(uint64_t seed, uint64_t realisation, uint32_t j, double lo, double hi) {
-  double u1, u2;
-  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_BWM, 0u), j), u1, u2);
-  return fma(hi - lo, u2, lo);
+  return pta_box_draw(seed, realisation, pta_stream_id(PTA_STREAM_BWM, 0u), j, lo, hi);
 }
 
 // (F+, Fx) of a pulsar (unit vector phat) for a source at (cos_gwtheta, gwphi): m = (sin phi, -cos phi, 0), n = (-cos theta cos phi,

@@ -1,5 +1,6 @@
 // One burst with memory per realisation (ReplicaEngine.set_bwm + theta bwm_* keys, set_bwm_prior + generate_sampled):
-//   pta_bwm_uniform        burst labels drawn on chip from uniform boxes, stream (BWM, 0), pair = label column: keyed by (seed, realisation)
+//   pta_bwm_uniform        burst labels drawn on chip from uniform boxes, stream (BWM, 0), pair = label column: keyed by (seed, realisation);
+//                          the shared box draw (pta_box_kernels.hip)
 //   pta_engine_bwm_params  coef[R, P] = pol * strain, one thread per (realisation, pulsar), and t0_s[R]
 //   pta_engine_bwm_add     the ramp over the engine's TOA tiles x groups of realisations, added into (or written to) out[R, n_toa]
 // Formulas: pta_bwm.h.  No atomics and one fixed operation per element: a realisation's term is the same in every batch.
@@ -10,23 +11,12 @@
 #define BWM_ADD_RG 16  // realisations per workgroup of the ramp kernel: two half-workgroups x two batches of BWM_ADD_U rows
 #define BWM_ADD_U 4    // rows a lane has in flight: 4 x 16 bytes per lane, 16 KiB per workgroup
 
-__global__ void k_bwm_uniform(uint64_t seed, uint64_t r0, int R, const double *__restrict__ lo, const double *__restrict__ hi,
-                              double *__restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)R * PTA_BWM_NSRC) return;
-  const int j = (int)(idx % PTA_BWM_NSRC);
-  const int64_t r = idx / PTA_BWM_NSRC;
-  out[idx] = pta_bwm_draw(seed, r0 + (uint64_t)r, (uint32_t)j, lo[j], hi[j]);
-}
-
 extern "C" int pta_bwm_uniform(uint64_t seed, uint64_t r0, int R, const double *lo, const double *hi, double *out, void *stream) {
   PTA_REQUIRE(lo && hi && out, PTA_E_ARG, "pta_bwm_uniform: NULL argument");
   PTA_REQUIRE(R > 0, PTA_E_ARG, "pta_bwm_uniform: R=%d", R);
   const int64_t total = (int64_t)R * PTA_BWM_NSRC;
   PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_bwm_uniform: problem too large");
-  hipLaunchKernelGGL(k_bwm_uniform, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, lo, hi, out);
-  PTA_LAUNCH_CHECK();
-  return PTA_OK;
+  return pta_box_uniform_launch(seed, r0, R, 1, PTA_BWM_NSRC, PTA_STREAM_BWM, 0u, lo, hi, out, pta_stream(stream));
 }
 
 __global__ void k_engine_bwm_params(pta_bwm_engine bw, int R) {

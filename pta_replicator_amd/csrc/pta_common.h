@@ -48,6 +48,11 @@ int pta_dgemm_tile_n(int M, int N, int K, int algo);
 int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int64_t n, int ntile, int J, double *vmax, int64_t ld_max,
                             int32_t *varg, int64_t ld_arg, hipStream_t stream);
 
+// the uniform box draw of every per-realisation prior (pta_box_kernels.hip): out[R, S, n_par], column j of source s of realisation
+// r0 + r from pair j of stream (kind, field0 + s); the calling entry checks its arguments
+int pta_box_uniform_launch(uint64_t seed, uint64_t r0, int R, int S, int n_par, uint32_t kind, uint32_t field0, const double *lo,
+                           const double *hi, double *out, hipStream_t stream);
+
 // ---- ragged batches (pta_potrf_ragged): matrices of different orders in END-ALIGNED virtual coordinates -------------------------
 // Every matrix of the batch is embedded in a virtual matrix of order E whose bottom-right corner it shares: virtual index i <-> real
 // index i - front[b], front[b] = E - n[b].  In these coordinates every panel boundary, trailing size and tile grid of the blocked

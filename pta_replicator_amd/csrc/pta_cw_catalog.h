@@ -35,9 +35,7 @@ PTA_HD int pta_cw_catalog_npar(int mode) { return mode == 0 ? PTA_CW_CATALOG_NPA
 
 // label column j of source s of realisation `realisation`: stream (CW, s), pair j, u2 - source 0 is pta_cw_draw
 PTA_HD double pta_cw_catalog_draw(uint64_t seed, uint64_t realisation, uint32_t s, uint32_t j, double lo, double hi) {
-  double u1, u2;
-  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_CW, s), j), u1, u2);
-  return fma(hi - lo, u2, lo);
+  return pta_box_draw(seed, realisation, pta_stream_id(PTA_STREAM_CW, s), j, lo, hi);
 }
 
 // Cs, Cc of one term: amplitude alpha, orbital phase offset q

@@ -52,9 +52,7 @@
 
 // label column j of realisation `realisation` drawn uniformly from [lo, hi): stream (CW, 0), pair j, u2 (the map of pta_hyper_draw)
 PTA_HD double pta_cw_draw(uint64_t seed, uint64_t realisation, uint32_t j, double lo, double hi) {
-  double u1, u2;
-  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_CW, 0u), j), u1, u2);
-  return fma(hi - lo, u2, lo);
+  return pta_box_draw(seed, realisation, pta_stream_id(PTA_STREAM_CW, 0u), j, lo, hi);
 }
 
 // (1 + d)^5 - 1

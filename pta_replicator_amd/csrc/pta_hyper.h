@@ -11,22 +11,18 @@
 #define PTA_YEAR_IN_SEC (365.25 * 86400.0)  // constants.py YEAR_IN_SEC
 #define PTA_GWB_F1YR (1.0 / 3.16e7)         // the GWB spectrum's f1yr (red_noise.py:247), not 1 / YEAR_IN_SEC
 
-// lo + (hi - lo) u, one rounding
+// lo + (hi - lo) u, one rounding (the map of pta_box_draw, pta_rng.h)
 PTA_HD double pta_hyper_affine(double lo, double hi, double u) { return fma(hi - lo, u, lo); }
 
 // parameter column j of realisation `realisation` drawn uniformly from [lo, hi)
 PTA_HD double pta_hyper_draw(uint64_t seed, uint64_t realisation, uint32_t j, double lo, double hi) {
-  double u1, u2;
-  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_HYPER, 0u), j), u1, u2);
-  return pta_hyper_affine(lo, hi, u2);
+  return pta_box_draw(seed, realisation, pta_stream_id(PTA_STREAM_HYPER, 0u), j, lo, hi);
 }
 
 // parameter column j of a further field of the hyperparameter stream: stream (PTA_STREAM_HYPER, field), pair j.  Field 0 is
 // pta_hyper_draw bit for bit; field 1 holds the nodes of a per-realisation GWB spectrum (gwb_log10_hc)
 PTA_HD double pta_hyper_draw_field(uint64_t seed, uint64_t realisation, uint32_t field, uint32_t j, double lo, double hi) {
-  double u1, u2;
-  pta_uniform_pair(pta_philox_draw(seed, realisation, pta_stream_id(PTA_STREAM_HYPER, field), j), u1, u2);
-  return pta_hyper_affine(lo, hi, u2);
+  return pta_box_draw(seed, realisation, pta_stream_id(PTA_STREAM_HYPER, field), j, lo, hi);
 }
 
 // characteristic strain hc(f) of the power-law GWB, with the optional turnover (red_noise.py:245-251): same operations in the

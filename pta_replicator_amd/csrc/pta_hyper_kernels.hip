@@ -1,8 +1,9 @@
 // Per-realisation hyperparameters in throughput mode (ReplicaEngine.generate(theta=...), generate_sampled):
-//   pta_hyper_uniform          theta drawn on chip from uniform boxes, keyed by (seed, realisation) like the residuals
+//   pta_hyper_uniform          theta drawn on chip from uniform boxes, keyed by (seed, realisation) like the residuals: stream (HYPER, 0)
+//                              through the shared box draw (pta_box_kernels.hip)
 //   pta_gwb_spectrum_scale     hcf(f_k; A_r, gamma_r) / hcf0(f_k) per (realisation, bin): the factor the scaled GWB transforms apply
 //   pta_gwb_spectrum_scale_user  the same factor for a spectrum given per realisation as M nodes of log10 hc (gwb_log10_hc)
-//   pta_hyper_uniform_field    pta_hyper_uniform on stream (HYPER, field): the prior draws of those nodes (field 1)
+//   pta_hyper_uniform_field    pta_hyper_uniform on stream (HYPER, field): the prior draws of those nodes (field 1), the same box draw
 //   pta_engine_rn_coef_hyper   k_engine_rn_coef with sqrt(prior) evaluated per (realisation, pulsar, frequency)
 // pta_engine_generate_hyper (pta_engine_kernels.hip) is pta_engine_generate with the last two stages above switched in, in the stage
 // order of pta_engine_generate: pta_engine_rn_coef_hyper -> pta_gwb_spectrum_scale -> scaled GWB transform -> ORF mix -> synthesis.
@@ -11,24 +12,13 @@
 #include "pta_rng.h"
 #include "pta_hyper.h"
 
-__global__ void k_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *__restrict__ lo,
-                                const double *__restrict__ hi, double *__restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)R * n_par) return;
-  const int j = (int)(idx % n_par);
-  const int64_t r = idx / n_par;
-  out[idx] = pta_hyper_draw(seed, r0 + (uint64_t)r, (uint32_t)j, lo[j], hi[j]);
-}
-
 extern "C" int pta_hyper_uniform(uint64_t seed, uint64_t r0, int R, int n_par, const double *lo, const double *hi, double *out,
                                  void *stream) {
   PTA_REQUIRE(lo && hi && out, PTA_E_ARG, "pta_hyper_uniform: NULL argument");
   PTA_REQUIRE(R > 0 && n_par > 0, PTA_E_ARG, "pta_hyper_uniform: R=%d n_par=%d", R, n_par);
   const int64_t total = (int64_t)R * n_par;
   PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_hyper_uniform: problem too large");
-  hipLaunchKernelGGL(k_hyper_uniform, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, n_par, lo, hi, out);
-  PTA_LAUNCH_CHECK();
-  return PTA_OK;
+  return pta_box_uniform_launch(seed, r0, R, 1, n_par, PTA_STREAM_HYPER, 0u, lo, hi, out, pta_stream(stream));
 }
 
 __global__ void k_gwb_spectrum_scale(const double *__restrict__ f, const double *__restrict__ hcf0, int Nf, int R,
@@ -98,15 +88,6 @@ extern "C" int pta_engine_rn_coef_hyper(uint64_t seed, uint64_t r0, int R, int P
   return PTA_OK;
 }
 
-__global__ void k_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_par, uint32_t field, const double *__restrict__ lo,
-                                      const double *__restrict__ hi, double *__restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)R * n_par) return;
-  const int j = (int)(idx % n_par);
-  const int64_t r = idx / n_par;
-  out[idx] = pta_hyper_draw_field(seed, r0 + (uint64_t)r, field, (uint32_t)j, lo[j], hi[j]);
-}
-
 extern "C" int pta_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_par, int field, const double *lo, const double *hi,
                                        double *out, void *stream) {
   PTA_REQUIRE(lo && hi && out, PTA_E_ARG, "pta_hyper_uniform_field: NULL argument");
@@ -114,10 +95,7 @@ extern "C" int pta_hyper_uniform_field(uint64_t seed, uint64_t r0, int R, int n_
   PTA_REQUIRE(field >= 0 && field <= 0xFFFFFF, PTA_E_ARG, "pta_hyper_uniform_field: field=%d does not fit the 24-bit stream field", field);
   const int64_t total = (int64_t)R * n_par;
   PTA_REQUIRE(total < (1LL << 31), PTA_E_ARG, "pta_hyper_uniform_field: problem too large");
-  hipLaunchKernelGGL(k_hyper_uniform_field, dim3(pta_cdiv(total, 256)), dim3(256), 0, pta_stream(stream), seed, r0, R, n_par, (uint32_t)field,
-                     lo, hi, out);
-  PTA_LAUNCH_CHECK();
-  return PTA_OK;
+  return pta_box_uniform_launch(seed, r0, R, 1, n_par, PTA_STREAM_HYPER, (uint32_t)field, lo, hi, out, pta_stream(stream));
 }
 
 #define PTA_GWB_SPEC_MMAX 4096  // nodes of one spectrum: 32 KiB of LDS

@@ -32,7 +32,8 @@
 #define PTA_STREAM_TD 5u    // + pulsar index: TD-mode z[i] of the pulsar's N_a x N_a factor, pair p = i>>1, branch i&1
 #define PTA_STREAM_TDGW 6u  // + pulsar index: TD-mode z[j] of the npts x npts GWB grid factor, pair p = j>>1, branch j&1
 #define PTA_STREAM_HYPER 7u // pulsar field 0: per-realisation hyperparameters, pair p = parameter column j, uniform u2 (pta_hyper.h); field 1: spectrum nodes
-#define PTA_STREAM_CW 8u    // pulsar field 0: per-realisation CW source labels, pair p = label column j, uniform u2 (pta_cw_hyper.h)
+#define PTA_STREAM_CW 8u    // pulsar field s: CW labels of source s of the realisation, pair p = label column j, uniform u2 (pta_cw_hyper.h, pta_cw_catalog.h)
+#define PTA_STREAM_BWM 9u   // pulsar field 0: per-realisation burst-with-memory labels, pair p = label column j, uniform u2 (pta_bwm.h)
 
 PTA_HD uint32_t pta_stream_id(uint32_t kind, uint32_t pulsar) { return (kind << 24) | (pulsar & 0xFFFFFFu); }
 
@@ -104,6 +105,15 @@ PTA_HD void pta_uniform_pair(pta_u32x4 v, double &u1, double &u2) {
   uint64_t b = ((((uint64_t)v.z << 32) | v.w) >> 12) | 0x3FF0000000000000ull;
   u1 = 2.0 - pta_bits_to_double(a);
   u2 = pta_bits_to_double(b) - 1.0;
+}
+
+// A parameter drawn uniformly from the box [lo, hi): u2 of pair j of `stream` (a pta_stream_id word) through lo + (hi - lo) u2 with one
+// rounding.  Every per-realisation prior draw (pta_hyper_draw, pta_hyper_draw_field, pta_cw_draw, pta_cw_catalog_draw, pta_bwm_draw)
+// is this function on its own stream; the explicit fma makes host (g++ -ffp-contract=off) and device agree bit for bit.
+PTA_HD double pta_box_draw(uint64_t seed, uint64_t realisation, uint32_t stream, uint32_t j, double lo, double hi) {
+  double u1, u2;
+  pta_uniform_pair(pta_philox_draw(seed, realisation, stream, j), u1, u2);
+  return fma(hi - lo, u2, lo);
 }
 
 // x/y and sqrt(x) without the IEEE division / square-root expansions: those lean on VCC (v_div_scale ->

@@ -1,0 +1,376 @@
+"""The per-realisation terms of the ReplicaEngine: theta split into its parts, the terms added after the fused launch (one CW source
+or a catalogue, a burst with memory, white noise per group) and theta drawn on chip from uniform boxes (set_*_prior, sample_theta).
+What the terms share is written once: the params -> add batch loop (_term_batches), the reused device tables grown on demand
+(_scratch), the buffers queued launches still read (self._keep, one entry per term) and the box draw (_uniform_table).  The fixed model,
+prepare(), the workspace and the generate* calls stay in engine.py.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _bwm, _cw, _hyper, _lib, _wn_hyper, device as dv
+from ._position import ra_dec
+
+
+class PerRealisationTermsMixin:
+    # ---------------------------------------------------------------- configuration -------------
+    def set_cw(self, psrTerm=True, evolve=True, phase_approx=False, tref=0.0, pdist=1.0):
+        """one continuous-wave source PER REALISATION, its parameters given by the cw_* keys of theta (generate, generate_per_signal,
+        generate_td, generate_os) or drawn from set_cw_prior() (generate_sampled).  The flags have add_cgw's meaning
+        (deterministic.py:13-48); tref [s]; pdist [kpc], a scalar or one value per pulsar (theta's cw_pdist [R, P] overrides it).
+        Adds nothing by itself; fixed sources of add_cgw / add_delays stay as they are, on top of it.  No prepare() needed."""
+        self._cw = _cw.make_config(self.P, psrTerm, evolve, phase_approx, tref, pdist)
+        self._cwt = None   # device tables of the previous configuration (_cw_tables)
+        return self
+
+    def set_bwm(self):
+        """one burst with memory PER REALISATION (the reference's add_gw_memory, deterministic.py:822-884, Earth term), its parameters
+        given by the bwm_* keys of theta (generate, generate_per_signal, generate_td, the generate_* statistics) or drawn from
+        set_bwm_prior() (generate_sampled): bwm_log10_h, bwm_cos_gwtheta, bwm_gwphi, bwm_psi (the reference's bwm_pol), bwm_t0_mjd, each
+        [R].  Adds nothing by itself; a fixed ramp of add_delays stays as it is, on top of it; a realisation may carry a CW source
+        (set_cw) and a burst together, but one burst only.  No prepare() needed."""
+        self._bwm = True
+        return self
+
+    def set_bwm_prior(self, log10_h=None, t0_mjd=None, cos_gwtheta=None, gwphi=None, psi=None):
+        """uniform boxes (lo, hi) of the per-realisation burst of generate_sampled() (set_bwm configures it).  Required: log10_h and
+        t0_mjd.  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), psi (0, pi) (isotropic sky and polarisation).  Drawn from stream (9, 0),
+        pair = label column (_bwm.COLUMNS), independently of set_hyper_prior's and set_cw_prior's parameters."""
+        self._bwm_prior = _bwm.make_prior(log10_h=log10_h, t0_mjd=t0_mjd, cos_gwtheta=cos_gwtheta, gwphi=gwphi, psi=psi)
+        return self
+
+    def set_cw_prior(self, log10_mc=None, log10_fgw=None, log10_h=None, log10_dist=None, cos_gwtheta=None, gwphi=None, phase0=None,
+                     psi=None, cos_inc=None, pdist=None, n_sources=None):
+        """uniform boxes (lo, hi) of the per-realisation CW source of generate_sampled() (set_cw configures it).  Required: log10_mc
+        [Msun], log10_fgw [Hz] and exactly one of log10_h / log10_dist [Mpc].  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), phase0
+        (0, 2 pi), psi (0, pi), cos_inc (-1, 1) (isotropic sky and orientation).  pdist [kpc]: (lo, hi) or [P, 2]; left out = set_cw's
+        pdist.  Drawn from stream (8, 0), pair = label column (_cw.COLUMNS), independently of set_hyper_prior's parameters.
+        n_sources = S: a catalogue of S sources per realisation, S independent draws from the same boxes, source s from stream (8, s)
+        (source 0 is the single-source draw); the labels are then [R, S].  pdist stays [R, P] on stream (8, 0).  None: one source,
+        labels [R]."""
+        self._cw_prior = _cw.make_prior(self.P, n_sources=n_sources, log10_mc=log10_mc, log10_fgw=log10_fgw, log10_h=log10_h, log10_dist=log10_dist,
+                                        cos_gwtheta=cos_gwtheta, gwphi=gwphi, phase0=phase0, psi=psi, cos_inc=cos_inc, pdist=pdist)
+        return self
+
+    def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None,
+                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None):
+        """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array;
+        gwb_log10_hc (needs set_gwb(userSpec=U [M, 2])): (lo, hi) for every node or [M, 2], box j for row j of U as given - a free
+        spectrum per realisation.  gwb_clm (needs set_gwb(lmax=L >= 1)): (lo, hi) for every c_lm with l >= 1 or [(L+1)^2 - 1, 2], box j for
+        column j + 1 of gwb_clm - a sky per realisation; c_00 stays as configured.  The ORF 2 sum_k c_k basis[k] is positive
+        semidefinite when the power sum_lm c_lm Y_lm is positive over the sky, which every box with
+        sum_{l>=1} |c_lm| max|Y_lm| <= c_00 Y_00 guarantees (real harmonics: Y_00 = 1 / sqrt(4 pi), max|Y_1m| = sqrt(3 / 4 pi)); a
+        wider box may draw skies that are not, which come back flagged (generate_sampled).  wn_efac, wn_log10_equad (need
+        set_white_noise) and wn_log10_ecorr (needs set_jitter): (lo, hi) for every group or [G, 2], G = len(wn_groups) or
+        len(ecorr_groups), box j for group j.  Parameters left out keep their configured values.  No prepare() needed after a change."""
+        wn_prior = _wn_hyper.make_prior(len(self.wn_groups), len(self.ecorr_groups), wn_efac=wn_efac, wn_log10_equad=wn_log10_equad,
+                                        wn_log10_ecorr=wn_log10_ecorr) or None
+        prior = None   # (white-noise boxes alone are a prior; nothing at all is _hyper.make_prior's "no parameter given")
+        if wn_prior is None or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
+            prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
+                                      rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
+        self._prior, self._wn_prior = prior, wn_prior   # new dicts: the device copies of the previous boxes are not theirs (_uniform_table)
+        return self
+
+    # ---------------------------------------------------------------- theta -> its parts --------
+    def _theta_parts(self, theta, R, td=False, check_values=True):
+        """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
+        (_hyper.check_theta), None for the fixed-parameter path (no theta, or the keys of det alone); det: the keys whose terms are
+        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta) and the white-noise keys
+        (_wn_hyper.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
+        skips the value checks (theta drawn by sample_theta)."""
+        if theta is None:
+            return None, {}
+        if _hyper.ORF_INFO_KEY in theta:   # a label of sampled theta, no parameter
+            theta = {k: v for k, v in theta.items() if k != _hyper.ORF_INFO_KEY}
+        rest, wnk = _wn_hyper.split(theta)   # ahead of _hyper.check_theta, whose key list stays the GWB / red-noise one
+        rest, cw = _cw.split(rest)
+        rest, bwm = _bwm.split(rest)
+        if td:
+            _wn_hyper.refuse_td(wnk)
+        if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
+            raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
+                             "cw_* and bwm_* keys are): use generate(theta=...) or generate_sampled()")
+        det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
+        det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
+        det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
+        if det and not rest:
+            return None, det
+        return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
+
+    def _det_apply(self, det, R, out):
+        """out[R, n_toa] += the deterministic terms of every row for the validated deterministic keys of theta (the second member of
+        _theta_parts): the CW term, then the burst with memory."""
+        if _cw.has_keys(det):
+            self._cw_apply(det, R, out)
+        if _bwm.has_keys(det):
+            self._bwm_apply(det, R, out)
+        return out
+
+    # ---------------------------------------------------------------- what the terms share ------
+    def _scratch(self, name, *shapes):
+        """the reused device table(s) `name` of a term, float64, at least shapes[i][0] rows of exactly shapes[i][1:]: the cached ones
+        while every one of them is large enough, else all of them are dropped first and allocated at `shapes` (one tensor for one
+        shape, a tuple otherwise).  They stay outside the workspace budget."""
+        tab = self._scratch_tabs.get(name)
+        if tab is None or any(t.shape[0] < sh[0] or tuple(t.shape[1:]) != tuple(sh[1:]) for t, sh in zip(tab, shapes)):
+            self._scratch_tabs[name] = None
+            tab = self._scratch_tabs[name] = tuple(dv.empty(sh) for sh in shapes)
+        return tab[0] if len(shapes) == 1 else tab
+
+    def _term_batches(self, params, add, struct, rows, R, step, out, accumulate):
+        """out[R, n_toa] (+)= a term in batches of `step` realisations: per batch the entry `params` fills the tables of the filled
+        ctypes struct, then the entry `add` walks the engine's tiles.  rows: [(field, tensor or None, bytes per row)], the members of
+        the struct that follow the batch (None stays NULL)."""
+        s = dv.stream_ptr()
+        for lo in range(0, R, step):
+            n = min(step, R - lo)
+            for field, t, nbytes in rows:
+                setattr(struct, field, None if t is None else t.data_ptr() + nbytes * lo)
+            _lib.call(params, ctypes.byref(struct), n, s)
+            _lib.call(add, ctypes.byref(self.plan), ctypes.byref(struct), n, ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0)),
+                      out.stride(0), 1 if accumulate else 0, s)
+        return out
+
+    def _phat_device(self):
+        """pulsar unit vectors [P, 3] on the device (the reference's expression, deterministic.py:88, :858), built once."""
+        if getattr(self, "_d_phat", None) is None:
+            self._d_phat = dv.f64(_cw.pulsar_vectors([ra_dec(p) for p in self.psrs]))
+        return self._d_phat
+
+    def _cw_tables(self):
+        """theta-independent device tables of the CW path: the pulsar unit vectors (_phat_device) and, built once per set_cw(), the
+        configured pulsar distances [P] (kpc)."""
+        if self._cwt is None:
+            self._cwt = {"phat": self._phat_device(), "pdist": dv.f64(self._cw["pdist"])}
+        return self._cwt
+
+    # ---------------------------------------------------------------- CW, catalogue, BWM --------
+    def _cw_apply(self, cw, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the CW term of every row for validated CW theta `cw` (row r = the source of realisation r0 + r): the
+        source table -> pta_engine_cw_params -> pta_engine_cw_add, in batches of max_batch(hyper=True, cw=True).  Source keys of
+        shape [R, S] are a catalogue (_cw_catalog_apply)."""
+        if _cw.is_catalog(cw):
+            return self._cw_catalog_apply(cw, R, out, accumulate)
+        if not self._prepared:
+            self.prepare()
+        P = self.P
+        amp = _cw.amp_key(cw)
+        cols = [dv.as_f64(cw[amp if c == "amp" else "cw_" + c]).reshape(R, 1) for c in _cw.COLUMNS]
+        has_pd = _cw.PDIST_KEY in cw
+        if has_pd:
+            cols.append(dv.as_f64(cw[_cw.PDIST_KEY]).reshape(R, P))
+        src = torch.cat(cols, dim=1).contiguous()
+        conf, tb = self._cw, self._cw_tables()
+        step = min(R, self.max_batch(hyper=True, cw=True))
+        c = _lib.CwEngine()
+        c.n_psr, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = P, _cw.mode(conf), int(conf["psrTerm"]), int(amp == "cw_log10_h"), int(has_pd)
+        c.tref, c.phat, c.pdist, c.toa_s = conf["tref"], tb["phat"].data_ptr(), tb["pdist"].data_ptr(), self.d_toa_s.data_ptr()
+        c.ld_src, c.par = src.stride(0), self._scratch("cw_par", (step, P, _lib.CW_ENGINE_NPAR)).data_ptr()
+        self._term_batches("pta_engine_cw_params", "pta_engine_cw_add", c, [("src", src, 8 * src.stride(0))], R, step, out, accumulate)
+        self._keep["cw"] = src   # the launches above read it asynchronously
+        return out
+
+    def _cw_catalog_apply(self, cw, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the sum of the catalogue of every row for validated CW theta `cw` with source keys [R, S] (and cw_count
+        [R]): the [R, S, 8] source table -> pta_engine_cw_catalog_params -> pta_engine_cw_catalog_add (one accumulator per element over
+        the sources, one read-modify-write of out), in batches of max_batch(hyper=True, cw=S)."""
+        if not self._prepared:
+            self.prepare()
+        dev = dv.require_gpu()
+        P, S = self.P, _cw.n_sources(cw)
+        amp = _cw.amp_key(cw)
+        src = torch.stack([dv.as_f64(cw[amp if c == "amp" else "cw_" + c]).reshape(R, S) for c in _cw.COLUMNS], dim=2).contiguous()   # [R, S, 8]
+        has_pd = _cw.PDIST_KEY in cw
+        conf, tb = self._cw, self._cw_tables()
+        pdist = dv.as_f64(cw[_cw.PDIST_KEY]).reshape(R, P) if has_pd else tb["pdist"]
+        count = cw.get(_cw.COUNT_KEY)
+        if count is not None:
+            count = (count.to(device=dev, dtype=torch.int32) if hasattr(count, "data_ptr") else dv.i32(count)).reshape(R).contiguous()
+        mode = _cw.mode(conf)
+        step = min(R, self.max_batch(hyper=True, cw=S))
+        c = _lib.CwCatalogEngine()
+        c.n_psr, c.n_src, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = P, S, mode, int(conf["psrTerm"]), int(amp == "cw_log10_h"), int(has_pd)
+        c.tref, c.phat, c.toa_s = conf["tref"], tb["phat"].data_ptr(), self.d_toa_s.data_ptr()
+        c.ld_src, c.ld_pdist = src.stride(0), (pdist.stride(0) if has_pd else 0)
+        c.par = self._scratch("cwc_par", (step * P * S * _lib.CW_CATALOG_NPAR[mode],)).data_ptr()
+        rows = [("src", src, 8 * src.stride(0)), ("pdist", pdist, 8 * pdist.stride(0) if has_pd else 0), ("count", count, 4)]
+        self._term_batches("pta_engine_cw_catalog_params", "pta_engine_cw_catalog_add", c, rows, R, step, out, accumulate)
+        self._keep["cw"] = (src, pdist, count)   # the launches above read them asynchronously
+        return out
+
+    def _bwm_apply(self, det, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the burst-with-memory term of every row for validated theta `det` (row r = the burst of realisation
+        r0 + r): the [R, 5] label table -> pta_engine_bwm_params (coef [R, P], t0 [R]) -> pta_engine_bwm_add, in batches of max_batch().
+        The tables are R (P + 1) doubles and stay outside the workspace budget."""
+        if not self._prepared:
+            self.prepare()
+        P = self.P
+        src = torch.stack([dv.as_f64(det[k]).reshape(R) for k in _bwm.KEYS], dim=1).contiguous()   # [R, 5]
+        step = min(R, self.max_batch())
+        coef, t0 = self._scratch("bwm_tab", (step, P), (step,))
+        b = _lib.BwmEngine()
+        b.n_psr, b.phat, b.toa_s = P, self._phat_device().data_ptr(), self.d_toa_s.data_ptr()
+        b.ld_src, b.coef, b.t0_s = src.stride(0), coef.data_ptr(), t0.data_ptr()
+        self._term_batches("pta_engine_bwm_params", "pta_engine_bwm_add", b, [("src", src, 8 * src.stride(0))], R, step, out, accumulate)
+        self._keep["bwm"] = src   # the launches above read it asynchronously
+        return out
+
+    # ---------------------------------------------------------------- white noise ---------------
+    def _wn_tables(self):
+        """theta-independent device tables of the per-realisation white noise, built once per prepare(): sigma [n_toa], the white-noise
+        group of every TOA and the ECORR group of every TOA's epoch (an epoch's flag is its first TOA's; -1 = in no group), the first
+        group of every pulsar, and the configured efac / equad [s] / ecorr [s] of every group as prepare() computed them."""
+        if self._wnh is not None:
+            return self._wnh
+        P, N = self.P, self.n_toa
+
+        def flags_of(conf, a, idx):
+            """flag values of TOAs idx of pulsar a; a pulsar that is its own group (flags None) reads no flags"""
+            if _wn_hyper._pick_flags(conf["flags"], a, P) is None:
+                return np.zeros(len(idx))
+            return self._flag_array(a, conf["flagid"])[idx]
+        t = {"sigma": dv.f64(np.concatenate(self.sigma_s)), "n_wn": 0, "n_ec": 0, "tnequad": 0, "max_per_psr": 1}
+        if self._wn is not None:
+            groups = self.wn_groups
+            grp = np.concatenate([_wn_hyper.toa_groups(groups, a, flags_of(self._wn, a, np.arange(int(self.counts[a])))) for a in range(P)])
+            efac, equad = _wn_hyper.configured_wn(P, self._wn)
+            psr0 = _wn_hyper.psr_offsets(P, groups)
+            t.update(n_wn=len(groups), wn_group=dv.i32(grp), wn_psr0=dv.i32(psr0), efac_conf=dv.f64(efac), equad_conf=dv.f64(equad),
+                     tnequad=int(self._wn["tnequad"]))
+            t["max_per_psr"] = max(t["max_per_psr"], int(np.diff(psr0).max()))
+        if self._ec is not None and self.ecorr_groups:
+            groups = self.ecorr_groups
+            grp = np.full(N, -1, dtype=np.int32)
+            for a in range(P):   # an epoch's flag is its first TOA's (white_noise.py:35)
+                of_epoch = _wn_hyper.toa_groups(groups, a, flags_of(self._ec, a, self.epoch_first[a]))
+                grp[self.off[a]:self.off[a + 1]] = of_epoch[self.epoch_of[a]]
+            psr0 = _wn_hyper.psr_offsets(P, groups)
+            t.update(n_ec=len(groups), ec_group=dv.i32(grp), ec_psr0=dv.i32(psr0), ecorr_conf=dv.f64(_wn_hyper.configured_ecorr(P, self._ec)))
+            t["max_per_psr"] = max(t["max_per_psr"], int(np.diff(psr0).max()))
+        self._wnh = t
+        return t
+
+    def _wn_theta_device(self, det, R):
+        """validated white-noise keys of theta -> {"efac", "equad", "log10_ecorr": contiguous float64 device tensor [R, G] or None (key
+        not given: as configured), "wn", "ecorr": whether the EFAC / EQUAD term and the ECORR term have a key}"""
+        get = lambda k: dv.as_f64(det[k]) if k in det else None   # noqa: E731
+        return {"efac": get(_wn_hyper.EFAC_KEY), "equad": get(_wn_hyper.EQUAD_KEY), "log10_ecorr": get(_wn_hyper.ECORR_KEY),
+                "wn": _wn_hyper.has_wn(det), "ecorr": _wn_hyper.has_ecorr(det)}
+
+    def _wn_add(self, wdev, lo, n, r_first, optr, ld_out, accumulate=True, wn=True, ecorr=True):
+        """rows lo .. lo+n-1 of theta's white-noise labels `wdev` (_wn_theta_device) -> pta_engine_wn_params (the amplitude tables ea, eb
+        [n, G_wn], ec [n, G_ec]) -> pta_engine_wn_add into the n rows at optr (realisations r_first ..): the EFAC / EQUAD term where
+        theta has one of its keys (and wn), the ECORR term where it has that key (and ecorr); accumulate=False writes the terms alone
+        (generate_per_signal).  The tables are n (2 G_wn + G_ec) doubles and stay outside the workspace budget, like the BWM tables."""
+        w = self._wn_struct(wdev, lo, n, wn, ecorr)
+        if w is None:
+            return
+        s = dv.stream_ptr()
+        _lib.call("pta_engine_wn_params", ctypes.byref(w), n, s)
+        _lib.call("pta_engine_wn_add", ctypes.byref(self.plan), ctypes.byref(w), self.seed, r_first, n, optr, ld_out, 1 if accumulate else 0, s)
+
+    def _wn_struct(self, wdev, lo, n, wn=True, ecorr=True):
+        """the pta_engine_wn_hyper of rows lo .. lo+n-1 of `wdev` with the terms asked for that theta has a key of (None: neither);
+        its amplitude tables are the engine's reused buffers, grown on demand"""
+        t = self._wn_tables()
+        wn, ecorr = wn and wdev["wn"], ecorr and wdev["ecorr"]
+        if not (wn or ecorr):
+            return None
+        ea, eb, ec = self._scratch("wn_amp", (n, t["n_wn"]), (n, t["n_wn"]), (n, t["n_ec"]))
+        w = _lib.WnHyper()
+        w.n_psr, w.n_wn, w.n_ec, w.tnequad, w.max_per_psr = self.P, t["n_wn"], t["n_ec"], t["tnequad"], t["max_per_psr"]
+        w.sigma = t["sigma"].data_ptr()
+        if wn:
+            w.wn_group, w.wn_psr0, w.efac_conf, w.equad_conf = (t[k].data_ptr() for k in ("wn_group", "wn_psr0", "efac_conf", "equad_conf"))
+            for name, ld, key in (("efac", "ld_efac", "efac"), ("log10_equad", "ld_equad", "equad")):
+                if wdev[key] is not None:
+                    setattr(w, name, dv.row_ptr(wdev[key], lo))
+                    setattr(w, ld, wdev[key].stride(0))
+            w.ea, w.eb = ea.data_ptr(), eb.data_ptr()
+        if ecorr:
+            w.ec_group, w.ec_psr0, w.ecorr_conf = (t[k].data_ptr() for k in ("ec_group", "ec_psr0", "ecorr_conf"))
+            w.log10_ecorr, w.ld_ecorr = dv.row_ptr(wdev["log10_ecorr"], lo), wdev["log10_ecorr"].stride(0)
+            w.ec = ec.data_ptr()
+        return w
+
+    # ---------------------------------------------------------------- theta drawn on chip -------
+    def sample_theta(self, R, r0=0):
+        """theta of realisations r0 .. r0+R-1 under the current prior, drawn on chip (what generate_sampled uses).  With a gwb_clm
+        prior also gwb_orf_info [R] int32 (pta_gwb_orf_factor's info of every drawn sky; generate() and the statistics skip the key)."""
+        return self._sample_theta(R, r0, orf_info=True)
+
+    def _orf_info_of(self, clm):
+        """info [R] int32 of pta_gwb_orf_factor for clm [R, n_lm] on the device, factored batch by batch into a scratch buffer"""
+        R, P = clm.shape[0], self.P
+        step = min(R, self.max_batch(hyper=True, clm=True))
+        scratch, info = dv.empty((step, P, P)), dv.zeros((R,), dtype=torch.int32)
+        for lo in range(0, R, step):
+            _lib.call("pta_gwb_orf_factor", dv.ptr(self.d_orf_basis), clm.shape[1], P, dv.row_ptr(clm, lo), clm.stride(0), min(step, R - lo),
+                      dv.ptr(scratch), ctypes.c_void_p(info.data_ptr() + 4 * lo), dv.stream_ptr())
+        torch.cuda.current_stream().synchronize()   # scratch dies with the call
+        return info
+
+    def _uniform_table(self, entry, name, prior, bounds, R, r0, mid=None, shape=None):
+        """[R, n] table (or `shape`) of the uniform entry `entry` for realisations r0 .. r0+R-1: column j uniform in the box (lo[j],
+        hi[j]) of bounds() -> (lo, hi).  The boxes `name` are uploaded once per prior object: the cache entry holds the prior dict it
+        was built from, so a set_*_prior call, which replaces the dict, invalidates it.  mid: the entry's arguments between R and lo
+        (default: the column count n)."""
+        ent = self._boxes.get(name)
+        if ent is None or ent[0] is not prior:
+            ent = self._boxes[name] = (prior, [dv.f64(x) for x in bounds()])
+        d_lo, d_hi = ent[1]
+        table = dv.empty(shape or (R, d_lo.shape[0]))
+        _lib.call(entry, self.seed, r0, R, *((d_lo.shape[0],) if mid is None else mid), dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
+        return table
+
+    def _sample_theta(self, R, r0, orf_info):
+        prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
+        wn_prior = getattr(self, "_wn_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None:
+            raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
+        if not self._prepared:
+            self.prepare()
+        theta = {}
+        if bwm_prior is not None:   # stream (9, 0): pair j = label column j, whatever else is sampled
+            theta.update(_bwm.labels(self._uniform_table("pta_bwm_uniform", "bwm", bwm_prior, lambda: _bwm.prior_bounds(bwm_prior), R, r0, mid=())))
+        if cw_prior is not None:    # stream (8, 0): pair j = label column j, whatever else is sampled
+            S, cw_bounds = cw_prior["n_sources"], lambda: _cw.prior_bounds(cw_prior, self.P)
+            table = catalog = None
+            if S is None or "pdist" in cw_prior:   # (with a catalogue: for the pdist columns, pairs 8 .. 8 + P - 1 of stream (8, 0))
+                table = self._uniform_table("pta_cw_uniform", "cw", cw_prior, cw_bounds, R, r0)
+            if S is not None:                      # source s from stream (8, s), pair = label column
+                catalog = self._uniform_table("pta_cw_catalog_uniform", "cw", cw_prior, cw_bounds, R, r0, mid=(S,), shape=(R, S, _cw.N_SRC))
+            theta.update(_cw.labels(table, cw_prior, self.P, catalog))
+        for k, box in (wn_prior or {}).items():   # streams (7, 3 .. 5): pair j = group j, whatever else is sampled
+            n_groups = len(self.ecorr_groups if k == _wn_hyper.ECORR_KEY else self.wn_groups)
+            if len(box[0]) != n_groups:
+                raise ValueError(f"sample_theta: the {k} boxes are for {len(box[0])} groups but the engine now has {n_groups}: "
+                                 "call set_hyper_prior again")
+            theta[k] = self._uniform_table("pta_hyper_uniform_field", k, wn_prior, lambda: box, R, r0, mid=(len(box[0]), _wn_hyper.FIELD[k]))
+        if prior is None:
+            return theta
+        box = _hyper.spec_bounds(prior)
+        if box is not None:        # stream (7, 1): pair j = node j of the userSpec as given
+            theta[_hyper.SPEC_KEY] = self._uniform_table("pta_hyper_uniform_field", "spec", prior, lambda: box, R, r0, mid=(len(box[0]), _hyper.SPEC_FIELD))
+        box = _hyper.clm_bounds(prior, self._gw)
+        if box is not None:        # stream (7, 2): pair j = column j of gwb_clm (column 0: the configured c_00)
+            clm = theta[_hyper.CLM_KEY] = self._uniform_table("pta_hyper_uniform_field", "clm", prior, lambda: box, R, r0,
+                                                              mid=(len(box[0]), _hyper.CLM_FIELD))
+            if orf_info:
+                theta[_hyper.ORF_INFO_KEY] = self._orf_info_of(clm)
+        if not any(k in prior for k in _hyper.KEYS):
+            return theta
+        table = self._uniform_table("pta_hyper_uniform", "hyper", prior, lambda: _hyper.prior_bounds(prior, self.P), R, r0)
+        cols = _hyper.columns(self.P)
+        for k in _hyper.KEYS:
+            if k in prior:
+                c0, c1 = cols[k]
+                theta[k] = table[:, c0].contiguous() if k in _hyper.GWB_KEYS else table[:, c0:c1].contiguous()
+        if self.plan.rn_k:
+            none = self._hyper_tables()["rn_none"]
+            for k in _hyper.RN_KEYS:
+                if k in theta and len(none):   # pulsars configured without red noise keep none: their labels are NaN
+                    theta[k][:, none] = float("nan")
+        return theta

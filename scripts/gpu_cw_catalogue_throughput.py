@@ -76,12 +76,12 @@ def main():
             cw = _cw.check_theta(theta, R, P, eng._cw, check_values=False)
             eng.generate(R, out=out)
             eng._cw_apply(cw, R, out)                       # builds the tables of both paths' shared inputs
-            src, _, _ = eng._cw_keep                        # [R, S, 8]
+            src, _, _ = eng._keep["cw"]                     # [R, S, 8]
             tb = eng._cw_tables()
             c = _lib.CwCatalogEngine()
             c.n_psr, c.n_src, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = P, S, mode, int(eng._cw["psrTerm"]), 1, 0
             c.tref, c.phat, c.pdist, c.toa_s = tref, tb["phat"].data_ptr(), tb["pdist"].data_ptr(), eng.d_toa_s.data_ptr()
-            c.src, c.ld_src, c.par = src.data_ptr(), src.stride(0), eng._cwc_par.data_ptr()
+            c.src, c.ld_src, c.par = src.data_ptr(), src.stride(0), eng._scratch("cwc_par", (1,)).data_ptr()
             par1 = dv.empty((R, P, _lib.CW_ENGINE_NPAR))
             b = _lib.CwEngine()
             b.n_psr, b.mode, b.psr_term, b.amp_is_h, b.has_pdist = P, mode, int(eng._cw["psrTerm"]), 1, 0

@@ -78,12 +78,12 @@ def main():
         cw = _cw.check_theta({k: v for k, v in theta.items() if k in _cw.KEYS}, R, eng.P, eng._cw, check_values=False)
         buf = dv.empty((R, eng.n_toa))
         eng._cw_apply(cw, R, buf, accumulate=False)
-        src, par, tb = eng._cw_keep, eng._cw_par, eng._cw_tables()
+        src, par, tb = eng._keep["cw"], eng._scratch("cw_par", (R, eng.P, _lib.CW_ENGINE_NPAR)), eng._cw_tables()
         c = _lib.CwEngine()
         c.n_psr, c.mode, c.psr_term, c.amp_is_h, c.has_pdist = eng.P, _cw.mode(eng._cw), int(eng._cw["psrTerm"]), 1, 0
         c.tref, c.phat, c.pdist, c.toa_s = tref, tb["phat"].data_ptr(), tb["pdist"].data_ptr(), eng.d_toa_s.data_ptr()
         c.src, c.ld_src, c.par = src.data_ptr(), src.stride(0), par.data_ptr()
-        lo, hi = eng._cw_prior_dev
+        lo, hi = eng._boxes["cw"][1]
         kern = {
             "cw_uniform_ms": lambda: _lib.call("pta_cw_uniform", eng.seed, r0, R, lo.shape[0], dv.ptr(lo), dv.ptr(hi),
                                                ctypes.c_void_p(buf.data_ptr()), s),

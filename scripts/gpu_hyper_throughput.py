@@ -81,8 +81,8 @@ def main():
             dv.ptr(theta["rn_log10_A"]), dv.ptr(theta["rn_gamma"]), dv.ptr(eng.d_amp), dv.ptr(ws["coef"]), int(eng.rng_fast), s),
         "rn_coef_fixed_ms": lambda: _lib.call("pta_engine_rn_coef", eng.seed, r0, R, eng.P, eng.K, dv.ptr(eng.d_amp), dv.ptr(ws["coef"]),
                                               int(eng.rng_fast), s),
-        "hyper_uniform_ms": lambda: _lib.call("pta_hyper_uniform", eng.seed, r0, R, 2 + 2 * eng.P, dv.ptr(eng._prior_dev[0]),
-                                              dv.ptr(eng._prior_dev[1]), ctypes.c_void_p(ws["G0"].data_ptr()), s),
+        "hyper_uniform_ms": lambda: _lib.call("pta_hyper_uniform", eng.seed, r0, R, 2 + 2 * eng.P, dv.ptr(eng._boxes["hyper"][1][0]),
+                                              dv.ptr(eng._boxes["hyper"][1][1]), ctypes.c_void_p(ws["G0"].data_ptr()), s),
     }
     kernels = {}
     for name, fn in kern.items():
