@@ -273,8 +273,12 @@ int pta_gwb_idft_rng(uint64_t seed, uint64_t r0, int R, int P, int Nf, const dou
  * one circular convolution of length 4096 per (realisation, pulsar) row = two in-LDS radix-8 fp64 FFTs,
  * ~0.5 MFLOP per row instead of 3.6 MFLOP of dense DFT.  pta_gwb_czt_setup fills pre[2*4096] (pre-chirp with
  * sqrtC), FB[2*4096] (chirp spectrum / 4096, digit-reversed order, stored [q][b] per 8-point butterfly b), tw[2*4096] (FFT twiddles), post[2*npts].
+ * (FB: the chirp W^{-u^2/2} on the lags u = min(i0 - (Nf-2), 0) .. i0 + npts - 2, lag u in slot u mod 4096; logical position 8 b + q of
+ * its radix-8 decimation-in-frequency spectrum, the frequency with the position's four octal digits reversed, sits at FB[2 (512 q + b)].)
  * pta_gwb_czt: w == NULL draws on chip (stream (GWB, a), pair k, like pta_gwb_idft_rng), else w[R*P x ldw]
- * interleaved (re, im) rows as in pta_gwb_idft (ldw = 0: one row of draws shared by all rows - timing probe).  */
+ * interleaved (re, im) rows as in pta_gwb_idft (ldw = 0: one row of draws shared by all rows - timing probe).
+ * pta_gwb_czt_fits: 1 when Nf >= 3, npts >= 1, i0 >= 1, the lags fit the convolution, (Nf-2) + npts - 2 < 4096, and so does the
+ * window itself, i0 + npts - 2 < 4096; else 0, and pta_gwb_czt_setup, pta_gwb_czt and pta_gwb_czt_scaled refuse with PTA_E_ARG.  */
 int pta_gwb_czt_fits(int Nf, int npts, int i0);
 /* pta_gwb_czt `variant`: 0 (default): six LDS exchanges, draws / product / output in registers, computed twiddles;
  *                        1: every stage through LDS with table twiddles (cross-check); 10+f: ladder step f (25 = the default

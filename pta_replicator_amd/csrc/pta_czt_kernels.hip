@@ -30,7 +30,8 @@ __global__ __launch_bounds__(PTA_FFT_THREADS) void k_czt_setup(const double *__r
     }
     pre[2 * m] = pr;
     pre[2 * m + 1] = pi_;
-    // convolution chirp b_u = e^{- pi i u^2 / n} on u = j - k in [i0 - Kf, i0 + npts - 2], wrapped mod 4096
+    // convolution chirp b_u = e^{- pi i u^2 / n} on u = j - k in [i0 - Kf, i0 + npts - 2], wrapped mod 4096 (with i0 > Kf from u = 0:
+    // lags the window does not need, which only reach outputs outside it)
     int64_t u = m;
     bool used = (m <= i0 + npts - 2);
     if (!used && m >= PTA_FFT_N - (Kf - i0)) {
@@ -75,12 +76,17 @@ __global__ __launch_bounds__(PTA_FFT_THREADS) void k_czt_setup(const double *__r
   }
 }
 
-static bool czt_fits(int Nf, int npts, int i0) { return Nf >= 3 && (Nf - 2) + npts - 2 < PTA_FFT_N && i0 >= 1 && (Nf - 2) <= PTA_FFT_N; }
+// the lags u = j - k in [i0 - Kf, i0 + npts - 2] take Kf + npts - 1 <= 4096 slots, and the window's own outputs i0 - 1 .. i0 + npts - 2
+// must lie inside the convolution: beyond 4095 the positive lags would claim the slots of the negative ones (k_czt_setup) and the
+// last butterfly would index past the plane (k_gwb_czt).  Sums in 64 bits: any int is refused, none wraps.
+static bool czt_fits(int Nf, int npts, int i0) {
+  return Nf >= 3 && npts >= 1 && i0 >= 1 && (int64_t)(Nf - 2) + npts - 2 < PTA_FFT_N && (int64_t)i0 + npts - 2 < PTA_FFT_N;
+}
 
 extern "C" int pta_gwb_czt_setup(const double *sqrtC, int Nf, int npts, int i0, double inv_dt, double *pre, double *FB, double *tw,
                                  double *post, void *stream) {
   PTA_REQUIRE(sqrtC && pre && FB && tw && post, PTA_E_ARG, "pta_gwb_czt_setup: NULL argument");
-  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt_setup: Nf=%d npts=%d does not fit one 4096-point convolution", Nf, npts);
+  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt_setup: Nf=%d npts=%d i0=%d does not fit one 4096-point convolution", Nf, npts, i0);
   hipLaunchKernelGGL(k_czt_setup, dim3(1), dim3(PTA_FFT_THREADS), 0, pta_stream(stream), sqrtC, Nf, npts, i0, inv_dt, pre, FB, tw, post);
   PTA_LAUNCH_CHECK();
   return PTA_OK;
@@ -323,7 +329,7 @@ extern "C" int pta_gwb_czt(uint64_t seed, uint64_t r0, const double *w, int64_t 
                            int variant, int rng_fast, void *stream) {
   PTA_REQUIRE(pre && FB && tw && post && G0, PTA_E_ARG, "pta_gwb_czt: NULL argument");
   PTA_REQUIRE(R > 0 && P > 0 && P < (1 << 24) && npts > 0 && ldg >= npts, PTA_E_ARG, "pta_gwb_czt: R=%d P=%d npts=%d", R, P, npts);
-  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt: Nf=%d npts=%d does not fit one 4096-point convolution", Nf, npts);
+  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt: Nf=%d npts=%d i0=%d does not fit one 4096-point convolution", Nf, npts, i0);
   PTA_REQUIRE(!w || ldw == 0 || ldw >= 2 * (int64_t)Nf, PTA_E_ARG, "pta_gwb_czt: ldw too small");  // 0 = one row of draws for all rows
   int64_t M64 = (int64_t)R * P;
   PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_czt: R*P too large");
@@ -372,8 +378,8 @@ extern "C" int pta_gwb_czt_scaled(uint64_t seed, uint64_t r0, const double *w, i
   (void)ldw;
   PTA_REQUIRE(R > 0 && P > 0 && P < (1 << 24) && npts > 0 && ldg >= npts, PTA_E_ARG, "pta_gwb_czt_scaled: R=%d P=%d npts=%d", R, P,
               npts);
-  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt_scaled: Nf=%d npts=%d does not fit one 4096-point convolution", Nf,
-              npts);
+  PTA_REQUIRE(czt_fits(Nf, npts, i0), PTA_E_ARG, "pta_gwb_czt_scaled: Nf=%d npts=%d i0=%d does not fit one 4096-point convolution", Nf,
+              npts, i0);
   PTA_REQUIRE(ld_scale >= Nf - 1, PTA_E_ARG, "pta_gwb_czt_scaled: ld_scale=%lld < Nf - 1", (long long)ld_scale);
   int64_t M64 = (int64_t)R * P;
   PTA_REQUIRE(M64 < (1LL << 31), PTA_E_ARG, "pta_gwb_czt_scaled: R*P too large");

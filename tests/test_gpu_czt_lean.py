@@ -11,7 +11,11 @@ pytestmark = pytest.mark.gpu
 BASE = 10 + 15                                            # the fused kernel without the new bits
 LEAN = [0, 10 + 15 + 16, 10 + 15 + 32, 10 + 15 + 64, 10 + 127]   # the default, each bit alone, all three
 # (2000, 1100): the window [9, 1109) crosses 1024, the last butterfly keeps its full form; (500, 37): only output 0 is ever stored
-SHAPES = [(3000, 600), (3001, 600), (601, 200), (500, 37), (2400, 601), (3400, 600), (2000, 1100)]
+# (3499, 600): the last shape that fits, Kf + npts - 2 = 4095; (1026, 1015), (700, 1016), (700, 1017): the window ends at 1023, 1024,
+# 1025 - the pruned last butterfly's last shape and the full one's first two; (513 .. 515, 40): Kf = 511, 512, 513 around the one
+# 512-block of the first butterfly that straddles Kf.  tests/test_gpu_gwb_direct.py repeats the comparison at i0 other than 10.
+SHAPES = [(3000, 600), (3001, 600), (601, 200), (500, 37), (2400, 601), (3400, 600), (2000, 1100),
+          (3499, 600), (1026, 1015), (700, 1016), (700, 1017), (513, 40), (514, 40), (515, 40)]
 
 
 @pytest.fixture(scope="module")
