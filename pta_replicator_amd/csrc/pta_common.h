@@ -43,8 +43,9 @@ int pta_dgemm_launch(int transB, int M, int N, int K, double alpha, const double
 
 int pta_dgemm_tile_n(int M, int N, int K, int algo);
 
-// fold of the per-sub-tile sky maxima of pta_fstat_fe / pta_bwm_stat (pta_fstat_kernels.hip): part_val / part_arg [r][tile][j], n = R J
-// outputs, tiles folded in ascending order, strictly greater wins (the lowest index on ties)
+// fold of the per-sub-tile sky maxima k_sky_stat leaves (defined in pta_fstat_kernels.hip, called by pta_sky_stat_launch of pta_sky_stat.h
+// for pta_fstat_fe and pta_bwm_stat): part_val / part_arg [r][tile][j], n = R J outputs, tiles folded in ascending order, strictly greater
+// wins (the lowest index on ties)
 int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int64_t n, int ntile, int J, double *vmax, int64_t ld_max,
                             int32_t *varg, int64_t ld_arg, hipStream_t stream);
 

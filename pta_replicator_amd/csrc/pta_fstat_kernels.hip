@@ -14,17 +14,10 @@
 // are never stored.  Every output is one MFMA chain over the TOAs in ascending slabs: no split-K, no atomics, so a realisation's Q
 // is bit-identical whatever R, the chunk or its row slot (MFMA output rows are independent).
 //
-// pta_fstat_fe: the product over pulsars (K = P) of Q against phi.  One wave owns 8 frequencies x 16 sky points: the 16 rows of its
-// A tile are (frequency, sin / cos) ordered so that accumulator registers (0, 1) and (2, 3) of a lane are the sin / cos sums of
-// frequencies g and g + 4 (g = lane >> 4); two MFMA chains, one against F+ and one against Fx of the same 16 sky points, leave the
-// whole 4-vector N_rjs of two (j, s) in one lane.  phi of the wave's sky points (2 KS doubles, KS = ceil(P / 4))
-// and the 10 unique entries of M_js^-1 of its two (j, s) stay in registers for the whole launch; the workgroup (4 waves = 64 sky
-// points) walks its realisations, staging Q[r, :, 16 columns] once per realisation in LDS (double-buffered, one barrier per
-// realisation).  N never leaves the registers.  Pulsars are summed in ascending groups of four by the MFMA, the quadratic form is
-// one fixed fma chain, the maximum over a tile is an ascending scan of its 16 sky points (strictly greater wins: the lower index on ties), and
-// the tiles are folded in ascending order: an (r, j, s) value is the same in either mode and in any chunk.
-#include "pta_common.h"
-#include "pta_mfma.h"
+// pta_fstat_fe: k_sky_stat (pta_sky_stat.h, shared with pta_bwm_stat) under the policy fe_stat below - 8 frequencies x (sin, cos) as
+// the 16 rows of a wave's A tile, the 10 unique entries of the 4 x 4 M_js^-1 per cell, pta_fstat_quad as the form - and the fold of the
+// per-tile maxima, k_fstat_fe_reduce, which both statistics use.
+#include "pta_sky_stat.h"
 
 #define FS_BK 16   // TOAs per K slab
 #define FS_LD 17   // LDS row stride in doubles (odd: the 16 rows of a fragment read fall into 16 different bank pairs)
@@ -142,103 +135,18 @@ __device__ __forceinline__ double pta_fstat_quad(const double (&m)[10], double n
   return fma(0.5, d, o);
 }
 
-#define FS_RB 8  // realisations per scan of the sky_max reduction: 8 x 8 frequencies = one (realisation, frequency) per lane
-#define FS_ST PTA_FSTAT_SKY_TILE  // sky points per workgroup of k_fstat_fe: four waves x 16
-static_assert(FS_ST == 64, "k_fstat_fe: a workgroup is four waves of 16 sky points");
-
-template <int KS, bool MAXMODE>
-__global__ __launch_bounds__(256) void k_fstat_fe(const double *__restrict__ Q, int64_t ld_q, int P, int J, int R, int rchunk,
-                                                  const double *__restrict__ phi, int S, const double *__restrict__ Minv,
-                                                  double *__restrict__ fe, int64_t ld_fe, double *__restrict__ pval,
-                                                  int32_t *__restrict__ parg, int ntile) {
-  __shared__ double Al[2][4 * KS * 16];  // Q[r, a, 2 j0 .. 2 j0 + 15] of one realisation, a < 4 KS (zeros past P)
-  __shared__ double Mx[MAXMODE ? 4 * FS_RB * 8 * FS_LD : 1];  // sky_max: Fe of FS_RB realisations x 8 frequencies x 16 sky points per wave
-  constexpr int NL = (4 * KS * 16 + 255) / 256;
-  const int t = threadIdx.x, l = t & 63, w = t >> 6, g = l >> 4, m = l & 15;
-  const int j0 = blockIdx.y * 8, st = blockIdx.x;
-  const int s = st * FS_ST + w * 16 + m;  // this lane's sky point
-  const int ja = j0 + g, jb = j0 + g + 4;   // and its two frequencies
-  const int r_lo = blockIdx.z * rchunk, r_hi = min(R, r_lo + rchunk);
-  // B operand: lane l of step k supplies phi[a = 4 k + (l >> 4)][s][+ / x]
-  double bplus[KS], bcross[KS];
-#pragma unroll
-  for (int k = 0; k < KS; ++k) {
-    const int a = 4 * k + g;
-    const bool ok = a < P && s < S;
-    bplus[k] = ok ? phi[((int64_t)a * S + s) * 2] : 0.0;
-    bcross[k] = ok ? phi[((int64_t)a * S + s) * 2 + 1] : 0.0;
+// pta_fstat_fe's policy of k_sky_stat (pta_sky_stat.h): 8 frequencies x (sin, cos) per workgroup.  Row rho of the A tile is frequency
+// (rho & 3) + 4 (rho >> 3), sin / cos (rho >> 2) & 1, so that accumulator registers (2 e, 2 e + 1) of a lane are the sin / cos sums of its
+// cell e (frequency j0 + g + 4 e): both chains together hold the whole 4-vector N_rjs of the lane's two cells.
+struct fe_stat {
+  static constexpr int JB = 8, NC = 2, NM = 10, QPJ = 2;
+  static constexpr bool AMP = false;
+  static __device__ __forceinline__ int64_t qoff(int a, int, int J) { return (int64_t)a * 2 * J; }
+  static __device__ __forceinline__ int acol(int m) { return 2 * ((m & 3) + 4 * (m >> 3)) + ((m >> 2) & 1); }
+  static __device__ __forceinline__ double value(const double (&mi)[10], const pta_f64x4 &np_, const pta_f64x4 &nc_, int cell, double &, double &) {
+    return pta_fstat_quad(mi, np_[2 * cell], np_[2 * cell + 1], nc_[2 * cell], nc_[2 * cell + 1]);
   }
-  double ma[10], mb[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    ma[i] = (ja < J && s < S) ? Minv[((int64_t)ja * S + s) * 10 + i] : 0.0;
-    mb[i] = (jb < J && s < S) ? Minv[((int64_t)jb * S + s) * 10 + i] : 0.0;
-  }
-  // A operand: row rho = l & 15 of the tile is frequency (rho & 3) + 4 (rho >> 3), sin / cos (rho >> 2) & 1
-  const int acol = 2 * ((m & 3) + 4 * (m >> 3)) + ((m >> 2) & 1);
-  double qv[NL];
-  auto fetch = [&](int r) {
-#pragma unroll
-    for (int u = 0; u < NL; ++u) {
-      const int idx = t + 256 * u, a = idx >> 4, c = 2 * j0 + (idx & 15);
-      qv[u] = (idx < 4 * KS * 16 && a < P && c < 2 * J) ? Q[(int64_t)r * ld_q + (int64_t)a * 2 * J + c] : 0.0;
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < NL; ++u) {
-      const int idx = t + 256 * u;
-      if (idx < 4 * KS * 16) Al[buf][idx] = qv[u];
-    }
-  };
-  if (r_lo < r_hi) fetch(r_lo);
-  for (int r = r_lo; r < r_hi; ++r) {
-    const int cur = (r - r_lo) & 1;
-    stash(cur);
-    __syncthreads();  // the buffer written two realisations ago was last read before the previous barrier
-    if (r + 1 < r_hi) fetch(r + 1);
-    pta_f64x4 np_ = pta_f64x4{0.0, 0.0, 0.0, 0.0}, nc_ = pta_f64x4{0.0, 0.0, 0.0, 0.0};
-    const double *Ab = Al[cur] + g * 16 + acol;
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const double av = Ab[k * 64];
-      np_ = pta_mfma_f64(av, bplus[k], np_);
-      nc_ = pta_mfma_f64(av, bcross[k], nc_);
-    }
-    // accumulator e of lane l: tile row (l >> 4) + 4 e = frequency g + 4 (e >> 1), sin / cos e & 1; column = sky point l & 15
-    const double fa = pta_fstat_quad(ma, np_[0], np_[1], nc_[0], nc_[1]);
-    const double fb = pta_fstat_quad(mb, np_[2], np_[3], nc_[2], nc_[3]);
-    if (!MAXMODE) {
-      if (s < S) {
-        if (ja < J) fe[(int64_t)r * ld_fe + (int64_t)ja * S + s] = fa;
-        if (jb < J) fe[(int64_t)r * ld_fe + (int64_t)jb * S + s] = fb;
-      }
-    } else {
-      // maximum over the 16 sky points of the wave, FS_RB realisations at a time through the wave's own LDS block [realisation]
-      // [frequency][sky point]: a lane then scans the 16 sky points of one (realisation, frequency) in ascending order, strictly
-      // greater winning (the lower index on ties), and eight lanes write eight consecutive frequencies.  Sky points past S never win.
-      const int q = (r - r_lo) % FS_RB;
-      double *mw = Mx + w * (FS_RB * 8 * FS_LD);
-      mw[(q * 8 + g) * FS_LD + m] = s < S ? fa : -INFINITY;
-      mw[(q * 8 + g + 4) * FS_LD + m] = s < S ? fb : -INFINITY;
-      if (q == FS_RB - 1 || r + 1 == r_hi) {  // uniform over the workgroup
-        __syncthreads();
-        const int qq = l >> 3, jj = j0 + (l & 7);
-        if (qq <= q && jj < J) {
-          const double *v = mw + l * FS_LD;
-          double best = v[0];
-          int bk = 0;
-#pragma unroll
-          for (int k = 1; k < 16; ++k)
-            if (v[k] > best) best = v[k], bk = k;
-          const int64_t slot = ((int64_t)(r - q + qq) * ntile + st * 4 + w) * J;  // [r][16-point sub-tile, ascending in s][j]
-          pval[slot + jj] = best;
-          parg[slot + jj] = st * FS_ST + w * 16 + bk;
-        }
-      }
-    }
-  }
-}
+};
 
 // fold the sub-tile maxima in ascending sky order: strictly greater wins, so the lowest index is kept on ties
 __global__ __launch_bounds__(256) void k_fstat_fe_reduce(const double *__restrict__ pval, const int32_t *__restrict__ parg, int64_t n, int ntile,
@@ -258,7 +166,7 @@ __global__ __launch_bounds__(256) void k_fstat_fe_reduce(const double *__restric
   fe_arg[r * ld_arg + j] = bi;
 }
 
-// internal launcher of the fold over the sub-tile maxima (declared in pta_common.h): shared with pta_bwm_stat, whose per-tile layout is the same
+// internal launcher of the fold over the sub-tile maxima (declared in pta_common.h): pta_sky_stat_launch calls it for both statistics
 int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int64_t n, int ntile, int J, double *vmax, int64_t ld_max,
                             int32_t *varg, int64_t ld_arg, hipStream_t stream) {
   hipLaunchKernelGGL(k_fstat_fe_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part_val, part_arg, n, ntile, J, vmax, ld_max, varg,
@@ -314,7 +222,7 @@ extern "C" int pta_fstat_fp(const double *Q, int64_t ld_q, int P, int J, int R, 
   return PTA_OK;
 }
 
-extern "C" int64_t pta_fstat_fe_tiles(int S) { return S < 1 ? 0 : (int64_t)((S + FS_ST - 1) / FS_ST) * (FS_ST / 16); }
+extern "C" int64_t pta_fstat_fe_tiles(int S) { return S < 1 ? 0 : (int64_t)((S + SKY_ST - 1) / SKY_ST) * (SKY_ST / 16); }
 
 extern "C" int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, const double *phi, int S, const double *Minv, double *fe,
                             int64_t ld_fe, double *fe_max, int64_t ld_max, int32_t *fe_arg, int64_t ld_arg, double *part_val, int32_t *part_arg,
@@ -323,47 +231,6 @@ extern "C" int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, 
   PTA_REQUIRE(P >= 2 && P <= PTA_FSTAT_PMAX && J >= 1 && 2 * J <= PTA_FSTAT_CMAX && R > 0 && S >= 1, PTA_E_ARG,
               "pta_fstat_fe: P=%d (2..%d) J=%d (1..%d) R=%d S=%d", P, PTA_FSTAT_PMAX, J, PTA_FSTAT_CMAX / 2, R, S);
   PTA_REQUIRE(ld_q >= (int64_t)P * 2 * J, PTA_E_ARG, "pta_fstat_fe: ld_q=%lld < 2*P*J=%lld", (long long)ld_q, (long long)P * 2 * J);
-  const bool maxmode = fe == nullptr;
-  if (maxmode) {
-    PTA_REQUIRE(fe_max && fe_arg && part_val && part_arg, PTA_E_ARG,
-                "pta_fstat_fe: without the full map (fe NULL) fe_max, fe_arg and the workspaces part_val, part_arg are needed");
-    PTA_REQUIRE(ld_max >= J && ld_arg >= J, PTA_E_ARG, "pta_fstat_fe: ld_max=%lld or ld_arg=%lld < J=%d", (long long)ld_max, (long long)ld_arg, J);
-  } else {
-    PTA_REQUIRE(!fe_max && !fe_arg, PTA_E_ARG, "pta_fstat_fe: one output mode per call: the full map (fe) or the maxima (fe_max, fe_arg)");
-    PTA_REQUIRE(ld_fe >= (int64_t)J * S, PTA_E_ARG, "pta_fstat_fe: ld_fe=%lld < J*S=%lld", (long long)ld_fe, (long long)J * S);
-  }
-  const unsigned nst = pta_cdiv(S, FS_ST), njb = pta_cdiv(J, 8);
-  // realisations per workgroup: enough workgroups to fill the chip, never fewer than 8 realisations per walk (phi and M^-1 are
-  // loaded once per workgroup); the split only regroups realisations
-  long long nz = 4096 / ((long long)nst * njb);
-  if (nz < 1) nz = 1;
-  if (nz > (R + 7) / 8) nz = (R + 7) / 8;
-  if (nz > 65535) nz = 65535;
-  const int rchunk = (int)((R + nz - 1) / nz);
-  const unsigned ngz = pta_cdiv(R, rchunk);
-  const int ntile = (int)pta_fstat_fe_tiles(S);
-  dim3 grid(nst, njb, ngz), block(256);
-  hipStream_t s = pta_stream(stream);
-  const int ks = (P + 3) / 4;  // MFMA steps of four pulsars
-#define PTA_FS_CASE(KS_)                                                                                                              \
-  case KS_:                                                                                                                           \
-    if (maxmode)                                                                                                                      \
-      hipLaunchKernelGGL((k_fstat_fe<KS_, true>), grid, block, 0, s, Q, ld_q, P, J, R, rchunk, phi, S, Minv, fe, ld_fe, part_val, \
-                         part_arg, ntile);                                                                                            \
-    else                                                                                                                              \
-      hipLaunchKernelGGL((k_fstat_fe<KS_, false>), grid, block, 0, s, Q, ld_q, P, J, R, rchunk, phi, S, Minv, fe, ld_fe, part_val, \
-                         part_arg, ntile);                                                                                            \
-    break;
-  switch (ks) {
-    PTA_FS_CASE(1) PTA_FS_CASE(2) PTA_FS_CASE(3) PTA_FS_CASE(4) PTA_FS_CASE(5) PTA_FS_CASE(6) PTA_FS_CASE(7) PTA_FS_CASE(8)
-    PTA_FS_CASE(9) PTA_FS_CASE(10) PTA_FS_CASE(11) PTA_FS_CASE(12) PTA_FS_CASE(13) PTA_FS_CASE(14) PTA_FS_CASE(15) PTA_FS_CASE(16)
-    PTA_FS_CASE(17) PTA_FS_CASE(18) PTA_FS_CASE(19) PTA_FS_CASE(20) PTA_FS_CASE(21) PTA_FS_CASE(22) PTA_FS_CASE(23) PTA_FS_CASE(24)
-    PTA_FS_CASE(25) PTA_FS_CASE(26) PTA_FS_CASE(27) PTA_FS_CASE(28) PTA_FS_CASE(29) PTA_FS_CASE(30) PTA_FS_CASE(31) PTA_FS_CASE(32)
-  }
-#undef PTA_FS_CASE
-  PTA_LAUNCH_CHECK();
-  if (maxmode) {
-    return pta_fstat_reduce_launch(part_val, part_arg, (int64_t)R * J, ntile, J, fe_max, ld_max, fe_arg, ld_arg, s);
-  }
-  return PTA_OK;
+  return pta_sky_stat_launch<fe_stat>("pta_fstat_fe", "fe", Q, ld_q, P, 2 * J, J, R, phi, S, Minv, fe, ld_fe, nullptr, 0, fe_max, ld_max, fe_arg, ld_arg,
+                                      part_val, part_arg, stream);
 }

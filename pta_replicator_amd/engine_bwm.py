@@ -16,23 +16,20 @@ The noise weights are the configured ones (white noise + ECORR + red noise, opti
 Out of scope: the pulsar term and the single-pulsar ramp statistic, a statistic matched to per-realisation theta, more than one burst
 per realisation, maximising over a continuous epoch.
 
-The argument checks, the host noise model, the rows and state checks and the chunked generation loop with its rows buffer are
-engine_stats.StatisticsMixin's, shared with the optimal statistic, the likelihood and the F-statistic.
+The low-rank columns of the noise model, the chunk rule, the workspace with the projection and the loops over given and generated
+rows are engine_stats.SkyStatisticsMixin's, shared with the F-statistic; the argument checks, the host noise model and the rows and
+state checks are its base StatisticsMixin's, shared with the optimal statistic and the likelihood too.
 """
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _cw, _lib, device as dv
 from . import bwm_statistic as bst
 from . import f_statistic as fst
-from . import optimal_statistic as ost
 from ._position import ra_dec
-from .engine_stats import StatisticsMixin, check_components, check_timing_model
+from .engine_stats import SkyStatisticsMixin, check_components, check_timing_model
 
 
-class BwmStatisticMixin(StatisticsMixin):
+class BwmStatisticMixin(SkyStatisticsMixin):
     def prepare_bwm_statistic(self, t0_mjd, sky, timing_model="spin", gwb_auto=None, components=14, gamma=13. / 3.):
         """W, g (and phi, M^-1 on the sky grid) of the array under the configured noise model (white noise + ECORR + red noise,
         optionally the GWB auto-term), uploaded once.  Returns self.
@@ -63,23 +60,9 @@ class BwmStatisticMixin(StatisticsMixin):
                              f"workspace_bytes = {int(self.workspace_bytes)}: use fewer epochs per preparation or raise workspace_bytes")
         gw_lA = self._stats_gwb_auto(gwb_auto)
         toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
-        P = self.P
-        F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]     # the low-rank part of C_a: red noise, then the GWB auto-term
-        if F_rn is not None:
-            for a in range(P):
-                F_low[a].append(F_rn[a])
-                phi_low[a].append(phi_rn[a])
-        if gw_lA is not None:
-            T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
-            S = ost.unit_spectrum(int(components), T, float(gamma))
-            for a in range(P):
-                F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
-                phi_low[a].append(10.0 ** (2 * gw_lA) * S)
-        low = bool(F_low[0])
+        F_low, phi_low = self._sky_low_rank(toas, F_rn, phi_rn, gw_lA, components, gamma)
         phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs])
-        plan = bst.prepare(toas, sigma2, t0 * 86400.0, phat, sky, epoch_of=epoch_of, ecorr=ecorr,
-                           F_rn=[np.concatenate(x, axis=1) for x in F_low] if low else None,
-                           phi_rn=[np.concatenate(x) for x in phi_low] if low else None, M=M)
+        plan = bst.prepare(toas, sigma2, t0 * 86400.0, phat, sky, epoch_of=epoch_of, ecorr=ecorr, F_rn=F_low, phi_rn=phi_low, M=M)
         self._bs = dict(plan=plan, engine_plan=self.plan, J=J, C=plan.C, S=plan.S, Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), t0_mjd=dv.f64(t0),
                         phi=dv.f64(plan.phi), Minv=dv.f64(plan.Minv_packed()), ntile=int(_lib.lib.pta_fstat_fe_tiles(plan.S)), ws=None)
         return self
@@ -91,12 +74,6 @@ class BwmStatisticMixin(StatisticsMixin):
     def _bs_modes(what, sky_max, amplitudes):
         if sky_max and amplitudes:
             raise ValueError(f"{what}: amplitudes=True needs the full map (sky_max=True keeps the maxima only)")
-
-    def _bs_chunk(self, st, R, sky_max, with_rows):
-        """realisations per launch sequence: Q [P, C], the per-tile maxima of sky_max (and the generated rows) within workspace_bytes.
-        The outputs (fb, amp or fb_max / fb_arg of all R realisations) are the call's result, not workspace."""
-        per_real = 8 * self.P * st["C"] + (12 * st["J"] * st["ntile"] if sky_max else 0) + (8 * self.n_toa if with_rows else 0)
-        return max(1, min(R, int(self.workspace_bytes) // per_real))
 
     def _bs_out(self, st, R, sky_max, amplitudes):
         J, S = st["J"], st["S"]
@@ -115,20 +92,13 @@ class BwmStatisticMixin(StatisticsMixin):
         return res
 
     def _bs_launch(self, rows, n, lo, out):
-        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: pta_fstat_project into the reused Q buffer,
-        then pta_bwm_stat - on the current stream"""
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: the projection into the reused Q buffer
+        (_sky_project), then pta_bwm_stat - on the current stream"""
         st = self._bs
         P, J, C, S = self.P, st["J"], st["C"], st["S"]
         sky_max = out["fb_max"] is not None
-        ws = st["ws"]
-        if ws is None or ws["n"] < n or (sky_max and ws["pv"] is None):
-            st["ws"] = None
-            ws = st["ws"] = dict(n=n, Q=dv.empty((n, P * C)), pv=dv.empty((n * J * st["ntile"],)) if sky_max else None,
-                                 pa=dv.empty((n * J * st["ntile"],), dtype=torch.int32) if sky_max else None)
-        s = dv.stream_ptr()
-        Q = ws["Q"]
-        _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
-                  dv.ptr(Q), P * C, s)
+        ws = self._sky_project(st, rows, n, sky_max)
+        s, Q = dv.stream_ptr(), ws["Q"]
         if sky_max:
             _lib.call("pta_bwm_stat", dv.ptr(Q), P * C, P, C, J, n, dv.ptr(st["phi"]), S, dv.ptr(st["Minv"]), None, 0, None, 0,
                       dv.row_ptr(out["fb_max"], lo), J, dv.row_ptr(out["fb_arg"], lo), J, dv.ptr(ws["pv"]), dv.ptr(ws["pa"]), s)
@@ -146,12 +116,7 @@ class BwmStatisticMixin(StatisticsMixin):
         lie outside that budget."""
         self._bs_modes("bwm_statistic", sky_max, amplitudes)
         st = self._bs_state("bwm_statistic")
-        R = self._stats_check_rows(rows)
-        out = self._bs_out(st, R, sky_max, amplitudes)
-        step = self._bs_chunk(st, R, sky_max, with_rows=False)
-        for lo in range(0, R, step):
-            self._bs_launch(rows[lo:lo + step], min(step, R - lo), lo, out)
-        return self._bs_result(st, out)
+        return self._bs_result(st, self._sky_rows(st, self._bs_launch, lambda R: self._bs_out(st, R, sky_max, amplitudes), rows, sky_max))
 
     def generate_bwm_statistic(self, R, r0=0, theta=None, td=False, chunk=1024, sky_max=False, amplitudes=False):
         """Fb of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td with
@@ -161,12 +126,6 @@ class BwmStatisticMixin(StatisticsMixin):
         noise weights stay the configured ones."""
         self._bs_modes("generate_bwm_statistic", sky_max, amplitudes)
         st = self._bs_state("generate_bwm_statistic")
-        R, r0, chunk = int(R), int(r0), int(chunk)
-        if R < 1 or chunk < 1 or r0 < 0:
-            raise ValueError(f"generate_bwm_statistic: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
-        hyper, det = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
-        chunk = max(1, min(chunk, self._bs_chunk(st, R, sky_max, with_rows=True)))
-        out = self._bs_out(st, R, sky_max, amplitudes)
-        for lo, n, rows in self._stats_generate_chunks(lambda: self._bs_state("generate_bwm_statistic"), R, r0, hyper, det, td, chunk):
-            self._bs_launch(rows, n, lo, out)
+        out = self._sky_generate("generate_bwm_statistic", st, lambda: self._bs_state("generate_bwm_statistic"), self._bs_launch,
+                                 lambda R: self._bs_out(st, R, sky_max, amplitudes), R, r0, theta, td, chunk, sky_max)
         return self._bs_result(st, out)

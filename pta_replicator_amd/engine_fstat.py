@@ -18,22 +18,19 @@ The noise weights are the configured ones (white noise + ECORR + red noise, opti
 marginalised): a statistic matched to per-realisation noise parameters theta is out of scope, as are the pulsar term and frequency
 evolution across the data span.
 
-The argument checks, the host noise model, the rows and state checks and the chunked generation loop with its rows buffer are
-engine_stats.StatisticsMixin's, shared with the optimal statistic and the likelihood.
+The low-rank columns of the noise model, the chunk rule, the workspace with the projection and the loops over given and generated
+rows are engine_stats.SkyStatisticsMixin's, shared with the BWM statistic; the argument checks, the host noise model and the rows and
+state checks are its base StatisticsMixin's, shared with the optimal statistic and the likelihood too.
 """
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _cw, _lib, device as dv
 from . import f_statistic as fst
-from . import optimal_statistic as ost
 from ._position import ra_dec
-from .engine_stats import StatisticsMixin, check_components, check_timing_model
+from .engine_stats import SkyStatisticsMixin, check_components, check_timing_model
 
 
-class FStatisticMixin(StatisticsMixin):
+class FStatisticMixin(SkyStatisticsMixin):
     def prepare_f_statistic(self, freqs, sky=None, timing_model="spin", gwb_auto=None, components=14, gamma=13. / 3.):
         """W, G^-1 (and with a sky grid phi, M^-1) of the array under the configured noise model (white noise + ECORR + red noise,
         optionally the GWB auto-term), uploaded once.  Returns self.
@@ -62,24 +59,10 @@ class FStatisticMixin(StatisticsMixin):
                              f"workspace_bytes = {int(self.workspace_bytes)}: use fewer frequencies per preparation or raise workspace_bytes")
         gw_lA = self._stats_gwb_auto(gwb_auto)
         toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
-        P = self.P
-        F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]     # the low-rank part of C_a: red noise, then the GWB auto-term
-        if F_rn is not None:
-            for a in range(P):
-                F_low[a].append(F_rn[a])
-                phi_low[a].append(phi_rn[a])
-        if gw_lA is not None:
-            T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
-            S = ost.unit_spectrum(int(components), T, float(gamma))
-            for a in range(P):
-                F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
-                phi_low[a].append(10.0 ** (2 * gw_lA) * S)
-        low = bool(F_low[0])
+        F_low, phi_low = self._sky_low_rank(toas, F_rn, phi_rn, gw_lA, components, gamma)
         phat = _cw.pulsar_vectors([ra_dec(p) for p in self.psrs]) if sky is not None else None
-        plan = fst.prepare(toas, sigma2, f, phat=phat, sky=sky, epoch_of=epoch_of, ecorr=ecorr,
-                           F_rn=[np.concatenate(x, axis=1) for x in F_low] if low else None,
-                           phi_rn=[np.concatenate(x) for x in phi_low] if low else None, M=M)
-        self._fs = dict(plan=plan, engine_plan=self.plan, J=J, S=plan.S, Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), Ginv=dv.f64(plan.Ginv_packed()),
+        plan = fst.prepare(toas, sigma2, f, phat=phat, sky=sky, epoch_of=epoch_of, ecorr=ecorr, F_rn=F_low, phi_rn=phi_low, M=M)
+        self._fs = dict(plan=plan, engine_plan=self.plan, J=J, C=2 * J, S=plan.S, Wt=dv.f64(plan.Wt()), off=dv.i32(self.off), Ginv=dv.f64(plan.Ginv_packed()),
                         freqs=dv.f64(f), phi=None, Minv=None, ntile=0, ws=None)
         if sky is not None:
             self._fs.update(phi=dv.f64(plan.phi), Minv=dv.f64(plan.Minv_packed()), ntile=int(_lib.lib.pta_fstat_fe_tiles(plan.S)))
@@ -90,12 +73,6 @@ class FStatisticMixin(StatisticsMixin):
         if sky_max and st["phi"] is None:
             raise ValueError(f"{what}: sky_max=True needs a sky grid (prepare_f_statistic(freqs, sky=...))")
         return st
-
-    def _fs_chunk(self, st, R, sky_max, with_rows):
-        """realisations per launch sequence: Q [P, 2 J], the per-tile maxima of sky_max (and the generated rows) within workspace_bytes.
-        The outputs (fp, fe or fe_max / fe_arg of all R realisations) are the call's result, not workspace."""
-        per_real = 8 * self.P * 2 * st["J"] + (12 * st["J"] * st["ntile"] if sky_max else 0) + (8 * self.n_toa if with_rows else 0)
-        return max(1, min(R, int(self.workspace_bytes) // per_real))
 
     def _fs_out(self, st, R, sky_max):
         J, S = st["J"], st["S"]
@@ -113,22 +90,14 @@ class FStatisticMixin(StatisticsMixin):
         return res
 
     def _fs_launch(self, rows, n, lo, out):
-        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: pta_fstat_project into the reused Q buffer,
-        pta_fstat_fp, pta_fstat_fe - all on the current stream"""
+        """rows [n, n_toa] = realisations lo .. lo+n-1 of the call -> rows lo .. of out: the projection into the reused Q buffer
+        (_sky_project), pta_fstat_fp, pta_fstat_fe - all on the current stream"""
         st = self._fs
         P, J, S = self.P, st["J"], st["S"]
         sky_max = out["fe_max"] is not None
-        ws = st["ws"]
-        if ws is None or ws["n"] < n or (sky_max and ws["pv"] is None):
-            st["ws"] = None
-            ws = st["ws"] = dict(n=n, Q=dv.empty((n, P * 2 * J)), pv=dv.empty((n * J * st["ntile"],)) if sky_max else None,
-                                 pa=dv.empty((n * J * st["ntile"],), dtype=torch.int32) if sky_max else None)
-        s = dv.stream_ptr()
-        Q = ws["Q"]
-        _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, 2 * J, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
-                  dv.ptr(Q), P * 2 * J, s)
-        fp = out["fp"]
-        _lib.call("pta_fstat_fp", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["Ginv"]), dv.row_ptr(fp, lo), J, s)
+        ws = self._sky_project(st, rows, n, sky_max)
+        s, Q = dv.stream_ptr(), ws["Q"]
+        _lib.call("pta_fstat_fp", dv.ptr(Q), P * 2 * J, P, J, n, dv.ptr(st["Ginv"]), dv.row_ptr(out["fp"], lo), J, s)
         if st["phi"] is None:
             return
         if sky_max:
@@ -147,12 +116,7 @@ class FStatisticMixin(StatisticsMixin):
         are the caller's result and lie outside that budget: the full map takes R J S 8 bytes, and sky_max=True is the way to stay
         small."""
         st = self._fs_state("f_statistic", sky_max)
-        R = self._stats_check_rows(rows)
-        out = self._fs_out(st, R, sky_max)
-        step = self._fs_chunk(st, R, sky_max, with_rows=False)
-        for lo in range(0, R, step):
-            self._fs_launch(rows[lo:lo + step], min(step, R - lo), lo, out)
-        return self._fs_result(st, out)
+        return self._fs_result(st, self._sky_rows(st, self._fs_launch, lambda R: self._fs_out(st, R, sky_max), rows, sky_max))
 
     def generate_f_statistic(self, R, r0=0, theta=None, td=False, chunk=1024, sky_max=False):
         """Fp / Fe of realisations r0 .. r0+R-1, generated chunk by chunk into one reused [chunk, n_toa] buffer (generate, generate_td
@@ -161,12 +125,6 @@ class FStatisticMixin(StatisticsMixin):
         chunk is cut so that the buffer and Q stay within workspace_bytes.  theta only shapes the data: the statistic's noise weights
         stay the configured ones."""
         st = self._fs_state("generate_f_statistic", sky_max)
-        R, r0, chunk = int(R), int(r0), int(chunk)
-        if R < 1 or chunk < 1 or r0 < 0:
-            raise ValueError(f"generate_f_statistic: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
-        hyper, cw = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
-        chunk = max(1, min(chunk, self._fs_chunk(st, R, sky_max, with_rows=True)))
-        out = self._fs_out(st, R, sky_max)
-        for lo, n, rows in self._stats_generate_chunks(lambda: self._fs_state("generate_f_statistic"), R, r0, hyper, cw, td, chunk):
-            self._fs_launch(rows, n, lo, out)
+        out = self._sky_generate("generate_f_statistic", st, lambda: self._fs_state("generate_f_statistic"), self._fs_launch,
+                                 lambda R: self._fs_out(st, R, sky_max), R, r0, theta, td, chunk, sky_max)
         return self._fs_result(st, out)

@@ -1,7 +1,9 @@
-"""The host front the per-realisation statistics of the ReplicaEngine share (engine_os.py, engine_lnl.py, engine_fstat.py): the
+"""The host front the per-realisation statistics of the ReplicaEngine share (engine_os.py, engine_lnl.py, engine_fstat.py, engine_bwm.py): the
 argument checks of their prepare_* calls, the noise model prepare() holds pulled back to the host, the checks of rows and of a
 prepared state, theta of the matched noise model on the device, the blocked pta_os_project, and the chunked generation loop with its
-one rows buffer.  What differs per statistic (its operands, its chunk arithmetic, its kernels) stays in its own mixin.
+one rows buffer.  What differs per statistic (its operands, its chunk arithmetic, its kernels) stays in its own mixin.  The two
+statistics over a sky grid (F-statistic, BWM) share more - the low-rank columns of their host plans, the chunk rule, the workspace
+behind pta_fstat_project and the loops over given and generated rows: SkyStatisticsMixin below.
 """
 import ctypes
 
@@ -9,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _hyper, _lib, device as dv
+from . import optimal_statistic as ost
 
 
 def check_components(components, columns=" (2 n_f <= 64 columns)"):
@@ -133,3 +136,72 @@ class StatisticsMixin:
                 self._generate(n, r0 + lo, rows, rows_of(hyper, lo, n), rows_of(cw, lo, n))
             state()
             yield lo, n, rows
+
+
+class SkyStatisticsMixin(StatisticsMixin):
+    """What the sky-grid statistics share beyond that (engine_fstat.py: Fp / Fe over a frequency grid, engine_bwm.py: the burst filter over
+    an epoch grid).  Both project the rows on C operator rows per pulsar with pta_fstat_project and hand Q [n, P C] to their own
+    kernels.  A statistic keeps its state dict (J, C, S, ntile, Wt, off, ws, ...) in an attribute of its own and passes it in as st; its
+    launch(rows [n, n_toa], n, lo, out) puts realisations lo .. lo+n-1 of the call into rows lo .. of out = make_out(R)."""
+
+    @staticmethod
+    def _sky_low_rank(toas, F_rn, phi_rn, gw_lA, components, gamma):
+        """(F_rn, phi_rn) of a host plan: per pulsar the low-rank part of C_a, the red-noise columns of _stats_noise_model (or None), then
+        the GWB auto-term of log10 amplitude gw_lA (or None) on the frequencies k / T, k <= components; (None, None) without either"""
+        P = len(toas)
+        F_low, phi_low = [[] for _ in range(P)], [[] for _ in range(P)]
+        if F_rn is not None:
+            for a in range(P):
+                F_low[a].append(F_rn[a])
+                phi_low[a].append(phi_rn[a])
+        if gw_lA is not None:
+            T = max(float(np.max(t)) for t in toas) - min(float(np.min(t)) for t in toas)
+            S = ost.unit_spectrum(int(components), T, float(gamma))
+            for a in range(P):
+                F_low[a].append(ost.fourier_basis(toas[a], int(components), T))
+                phi_low[a].append(10.0 ** (2 * gw_lA) * S)
+        if not F_low[0]:
+            return None, None
+        return [np.concatenate(x, axis=1) for x in F_low], [np.concatenate(x) for x in phi_low]
+
+    def _sky_chunk(self, st, R, sky_max, with_rows):
+        """realisations per launch sequence: Q [P, C], the per-tile maxima of sky_max (and the generated rows) within workspace_bytes.
+        The outputs of all R realisations are the call's result, not workspace."""
+        per_real = 8 * self.P * st["C"] + (12 * st["J"] * st["ntile"] if sky_max else 0) + (8 * self.n_toa if with_rows else 0)
+        return max(1, min(R, int(self.workspace_bytes) // per_real))
+
+    def _sky_project(self, st, rows, n, sky_max):
+        """Q [n, P C] of rows [n, n_toa] by pta_fstat_project on the current stream, in the statistic's workspace st["ws"] = {n, Q, pv,
+        pa} (pv / pa: the per-tile maxima and their sky indices, with sky_max), grown on demand.  Returns the workspace."""
+        P, J, C = self.P, st["J"], st["C"]
+        ws = st["ws"]
+        if ws is None or ws["n"] < n or (sky_max and ws["pv"] is None):
+            st["ws"] = None
+            ws = st["ws"] = dict(n=n, Q=dv.empty((n, P * C)), pv=dv.empty((n * J * st["ntile"],)) if sky_max else None,
+                                 pa=dv.empty((n * J * st["ntile"],), dtype=torch.int32) if sky_max else None)
+        _lib.call("pta_fstat_project", dv.ptr(st["Wt"]), self.n_toa, C, dv.ptr(st["off"]), P, ctypes.c_void_p(rows.data_ptr()), rows.stride(0), n,
+                  dv.ptr(ws["Q"]), P * C, dv.stream_ptr())
+        return ws
+
+    def _sky_rows(self, st, launch, make_out, rows, sky_max):
+        """the statistic of the given rows [R, n_toa], in chunks that keep the workspace within workspace_bytes: returns out"""
+        R = self._stats_check_rows(rows)
+        out = make_out(R)
+        step = self._sky_chunk(st, R, sky_max, with_rows=False)
+        for lo in range(0, R, step):
+            launch(rows[lo:lo + step], min(step, R - lo), lo, out)
+        return out
+
+    def _sky_generate(self, what, st, state, launch, make_out, R, r0, theta, td, chunk, sky_max):
+        """the statistic of realisations r0 .. r0+R-1, generated chunk by chunk (_stats_generate_chunks; state() re-validates the
+        prepared state behind each chunk), the chunk cut so that the rows buffer and the workspace stay within workspace_bytes:
+        returns out"""
+        R, r0, chunk = int(R), int(r0), int(chunk)
+        if R < 1 or chunk < 1 or r0 < 0:
+            raise ValueError(f"{what}: R={R}, chunk={chunk} must be >= 1 and r0={r0} >= 0")
+        hyper, det = self._theta_parts(theta, R, td=td)   # all of theta, before the first chunk is launched
+        chunk = max(1, min(chunk, self._sky_chunk(st, R, sky_max, with_rows=True)))
+        out = make_out(R)
+        for lo, n, rows in self._stats_generate_chunks(state, R, r0, hyper, det, td, chunk):
+            launch(rows, n, lo, out)
+        return out

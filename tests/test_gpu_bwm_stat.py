@@ -28,7 +28,8 @@ def _packed(Minv):
     return np.stack([Minv[..., 0, 0], Minv[..., 0, 1], Minv[..., 1, 1]], axis=-1)
 
 
-@pytest.mark.parametrize("P,J,S,R", [(23, 11, 100, 37), (68, 8, 64, 9), (2, 1, 1, 1), (5, 17, 130, 300)])
+@pytest.mark.parametrize("P,J,S,R", [(23, 11, 100, 37), (68, 8, 64, 9), (2, 1, 1, 1), (5, 17, 130, 300),
+                                     (4, 16, 64, 4), (128, 17, 65, 5)])   # one full MFMA step / epoch block / sky tile; PMAX, one past each
 def test_bwm_stat_vs_numpy_all_modes(P, J, S, R):
     from pta_replicator_amd import _lib, bwm_statistic as bst, device as dv
     Q, phi, Minv, C = _operands(P, J, S, R, P + J)

@@ -98,7 +98,8 @@ def test_fstat_fp_vs_numpy():
     assert np.all(got[:, J] == 0)
 
 
-@pytest.mark.parametrize("P,J,S,R", [(23, 11, 100, 37), (68, 8, 64, 9), (2, 1, 1, 1), (5, 17, 130, 300)])
+@pytest.mark.parametrize("P,J,S,R", [(23, 11, 100, 37), (68, 8, 64, 9), (2, 1, 1, 1), (5, 17, 130, 300),
+                                     (4, 8, 64, 8), (128, 9, 65, 5)])   # one full MFMA step / frequency block / sky tile; PMAX, one past each
 def test_fstat_fe_vs_numpy_both_modes(P, J, S, R):
     from pta_replicator_amd import _lib, device as dv, f_statistic as fst
     Q, phi, Minv, _ = _fe_operands(P, J, S, R, P + J)
@@ -297,7 +298,7 @@ def test_generate_f_statistic_bit_identical_to_f_statistic_of_generate():
     keep = eng.workspace_bytes
     eng.workspace_bytes = max(8 * 2 * len(FREQS) * eng.n_toa, 11 * 8 * eng.P * 2 * len(FREQS))
     try:
-        assert eng._fs_chunk(eng._fs, R, False, False) < R
+        assert eng._sky_chunk(eng._fs, R, False, False) < R
         assert _same(eng.f_statistic(eng.generate(R)), ref)
     finally:
         eng.workspace_bytes = keep
