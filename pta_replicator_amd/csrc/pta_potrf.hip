@@ -50,6 +50,11 @@ __device__ __forceinline__ void pta_potf2_sweep(double (&v)[4][4], double (*colb
 #pragma unroll
       for (int b = 0; b < 4; ++b) cq[b] = cb[tc + 16 * b] * r;
       bad = (!(d > 0.0) && bad == 0) ? col0 + j + 1 : bad;
+      // L[j][j] = sqrt(d) to half an ulp: d * r alone carries r's two or three roundings, and its square then misses d by more than the
+      // gamma_2 that conventional Cholesky is allowed at n = 1 (tests/td_reference.py, bound (s): 2.12 u measured against 2 u); one
+      // Heron step on the exact residual d - l0^2 repairs it.  Nothing of the step waits for it: col[] is scaled by r as before.
+      const double l0 = d * r;
+      const double ljj = fma(fma(-l0, l0, d), 0.5 * r, l0);
       // the step as selects (no branch, no store): with a, b, jq compile-time most of the conditions fold away - what is left per step
       // are four comparisons of (ti, tc) with jr and the selects of the sub-blocks in row / column jq
       const bool c_gt = tc > jr, c_eq = tc == jr, r_lt = ti < jr, r_eq = ti == jr;
@@ -65,7 +70,7 @@ __device__ __forceinline__ void pta_potf2_sweep(double (&v)[4][4], double (*colb
           const bool pgq = a > b || (a == b && diag_ge);                  // p >= q
           double nv = (qg && (pgq || pl)) ? fma(-cp[a], cq[b], v[a][b]) : v[a][b];   // Schur complement of L / X[q][p]
           nv = (qg && pe) ? -cq[b] * r : nv;                              // X[q][j] = -L[q][j] / L[j][j]
-          nv = qe ? (pe ? d * r : cp[a]) : nv;                            // column j scaled; L[j][j] = sqrt(d)
+          nv = qe ? (pe ? ljj : cp[a]) : nv;                              // column j scaled; L[j][j] = sqrt(d)
           v[a][b] = nv;
         }
     }
