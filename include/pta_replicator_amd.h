@@ -321,8 +321,11 @@ int pta_gwb_spectrum_scale_user(const int32_t *seg, const double *dx, const doub
                                 const double *log10_hc, int64_t ld_hc, double *scale, int64_t ld_scale, void *stream);
 
 /* G[r,a,:] = sum_b Mchol[a,b] G0[r,b,:]  (the M@w of red_noise.py:268, applied after the DFT). */
-/* variant 0 (default): LDS-resident Mchol kernel when P <= 80, generic batched MFMA GEMM otherwise; 1: always the generic
- * MFMA GEMM; 2: the generic VALU reference GEMM (cross-check)                                                       */
+/* variant 0 (default): LDS-resident Mchol kernel when P <= 80 (a resident grid that streams the realisations through it and reads
+ * only the lower triangle of Mchol: what lies above the diagonal is taken as zero), generic batched MFMA GEMM otherwise; 1: always
+ * the generic MFMA GEMM; 2: the generic VALU reference GEMM (cross-check); 3: the LDS kernel as it was before it streamed (one
+ * workgroup per 64 samples x 4 realisations, the full square of Mchol read; bit-identical to 0 for a lower-triangular Mchol and
+ * finite G0) - the A/B partner of variant 0, GEMM as 1 when P > 80                                                              */
 int pta_gwb_mix(const double *Mchol, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant, void *stream);
 
 /* An ORF factor per realisation (ABI 8, additive): Mchol[r] = chol(2 sum_k clm[r * ld_clm + k] basis[k]), k < n_lm = (lmax + 1)^2 <= 81,
@@ -954,7 +957,7 @@ int pta_dgemm(int transB, int M, int N, int K, double alpha, const double *A, in
  * 2: HBM write GB/s over `bytes`, 3: HBM copy GB/s, 4: Philox+Box-Muller G normals/s, 5: fp64 MFMA in the GEMM kernels'
  * register-tile pattern (4 A x 4 B fragments -> 16 accumulators), 6: that MFMA loop
  * and the FMA loop on alternating waves of the same SIMDs (sum of both rates: do they share the fp64 ALUs?).  kinds 0 / 1 / 4 / 5: `bytes` in 1..32 = 256-thread blocks per CU.       */
-int pta_microbench(int kind, int64_t bytes, int iters, int option, double *result_host);   /* option of kind 4: 0 = default fp64 transform, 1 = rng_fast, 2 = the polynomial fp64 transform (A/B) */
+int pta_microbench(int kind, int64_t bytes, int iters, int option, double *result_host);   /* option of kind 4: 0 = default fp64 transform, 1 = rng_fast, 2 = the polynomial fp64 transform (A/B); kind 9: issue rate of one VALU instruction in 16 independent chains per lane, option 0 = v_fma_f64, 1 = v_mad_u64_u32, 2 = v_bitop3_b32, `bytes` = workgroups per CU (= waves per SIMD), result in tera lane-instructions / s */
 
 /* Engine-clock probe (ABI 6): one wave on `stream` samples (s_memrealtime [100 MHz ticks], s_memtime [shader cycles]) into
  * samples[2 i], samples[2 i + 1] every `period_us` for `us` microseconds (at most max_samples pairs; unused slots zeroed).  Launch it

@@ -8,6 +8,8 @@
 // Every step is linear, so the re-association changes results only at the 1e-15 level; what it buys:
 // no length-5998 (= 2 x 2999, prime) FFT, 10x fewer flops in the mix, and the only large operand
 // (T, 28.8 MB at the headline size) is realisation independent and stays L2/Infinity-Cache resident.
+#include <algorithm>
+#include <atomic>
 #include "pta_common.h"
 #include "pta_mfma.h"
 #include "pta_rng.h"
@@ -357,14 +359,161 @@ __global__ __launch_bounds__(256) void k_gwb_mix_small(const double *__restrict_
   }
 }
 
-// variant: 0 = specialised kernel when P <= 80 (else the generic batched MFMA GEMM), 1 = always the generic MFMA GEMM,
-// 2 = the generic VALU reference GEMM
+// The same product as a streaming kernel (pta_gwb_mix's default).  An item is one realisation's 16 samples; every wave of a resident
+// grid walks a strided list of items, so the factor is staged once per workgroup for the whole launch and the last round is as full as
+// the others.  The B operand of the wave's next item is requested before the MFMAs of the present one and the stores go behind those
+// requests (two register sets, rotated by name).  Only the factor's lower triangle is read: what is staged above the diagonal is zero
+// whatever the input holds there, and tile i runs K-steps 0 .. min(4i + 3, KP/4 - 1) only.  The skipped steps added exact zeros to
+// their accumulators, so on finite input every output element is the one k_gwb_mix_small gives, bit for bit.
+//
+// Requests carry no per-lane branch and no select (either makes the compiler wait for each load where it stands): a lane past npts
+// re-reads sample npts - 1 into a B column that is never stored, a lane past row P - 1 re-reads that row and mix_item drops the
+// value.  K-steps below (NTA - 1) * 4 are whole for every P of the instance; the up to three that P decides are requested first and
+// behind a uniform branch, so the wait before the MFMAs still counts the requests behind it instead of draining them.  r and ch are
+// wave-uniform: a row's address is a scalar base plus the lane's 32-bit offset (the host sends ldg >= 2^29 to k_gwb_mix_small).
+template <int NTA>
+__device__ __forceinline__ void mix_request(double (&bv)[NTA * 4], const double *__restrict__ G0, int P, int npts, int64_t ldg, int r,
+                                            int ch, int col, int quad) {
+  const uint32_t jc = (uint32_t)min(ch * 16 + col, npts - 1);
+  const double *__restrict__ g0 = G0 + (int64_t)r * P * ldg;
+#pragma unroll
+  for (int s4 = NTA * 4 - 1; s4 >= (NTA - 1) * 4; --s4)
+    if (4 * s4 < P)  // uniform
+      bv[s4] = g0[(int64_t)(4 * s4) * ldg + ((uint32_t)min(quad, P - 1 - 4 * s4) * (uint32_t)ldg + jc)];
+  const uint32_t off = (uint32_t)quad * (uint32_t)ldg + jc;
+#pragma unroll
+  for (int s4 = 0; s4 < (NTA - 1) * 4; ++s4) bv[s4] = g0[(int64_t)(4 * s4) * ldg + off];
+}
+
+template <int NTA>
+__device__ __forceinline__ void mix_item(const double (&bv)[NTA * 4], const double *Ms, int P, int npts, int64_t ldg,
+                                         double *__restrict__ G, int r, int ch, int l) {
+  constexpr int MP = NTA * 16;
+  const int col = l & 15, quad = l >> 4;
+  pta_f64x4 acc[NTA];
+#pragma unroll
+  for (int i = 0; i < NTA; ++i) acc[i] = pta_f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s4 = 0; s4 < NTA * 4; ++s4) {
+    if (s4 < (NTA - 1) * 4 || 4 * s4 < P) {  // uniform
+      const int b = 4 * s4 + quad;
+      const double bs = (s4 < (NTA - 1) * 4 || b < P) ? bv[s4] : 0.0;
+#pragma unroll
+      for (int i = s4 >> 2; i < NTA; ++i) acc[i] = pta_mfma_f64(Ms[b * MP + i * 16 + col], bs, acc[i]);  // s4 <= 4i + 3
+    }
+  }
+  const int jj = ch * 16 + col;
+  const uint32_t off = (uint32_t)quad * (uint32_t)ldg + (uint32_t)jj;
+  if (jj < npts) {
+#pragma unroll
+    for (int i = 0; i < NTA; ++i)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg)  // row pta_mfma_row(l, rg) of tile i; only the last tile can reach past P
+        if (i < NTA - 1 || i * 16 + 4 * rg + quad < P) G[((int64_t)r * P + i * 16 + 4 * rg) * ldg + off] = acc[i][rg];
+  }
+}
+
+// items are numbered r * nch + ch; a wave steps by the grid's wave count, given as (dr, dc) = divmod(step, nch).  The wave's last item
+// has a copy of its own without a request: a branch round the requests would again make the wait ahead of the MFMAs drain them.
+#define MIX_NEXT(rn, cn)           \
+  int rn = r + dr, cn = ch + dc;   \
+  if (cn >= nch) {                 \
+    cn -= nch;                     \
+    ++rn;                          \
+  }
+template <int NTA>
+__global__ __launch_bounds__(256) void k_gwb_mix_stream(const double *__restrict__ Mchol, int P, const double *__restrict__ G0, int R,
+                                                        int npts, int64_t ldg, double *__restrict__ G, int nch, int dr, int dc) {
+  extern __shared__ double Ms[];  // [KP][MP]: Ms[b * MP + a] = Mchol[a][b] for b <= a < P, zero elsewhere
+  constexpr int MP = NTA * 16;
+  const int KP = (P + 3) & ~3;
+  const int t = threadIdx.x, l = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  for (int b = wv; b < KP; b += 4)
+    for (int a = l; a < MP; a += 64) Ms[b * MP + a] = (a < P && b <= a) ? Mchol[(int64_t)a * P + b] : 0.0;
+  __syncthreads();
+  const int col = l & 15, quad = l >> 4;
+  const int w = blockIdx.x * 4 + wv;
+  int r = w / nch, ch = w - r * nch;
+  if (r >= R) return;  // fewer items than waves
+  double b0[NTA * 4], b1[NTA * 4];
+  mix_request<NTA>(b0, G0, P, npts, ldg, r, ch, col, quad);
+  for (;;) {
+    {
+      MIX_NEXT(rn, cn)
+      if (rn >= R) {
+        mix_item<NTA>(b0, Ms, P, npts, ldg, G, r, ch, l);
+        break;
+      }
+      mix_request<NTA>(b1, G0, P, npts, ldg, rn, cn, col, quad);
+      mix_item<NTA>(b0, Ms, P, npts, ldg, G, r, ch, l);
+      r = rn, ch = cn;
+    }
+    {
+      MIX_NEXT(rn, cn)
+      if (rn >= R) {
+        mix_item<NTA>(b1, Ms, P, npts, ldg, G, r, ch, l);
+        break;
+      }
+      mix_request<NTA>(b0, G0, P, npts, ldg, rn, cn, col, quad);
+      mix_item<NTA>(b1, Ms, P, npts, ldg, G, r, ch, l);
+      r = rn, ch = cn;
+    }
+  }
+}
+#undef MIX_NEXT
+
+// resident workgroups of k_gwb_mix_stream per CU times the CU count of the current device, asked once per (KP, device): KP fixes the
+// instance and its LDS
+static int mix_stream_slots(const void *kern, int kp4, size_t shmem, int *slots) {
+  static std::atomic<int> cache[21][16];
+  int dev = 0;
+  PTA_HIP(hipGetDevice(&dev));
+  PTA_REQUIRE(dev >= 0, PTA_E_ARG, "pta_gwb_mix: device %d", dev);
+  if (dev < 16 && (*slots = cache[kp4][dev].load(std::memory_order_relaxed)) > 0) return PTA_OK;
+  int cus = 0, occ = 0;
+  PTA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  PTA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, shmem));
+  PTA_REQUIRE(cus > 0 && occ > 0, PTA_E_ARG, "pta_gwb_mix: %d CUs, %d workgroups per CU", cus, occ);
+  *slots = cus * occ;
+  if (dev < 16) cache[kp4][dev].store(*slots, std::memory_order_relaxed);
+  return PTA_OK;
+}
+
+// variant: 0 = the streaming kernel when P <= 80 (else the generic batched MFMA GEMM), 1 = always the generic MFMA GEMM,
+// 2 = the generic VALU reference GEMM, 3 = k_gwb_mix_small when P <= 80 (what variant 0 was: the A/B and bit-identity partner)
 extern "C" int pta_gwb_mix(const double *Mchol, int P, const double *G0, int R, int npts, int64_t ldg, double *G, int variant,
                            void *stream) {
   PTA_REQUIRE(Mchol && G0 && G, PTA_E_ARG, "pta_gwb_mix: NULL argument");
   PTA_REQUIRE(P > 0 && R > 0 && npts > 0 && ldg >= npts, PTA_E_ARG, "pta_gwb_mix: P=%d R=%d npts=%d", P, R, npts);
   const int64_t sr = (int64_t)P * ldg;
-  if (variant == 0 && P <= 80) {
+  if (variant == 0 && P <= 80 && ldg < (1LL << 29)) {
+    const int nta = (P + 15) / 16, kp = (P + 3) & ~3;
+    const size_t shmem = (size_t)kp * nta * 16 * sizeof(double);
+    const int nch = pta_cdiv(npts, 16);
+    const int64_t nitem = (int64_t)R * nch;
+    PTA_REQUIRE(nitem < (1LL << 31), PTA_E_ARG, "pta_gwb_mix: R=%d x npts=%d too large for one launch", R, npts);
+    int slots = 0, rc = PTA_OK;
+#define PTA_MIX(N)                                                                                                                  \
+  do {                                                                                                                              \
+    rc = mix_stream_slots((const void *)k_gwb_mix_stream<N>, kp >> 2, shmem, &slots);                                                   \
+    if (rc != PTA_OK) return rc;                                                                                                    \
+    const int nwg = (int)std::min<int64_t>(slots, nitem / 4 > 0 ? nitem / 4 : 1);                                                   \
+    const int step = nwg * 4;                                                                                                       \
+    hipLaunchKernelGGL(k_gwb_mix_stream<N>, dim3(nwg), dim3(256), shmem, pta_stream(stream), Mchol, P, G0, R, npts, ldg, G, nch,   \
+                       step / nch, step % nch);                                                                                     \
+  } while (0)
+    switch (nta) {
+      case 1: PTA_MIX(1); break;
+      case 2: PTA_MIX(2); break;
+      case 3: PTA_MIX(3); break;
+      case 4: PTA_MIX(4); break;
+      default: PTA_MIX(5); break;
+    }
+#undef PTA_MIX
+    PTA_LAUNCH_CHECK();
+    return PTA_OK;
+  }
+  if ((variant == 0 || variant == 3) && P <= 80) {
     const int nta = (P + 15) / 16, kp = (P + 3) & ~3;
     const int rpw = 4;
     const size_t shmem = (size_t)kp * nta * 16 * sizeof(double);

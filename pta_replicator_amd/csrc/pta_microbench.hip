@@ -182,6 +182,54 @@ __global__ __launch_bounds__(256) void k_mb_rng(double *out, int iters, int fast
   if (s == 123.456) out[0] = s;
 }
 
+// issue rate of one VALU instruction (kind 9): 16 independent chains per lane, nothing else in the loop.  OP 0 = v_fma_f64, 1 =
+// v_mad_u64_u32 (the Philox multiply: 32 x 32 + 64 -> 64), 2 = v_bitop3_b32 (the Philox 3-input xor).  The ratios are what the
+// instruction-count estimates of DESIGN 4.1 weigh the integer multiply with.
+template <int OP>
+__global__ __launch_bounds__(256) void k_mb_issue(double *out, int iters) {
+  if (OP == 0) {
+    double x[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = 1.0 + i * 1e-3 + threadIdx.x * 1e-9;
+    const double a = 1.0000001, b = 1e-9;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) x[i] = fma(x[i], a, b);
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += x[i];
+    if (s == 123.456) out[0] = s;
+  } else if (OP == 1) {
+    uint64_t x[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = 0x9E3779B97F4A7C15ull * (uint64_t)(threadIdx.x + 256 * i + 1);
+    const uint32_t m = 0xD2511F53u + 2u * threadIdx.x;
+    const uint64_t k = 0xBB67AE8584CAA73Bull + threadIdx.x;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) x[i] = (uint64_t)(uint32_t)x[i] * m + k;
+    }
+    uint64_t s = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s ^= x[i];
+    if (s == 123456u) out[0] = 1.0;
+  } else {
+    uint32_t x[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) x[i] = 0x9E3779B9u * (threadIdx.x + 256u * i + 1u);
+    const uint32_t k = 0xBB67AE85u + threadIdx.x;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) x[i] = __builtin_amdgcn_bitop3_b32(x[i], x[(i + 5) & 15], k, 0x96);  // operands of the previous pass
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += x[i];
+    if (s == 123456u) out[0] = 1.0;
+  }
+}
+
 extern "C" int pta_microbench(int kind, int64_t bytes, int iters, int option, double *result_host) {
   PTA_REQUIRE(result_host && iters > 0, PTA_E_ARG, "pta_microbench: bad argument");
   int dev = 0;
@@ -190,7 +238,7 @@ extern "C" int pta_microbench(int kind, int64_t bytes, int iters, int option, do
   PTA_HIP(hipGetDeviceProperties(&prop, dev));
   const int cus = prop.multiProcessorCount;
   // kinds 0/1/4: `bytes` in 1..32 selects the number of 256-thread blocks per CU (= waves per SIMD); default 8
-  const int bpc = ((kind == 0 || kind == 1 || kind == 4 || kind == 5 || kind == 6 || kind == 8) && bytes >= 1 && bytes <= 32) ? (int)bytes : 8;
+  const int bpc = ((kind == 0 || kind == 1 || kind == 4 || kind == 5 || kind == 6 || kind == 8 || kind == 9) && bytes >= 1 && bytes <= 32) ? (int)bytes : 8;
   // kind 7: `option` = bytes per row segment (256 .. 8192), `bytes` = total bytes written per launch (blocks of 5000 x 5008 doubles)
   const int s7_rows = 5000, s7_ld2 = 5008 / 2;
   const int s7_seg = option & 0xFFFF, s7_lds = (option >> 16) * 1024;  // option = bytes per row segment | (KB of dynamic LDS per workgroup << 16): 70 KB -> two workgroups per CU, as k_td_cov_walk
@@ -256,6 +304,12 @@ extern "C" int pta_microbench(int kind, int64_t bytes, int iters, int option, do
           work = (double)cus * bpc * 4 * iters * (double)(na == 1 || na == 2 || na == 4 || na == 8 || na == 12 ? na : 16) * 2048.0 * reps;
           break;
         }
+        case 9:  // result: tera lane-instructions per second
+          if (option == 0) hipLaunchKernelGGL(k_mb_issue<0>, dim3(cus * bpc), dim3(256), 0, 0, buf, iters);
+          else if (option == 1) hipLaunchKernelGGL(k_mb_issue<1>, dim3(cus * bpc), dim3(256), 0, 0, buf, iters);
+          else hipLaunchKernelGGL(k_mb_issue<2>, dim3(cus * bpc), dim3(256), 0, 0, buf, iters);
+          work = (double)cus * bpc * 256 * iters * 16.0 * reps;
+          break;
         case 4:
           hipLaunchKernelGGL(k_mb_rng, dim3(cus * bpc), dim3(256), 0, 0, buf, iters, option);
           work = (double)cus * bpc * 256 * iters * 2.0 * reps;  // normals
