@@ -649,6 +649,38 @@ int pta_engine_wn_params(const pta_engine_wn_hyper *wn_host, int R, void *stream
 int pta_engine_wn_add(const pta_engine_plan *plan_host, const pta_engine_wn_hyper *wn_host, uint64_t seed, uint64_t r0, int R, double *out,
                       int64_t ld_out, int accumulate, void *stream);
 
+/* ---------------------------------------------------------------- one chromatic Gaussian process per pulsar (ABI 8, additive) */
+/* dt_i = (nu_ref / nu_i)^chi sum_c F_ic sqrt(phi_c) z_c per pulsar (DM variations at chi = 2), F and phi those of the red noise
+ * (red_noise.py:106-128), z from stream (CHROM = 10, pulsar) of the realisation.  The row weights are part of the design matrix the
+ * caller hands over.  Added after the fused synthesis, like the terms above.  Device pointers.                                   */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t k;                  /* K_c = 2 x components, even */
+  int32_t rng_fast;           /* the Gaussian transform of the plan's rng_fast */
+  const double *Ft;           /* [k x ldf] weighted design matrix over the concatenated TOAs, row c = column c of w . F */
+  int64_t ldf;                /* >= n_toa */
+  const double *amp;          /* [n_psr x k] configured sqrt(phi), a row of zeros = no process for that pulsar */
+  const double *f;            /* [n_psr x k / 2] frequencies [Hz] of the column pairs (read with log10_A) */
+  const double *tspan;        /* [n_psr] Tspan [s] (read with log10_A) */
+  const double *log10_A;      /* [R x ld_theta] labels of realisation r0 + r, NaN = as configured; NULL = all as configured */
+  const double *gamma;        /* [R x ld_theta] likewise (needed beside log10_A) */
+  int64_t ld_theta;           /* >= n_psr */
+  double *coef;               /* [R x n_psr x k] sqrt(phi) z, written by pta_engine_chrom_coef, read by pta_engine_chrom_add */
+} pta_chrom_engine;
+
+/* coef[(r * P + a) * k + c] = amp(r, a, c) * z, z = deviate c of stream (CHROM, a) of realisation r0 + r: pair c >> 1, branch c & 1 (the
+ * mapping pta_engine_rn_coef uses for stream RN).  amp = the configured table, or - log10_A given and not NaN at (r, a) -
+ * sqrt(A^2 (f / f_yr)^-gamma / (12 pi^2 Tspan) yr^3) at the column's frequency.  One thread per (r, a, pair).                   */
+int pta_engine_chrom_coef(const pta_chrom_engine *chrom_host, uint64_t seed, uint64_t r0, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum_c Ft[c * ldf + i] coef[(r * P + a) * k + c] for r < R, a the pulsar of TOA i (accumulate = 1 adds, 0
+ * writes), over the plan's TOA tiles (tile_psr / tile_start / tile_count, n_tiles, n_psr, n_toa; nothing else of the plan is read).  The
+ * product runs on the fp64 matrix cores in a fixed order of c: a realisation's term is bit-identical in every batch, row slot and view.
+ * Two adjacent TOAs per lane and 16-byte accesses wherever the row's address allows; out and ld_out need 8-byte alignment only.
+ * Nothing outside the tiles' columns is touched.  No atomics.                                                                    */
+int pta_engine_chrom_add(const pta_engine_plan *plan_host, const pta_chrom_engine *chrom_host, int R, double *out, int64_t ld_out,
+                         int accumulate, void *stream);
+
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,
  * which never forms an N_toa x N_toa object: SURVEY.md §0.2, App. A.1).

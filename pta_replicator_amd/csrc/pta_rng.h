@@ -34,6 +34,7 @@
 #define PTA_STREAM_HYPER 7u // pulsar field 0: per-realisation hyperparameters, pair p = parameter column j, uniform u2 (pta_hyper.h); field 1: spectrum nodes
 #define PTA_STREAM_CW 8u    // pulsar field s: CW labels of source s of the realisation, pair p = label column j, uniform u2 (pta_cw_hyper.h, pta_cw_catalog.h)
 #define PTA_STREAM_BWM 9u   // pulsar field 0: per-realisation burst-with-memory labels, pair p = label column j, uniform u2 (pta_bwm.h)
+#define PTA_STREAM_CHROM 10u // + pulsar index: pair p -> coefficients (2p, 2p+1) of the chromatic process (pta_chrom.h), as stream RN
 
 PTA_HD uint32_t pta_stream_id(uint32_t kind, uint32_t pulsar) { return (kind << 24) | (pulsar & 0xFFFFFFu); }
 

@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _cw, _hyper, _lib, _wn_hyper, device as dv
+from . import _bwm, _chrom, _cw, _hyper, _lib, _wn_hyper, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -45,6 +45,8 @@ STREAM_HYPER = 7   # per-realisation hyperparameters (generate_sampled): stream_
                    # stream_id(7, 3 .. 5), pair = group: the per-realisation EFAC, log10 EQUAD and log10 ECORR (_wn_hyper.FIELD)
 STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream_id(8, 0), pair = label column (_cw.COLUMNS)
 STREAM_BWM = 9     # per-realisation burst-with-memory labels (generate_sampled): stream_id(9, 0), pair = label column (_bwm.COLUMNS)
+STREAM_CHROM = _chrom.STREAM_CHROM   # 10: the chromatic process, stream_id(10, pulsar), pair c >> 1, branch c & 1 = coefficient c (as STREAM_RN);
+                                     # its prior boxes: stream_id(7, 6 .. 7), pair = pulsar (_chrom.FIELD)
 
 
 def stream_id(kind, pulsar):
@@ -76,6 +78,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._delays = None
         self._cw = None      # one CW source per realisation (set_cw), parameters from theta / set_cw_prior
         self._bwm = False    # one burst with memory per realisation (set_bwm), parameters from theta / set_bwm_prior
+        self._chrom = None   # one chromatic Gaussian process per pulsar (set_chromatic_noise), added after the fused launch
+        self._chrom_t = None   # its device tables, built by prepare()
         # state of the per-realisation terms (engine_terms.py): per term the buffers its queued launches still read, replaced when the
         # term next runs; the reused device tables (_scratch); the device copies of the prior boxes (_uniform_table)
         self._keep, self._scratch_tabs, self._boxes = {}, {}, {}
@@ -106,6 +110,16 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._rn = dict(A=list(np.broadcast_to(np.asarray(log10_amplitude, dtype=object), (self.P,))),
                         g=list(np.broadcast_to(np.asarray(spectral_index, dtype=object), (self.P,))),
                         components=int(components), libstempo=bool(libstempo_convention))
+        self._prepared = False
+
+    def set_chromatic_noise(self, log10_amplitude, spectral_index, components=30, index=2.0, ref_freq_mhz=1400.0):
+        """one chromatic power-law Gaussian process per pulsar, dt_i = (ref_freq_mhz / nu_i)^index sum_k F_ik sqrt(phi_k) z_k with the
+        basis and prior of the red noise (red_noise.py:106-128) and `components` frequencies of its own: index 2 = DM variations.
+        Amplitude and spectral index per pulsar as in set_red_noise (a scalar or a list; None = no process for that pulsar).  The
+        radio frequencies come from the pulsars (toas.freqs_mhz, else toas.get_freqs()).  Drawn from stream (10, pulsar) and added
+        after the fused launch (pta_engine_chrom_coef -> pta_engine_chrom_add); theta's chrom_log10_A / chrom_gamma [R, P] give it
+        parameters per realisation (_chrom).  Not available in TD mode, nor under the theta-matched OS and the likelihood."""
+        self._chrom = _chrom.make_config(self.P, log10_amplitude, spectral_index, components, index, ref_freq_mhz)
         self._prepared = False
 
     def set_white_noise(self, efac=1.0, log10_equad=None, flagid="f", flags=None, tnequad=False):
@@ -161,6 +175,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._ws = None  # tables of a previous prepare() point at replaced buffers
         self._hy = None  # and the hyper path's tables describe the previous configuration
         self._wnh = None  # and so do the group tables of the per-realisation white noise
+        self._chrom_t = None  # and the tables of the chromatic process
         self._td_prepared = False  # and so do the dense factors of TD mode
         self._gw_grid_ready = False
         s = dv.stream_ptr()
@@ -347,6 +362,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             if self._det:
                 torch.cuda.current_stream().synchronize()      # once, not once per pulsar per source
             pl.det = self.d_det.data_ptr()
+        if self._chrom is not None:
+            self._prepare_chrom()
         self._prepared = True
         # set-up time is where one-off driver costs belong: with measurement noise configured the dense path can follow, and the
         # factorisation's internal streams (hardware queues, ~10 ms each on this stack: profiles/r05_prepare_td_first_call.txt) are
@@ -354,6 +371,57 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         if self._wn is not None and getattr(self, "td_warmup", True):
             _lib.call("pta_potrf_warmup", 2)
         return self
+
+    def _chrom_host_tables(self):
+        """the host half of the chromatic tables, NumPy alone: the row weights w [n_toa] = (nu_ref / nu_i)^chi, per pulsar the
+        frequencies k / Tspan [K_c / 2], Tspan [P], and the configured sqrt(prior) amp [P, K_c] (a row of zeros = no process)"""
+        c = self._chrom
+        P, nm = self.P, c["components"]
+        w = np.concatenate([_chrom.weights(_chrom.toa_freqs(p), c["index"], c["ref"], name=f"pulsar {p.name}") for p in self.psrs])
+        amp, freqs, tspan = np.zeros((P, 2 * nm)), [], np.zeros(P)
+        for a in range(P):
+            lA, g = c["A"][a], c["g"][a]
+            toas = self.tdb_s[a]
+            tspan[a] = toas.max() - toas.min()
+            freqs.append(1.0 * np.arange(1, nm + 1) / tspan[a])
+            if lA is not None and g is not None:
+                amp[a] = np.sqrt(_chrom.prior_phi(freqs[a], tspan[a], lA, g))
+        return dict(K=2 * nm, w=w, amp_host=amp, freqs=freqs, tspan_host=tspan)
+
+    def _prepare_chrom(self):
+        """the tables of the chromatic process (self._chrom_t), buffers of their own beside everything prepare() built: the weighted design
+        matrix Ft [K_c, n_toa] (pta_rn_basis, its rows then scaled by the host's weights - no device pow), the configured amplitudes amp
+        [P, K_c], and frequencies [P, K_c / 2] and Tspan [P] of the theta path"""
+        t = self._chrom_host_tables()
+        c = self._chrom
+        N, nm = self.n_toa, c["components"]
+        s = dv.stream_ptr()
+        Ft = dv.zeros((t["K"], N))
+        keep = []
+        for a in range(self.P):
+            if c["A"][a] is None or c["g"][a] is None:
+                continue
+            t_d, f_d = dv.f64(self.tdb_s[a]), dv.f64(t["freqs"][a])
+            keep += [t_d, f_d]
+            _lib.call("pta_rn_basis", dv.ptr(t_d), len(self.tdb_s[a]), ctypes.c_double(0.0), dv.ptr(f_d), None, nm, 0,
+                      ctypes.c_void_p(Ft.data_ptr() + 8 * int(self.off[a])), N, s)
+        Ft *= dv.f64(t["w"]).unsqueeze(0)
+        torch.cuda.current_stream().synchronize()  # the temporaries die with the call
+        t.update(Ft=Ft, amp=dv.f64(t["amp_host"]), f=dv.f64(np.stack(t["freqs"])), tspan=dv.f64(t["tspan_host"]))
+        self._chrom_t = t
+
+    def _chrom_low_rank_host(self):
+        """(F [P][N_a, K_c], phi [P][K_c]): the weighted chromatic basis w_i times sin / cos of 2 pi f t as prepare() puts it on the
+        device, and the configured prior - the columns the fixed-noise statistics add to the low-rank part of C_a.  NumPy alone."""
+        t = self._chrom_t if self._chrom_t is not None else self._chrom_host_tables()
+        F_all = []
+        for a in range(self.P):
+            tdb, f = self.tdb_s[a], t["freqs"][a]
+            arg = 2 * np.pi * tdb[:, None] * f[None, :]
+            F = np.empty((len(tdb), 2 * len(f)))
+            F[:, 0::2], F[:, 1::2] = np.sin(arg), np.cos(arg)
+            F_all.append(t["w"][self.off[a]:self.off[a + 1], None] * F)
+        return F_all, [t["amp_host"][a] ** 2 for a in range(self.P)]
 
     def psrs_ideal_view(self):
         """objects exposing first_MJD/last_MJD of the IDEAL TOAs for the GWB grid (red_noise.py:182-183)."""
@@ -465,7 +533,9 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         redraws the same deviates (same stream, same counter: dump_draws is unchanged) with the realisation's own amplitudes, ahead
         of the CW / BWM terms.  Fixed-noise statistics evaluated on such realisations (generate_os and the other generate_* with these
         keys in the generation theta) weight with the configured white noise, as they do for red-noise keys; as a statistic's noise
-        model (optimal_statistic(theta=), matched=True, likelihood grids), in TD mode and in wn_mode "single" the keys are refused."""
+        model (optimal_statistic(theta=), matched=True, likelihood grids), in TD mode and in wn_mode "single" the keys are refused.  On an engine
+        configured with set_chromatic_noise theta may hold chrom_log10_A, chrom_gamma [R, P] (pta_replicator_amd._chrom), with the rules of
+        the red-noise keys; the chromatic term is added last, after the CW / BWM terms."""
         hyper, cw = self._theta_parts(theta, R)
         return self._generate(R, r0, out, hyper, cw)
 
@@ -573,7 +643,11 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             bad = torch.nonzero(info).flatten()
             if bad.numel():
                 raise np.linalg.LinAlgError(f"Matrix is not positive definite (gwb_clm of realisation {r0 + int(bad[0])}: its ORF)")
-        return self._det_apply(cw, R, out) if cw else out
+        if cw:
+            self._det_apply(cw, R, out)
+        if self._chrom is not None:   # last, so that a row is the row of the engine without the process plus the term: one add
+            self._chrom_apply(cw, R, r0, out)
+        return out
 
     def _theta_device(self, th, R, mask_unconfigured=True):
         """validated theta -> contiguous float64 device tensors, keys not given filled with the configured values:
@@ -650,9 +724,11 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         all NaN and flagged, not raised.  Sampled white noise comes back as wn_efac, wn_log10_equad [R, G_wn] and wn_log10_ecorr
         [R, G_ec], group j drawn from stream (7, 3), (7, 4), (7, 5), pair j: no other label or residual moves."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        wn_prior = getattr(self, "_wn_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None:
+        wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None:
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
+        if chrom_prior is not None and self._chrom is None:
+            raise ValueError("generate_sampled: chromatic boxes given but no chromatic process is configured (set_chromatic_noise)")
         if prior is not None:
             _hyper.check_config(prior.keys(), self._gw, self._rn, self.gwb_mode)
         if wn_prior is not None:
@@ -711,7 +787,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer; for a catalogue the
         sum over its sources, pta_engine_cw_catalog_add); with BWM keys 'bwm', the per-realisation burst-with-memory term alone
         (pta_engine_bwm_add writing its own buffer); with white-noise keys (wn_efac / wn_log10_equad, wn_log10_ecorr) 'wn' and 'ecorr' are the
-        per-realisation terms (pta_engine_wn_add writing its own buffer)."""
+        per-realisation terms (pta_engine_wn_add writing its own buffer); on an engine with a chromatic process
+        (set_chromatic_noise) 'chrom', that term alone (pta_engine_chrom_add writing its own buffer)."""
         hyper, cw = self._theta_parts(theta, R)
         if not self._prepared:
             self.prepare()
@@ -756,6 +833,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             out["cw"] = self._cw_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         if _bwm.has_keys(cw):
             out["bwm"] = self._bwm_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
+        if self._chrom is not None:
+            out["chrom"] = self._chrom_apply(cw, R, r0, dv.empty((R, self.n_toa)), accumulate=False)
         return out
 
     def stream_to_host(self, total, chunk=480, r0=0):
@@ -797,7 +876,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
     # ---------------------------------------------------------------- replay mode ---------------
     def dump_draws(self, r):
         """The normals realisation r uses in generate(), as NumPy arrays in the reference's shapes:
-        {'gwb': w[P,Nf] complex, 'rn': [z[K]], 'wn': [(z1[N_a], z2[N_a])], 'ecorr': [z[E_a]]}."""
+        {'gwb': w[P,Nf] complex, 'rn': [z[K]], 'wn': [(z1[N_a], z2[N_a])], 'ecorr': [z[E_a]], 'chrom': [z[K_c]]}."""
         self._require_reference_draws("dump_draws")
         if not self._prepared:
             self.prepare()
@@ -832,13 +911,20 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
                 buf = dv.empty((2 * npair,))
                 _lib.call("pta_rng_fill_normal", self.seed, r, 1, stream_id(STREAM_ECORR, a), npair, 1, dv.ptr(buf), None, 2 * npair, int(self.rng_fast), s)
                 d["ecorr"].append(buf.cpu().numpy()[:ne])
+        if self._chrom is not None:
+            Kc = self._chrom_t["K"]
+            d["chrom"] = []
+            for a in range(self.P):
+                buf = dv.empty((Kc,))
+                _lib.call("pta_rng_fill_normal", self.seed, r, 1, stream_id(STREAM_CHROM, a), Kc // 2, 1, dv.ptr(buf), None, Kc, int(self.rng_fast), s)
+                d["chrom"].append(buf.cpu().numpy())
         return d
 
     def replay(self, draws_list, per_signal=False):
         """Push caller-supplied draws through the per-signal kernels (replay mode / parity path).
 
         draws_list: one dict per realisation, shaped like dump_draws().  Returns out[R, n_toa] (device), or with
-        per_signal=True a dict of such tensors keyed 'rn', 'gwb', 'wn', 'ecorr', 'det', 'total'."""
+        per_signal=True a dict of such tensors keyed 'rn', 'chrom', 'gwb', 'wn', 'ecorr', 'det', 'total' (the order 'total' sums them in)."""
         self._require_reference_draws("replay")
         if not self._prepared:
             self.prepare()
@@ -859,6 +945,21 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
                           ctypes.c_void_p(coef_d.data_ptr() + 8 * a * self.K), P * self.K, R,
                           ctypes.c_void_p(out.data_ptr() + 8 * int(self.off[a])), N, 0, s)
             sig["rn"] = out
+        if self._chrom is not None:   # the red-noise synthesis on the weighted design matrix
+            t = self._chrom_t
+            Kc = t["K"]
+            coef = np.zeros((R, P, Kc))
+            for r, d in enumerate(draws_list):
+                for a in range(P):
+                    coef[r, a] = t["amp_host"][a] * d["chrom"][a]
+            ccoef_d = dv.f64(coef)
+            out = dv.zeros((R, N))
+            for a in range(P):
+                n = int(self.counts[a])
+                _lib.call("pta_rn_synth", ctypes.c_void_p(t["Ft"].data_ptr() + 8 * int(self.off[a])), N, n, Kc,
+                          ctypes.c_void_p(ccoef_d.data_ptr() + 8 * a * Kc), P * Kc, R,
+                          ctypes.c_void_p(out.data_ptr() + 8 * int(self.off[a])), N, 0, s)
+            sig["chrom"] = out
         if pl.gw_npts:
             Nf, npts = self.grid["Nf"], pl.gw_npts
             w = np.zeros((R, P, Nf, 2))
@@ -899,7 +1000,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             del keep
             sig["ecorr"] = out
         total = dv.zeros((R, N))
-        for k in ("rn", "gwb", "wn", "ecorr"):
+        for k in ("rn", "chrom", "gwb", "wn", "ecorr"):
             if k in sig:
                 total += sig[k]
         if pl.det:

@@ -24,7 +24,7 @@ state checks are its base StatisticsMixin's, shared with the optimal statistic a
 """
 import torch
 
-from . import _cw, _lib, device as dv
+from . import _chrom, _cw, _lib, device as dv
 from . import f_statistic as fst
 from ._position import ra_dec
 from .engine_stats import SkyStatisticsMixin, check_components, check_timing_model
@@ -124,6 +124,8 @@ class FStatisticMixin(SkyStatisticsMixin):
         the statistics are kept.  Same results as f_statistic(generate(R, r0, ...), sky_max), bit for bit, whatever the chunk.  The
         chunk is cut so that the buffer and Q stay within workspace_bytes.  theta only shapes the data: the statistic's noise weights
         stay the configured ones."""
+        if td:
+            _chrom.refuse_td(self._chrom, "generate_f_statistic(td=True)")
         st = self._fs_state("generate_f_statistic", sky_max)
         out = self._sky_generate("generate_f_statistic", st, lambda: self._fs_state("generate_f_statistic"), self._fs_launch,
                                  lambda R: self._fs_out(st, R, sky_max), R, r0, theta, td, chunk, sky_max)

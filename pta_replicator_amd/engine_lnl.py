@@ -22,7 +22,7 @@ buffer) is shared too: engine_stats.StatisticsMixin.
 """
 import ctypes
 
-from . import _cw, _hyper, _lib, device as dv
+from . import _chrom, _cw, _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
@@ -37,6 +37,7 @@ class LikelihoodMixin(StatisticsMixin):
         K = red-noise columns + 2 n_f <= 128."""
         check_components(components)
         check_timing_model(timing_model)
+        _chrom.refuse_matched(self._chrom, "prepare_likelihood")
         self._stats_need_noise("the likelihood")
         gw_lA = self._stats_gwb_auto(gwb_auto)
         K_rn = 2 * self._rn["components"] if self._rn is not None else 0
@@ -155,6 +156,7 @@ class LikelihoodMixin(StatisticsMixin):
         noise / the prepared common process; cw_* keys are refused.  Returns {"lnl": [R, G]} and, with per_pulsar=True, also
         {"lnl_pulsar": [R, P, G]} (device tensors, views with free strides); lnl is the sum of lnl_pulsar over the pulsars in
         ascending order.  G and R are cut into chunks that keep the workspace within workspace_bytes."""
+        _chrom.refuse_noise_model(grid)
         st = self._lnl_state("log_likelihood")
         R = self._stats_check_rows(rows)
         th, G = self._lnl_check_grid(st, grid)
@@ -170,6 +172,9 @@ class LikelihoodMixin(StatisticsMixin):
         generate_td with td=True, or generate(theta=...) with theta = per-realisation parameters of the R realisations); only ln L is
         kept.  Same results as log_likelihood(generate(R, r0, ...), grid), bit for bit, whatever the chunk.  The chunk is cut so that
         the buffer and the likelihood's workspace stay within workspace_bytes."""
+        if td:
+            _chrom.refuse_td(self._chrom, "generate_lnl(td=True)")
+        _chrom.refuse_noise_model(grid)
         st = self._lnl_state("generate_lnl")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:

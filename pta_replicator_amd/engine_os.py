@@ -33,7 +33,7 @@ import ctypes
 
 import numpy as np
 
-from . import _hyper, _lib, device as dv
+from . import _chrom, _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -59,6 +59,8 @@ class OptimalStatisticMixin(StatisticsMixin):
         [n_lm, n_lm] (optimal_statistic.joint_weights; pta_os_pairs with the joint weights, 8 rows per call).  Needs at least
         (L+1)^2 pairs.  The fixed-noise statistic only: not together with matched=True, and the per-frequency OS does not carry it."""
         check_components(components)
+        if matched:
+            _chrom.refuse_matched(self._chrom, "prepare_optimal_statistic(matched=True)")
         if anisotropy_lmax is not None:
             if isinstance(anisotropy_lmax, bool) or not isinstance(anisotropy_lmax, (int, np.integer)) or not 0 <= anisotropy_lmax <= anis.LMAX_SUPPORTED:
                 raise ValueError(f"anisotropy_lmax={anisotropy_lmax!r}: an integer 0 .. {anis.LMAX_SUPPORTED}")
@@ -125,6 +127,7 @@ class OptimalStatisticMixin(StatisticsMixin):
         prepared; cw_* keys are ignored).  sigma is then [R, n_orf] and sigma_pair [R, n_pairs].  With gwb_log10_hc [R, M] (an engine
         configured with a userSpec, the statistic prepared with the GW auto-term) the GW auto-term of row r follows its own spectrum;
         the broadband template S(gamma) stays the prepared one."""
+        _chrom.refuse_noise_model(theta)
         st = self._os_state("optimal_statistic")
         R = self._stats_check_rows(rows)
         if theta is not None:
@@ -194,6 +197,10 @@ class OptimalStatisticMixin(StatisticsMixin):
         chunk stay within workspace_bytes.  The matched noise model ignores theta's gwb_clm as it ignores cw_*: its GW auto-term stays the
         isotropic one; it refuses the white-noise keys (its per-TOA weights are built once, from the configured white noise).  Prepared
         with anisotropy_lmax the result also has a2clm, clm_sigma and clm_cov (not with matched=True)."""
+        if td:
+            _chrom.refuse_td(self._chrom, "generate_os(td=True)")
+        if matched:
+            _chrom.refuse_noise_model(theta)
         st = self._os_state("generate_os")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:

@@ -43,7 +43,9 @@ class StatisticsMixin:
     def _stats_noise_model(self, timing_model):
         """(toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M): the noise model prepare() holds, as per-pulsar host arrays in the form
         the plan builders of optimal_statistic.py / f_statistic.py take (None where the engine has no ECORR / red noise / timing
-        model); prepares the engine if it is not"""
+        model); prepares the engine if it is not.  F_rn / phi_rn are the low-rank part of C_a: the red-noise columns, then - on an engine
+        with a chromatic process - its weighted columns w . F_chrom with phi_chrom (the matched OS and the likelihood, whose columns are
+        the red noise's alone, refuse such an engine before they get here)"""
         if not self._prepared:
             self.prepare()
         from .simulate import timing_design_matrix
@@ -57,6 +59,10 @@ class StatisticsMixin:
         if self.plan.rn_k:
             F_rn = [self._rn_basis_host(a) for a in range(P)]
             phi_rn = [self.rn_amp[a] ** 2 for a in range(P)]
+        if self._chrom is not None:   # the chromatic columns w . F_chrom join the low-rank part beside the red-noise ones
+            F_ch, phi_ch = self._chrom_low_rank_host()
+            F_rn = F_ch if F_rn is None else [np.concatenate([x, y], axis=1) for x, y in zip(F_rn, F_ch)]
+            phi_rn = phi_ch if phi_rn is None else [np.concatenate([x, y]) for x, y in zip(phi_rn, phi_ch)]
         M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
         return toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M
 

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _cw, _hyper, _lib, _wn_hyper, device as dv
+from . import _bwm, _chrom, _cw, _hyper, _lib, _wn_hyper, device as dv
 from ._position import ra_dec
 
 
@@ -54,7 +54,7 @@ class PerRealisationTermsMixin:
         return self
 
     def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None,
-                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None):
+                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None, chrom_log10_A=None, chrom_gamma=None):
         """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array;
         gwb_log10_hc (needs set_gwb(userSpec=U [M, 2])): (lo, hi) for every node or [M, 2], box j for row j of U as given - a free
         spectrum per realisation.  gwb_clm (needs set_gwb(lmax=L >= 1)): (lo, hi) for every c_lm with l >= 1 or [(L+1)^2 - 1, 2], box j for
@@ -63,13 +63,17 @@ class PerRealisationTermsMixin:
         sum_{l>=1} |c_lm| max|Y_lm| <= c_00 Y_00 guarantees (real harmonics: Y_00 = 1 / sqrt(4 pi), max|Y_1m| = sqrt(3 / 4 pi)); a
         wider box may draw skies that are not, which come back flagged (generate_sampled).  wn_efac, wn_log10_equad (need
         set_white_noise) and wn_log10_ecorr (needs set_jitter): (lo, hi) for every group or [G, 2], G = len(wn_groups) or
-        len(ecorr_groups), box j for group j.  Parameters left out keep their configured values.  No prepare() needed after a change."""
+        len(ecorr_groups), box j for group j.  chrom_log10_A, chrom_gamma (need set_chromatic_noise): (lo, hi) for every pulsar or [P, 2],
+        drawn from stream (7, 6) and (7, 7), pair = pulsar (_chrom.FIELD).  Parameters left out keep their configured values.  No prepare()
+        needed after a change."""
         wn_prior = _wn_hyper.make_prior(len(self.wn_groups), len(self.ecorr_groups), wn_efac=wn_efac, wn_log10_equad=wn_log10_equad,
                                         wn_log10_ecorr=wn_log10_ecorr) or None
-        prior = None   # (white-noise boxes alone are a prior; nothing at all is _hyper.make_prior's "no parameter given")
-        if wn_prior is None or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
+        chrom_prior = _chrom.make_prior(self.P, chrom_log10_A=chrom_log10_A, chrom_gamma=chrom_gamma) or None
+        prior = None   # (white-noise or chromatic boxes alone are a prior; nothing at all is _hyper.make_prior's "no parameter given")
+        if (wn_prior is None and chrom_prior is None) or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
             prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
                                       rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
+        self._chrom_prior = chrom_prior
         self._prior, self._wn_prior = prior, wn_prior   # new dicts: the device copies of the previous boxes are not theirs (_uniform_table)
         return self
 
@@ -78,16 +82,18 @@ class PerRealisationTermsMixin:
         """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
         (_hyper.check_theta), None for the fixed-parameter path (no theta, or the keys of det alone); det: the keys whose terms are
         added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta) and the white-noise keys
-        (_wn_hyper.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
+        (_wn_hyper.check_theta) and the chromatic keys (_chrom.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
         skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
             return None, {}
         if _hyper.ORF_INFO_KEY in theta:   # a label of sampled theta, no parameter
             theta = {k: v for k, v in theta.items() if k != _hyper.ORF_INFO_KEY}
         rest, wnk = _wn_hyper.split(theta)   # ahead of _hyper.check_theta, whose key list stays the GWB / red-noise one
+        rest, chk = _chrom.split(rest)
         rest, cw = _cw.split(rest)
         rest, bwm = _bwm.split(rest)
         if td:
+            _chrom.refuse_td(self._chrom)
             _wn_hyper.refuse_td(wnk)
         if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
@@ -95,6 +101,7 @@ class PerRealisationTermsMixin:
         det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
         det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
         det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
+        det.update(_chrom.check_theta(chk, R, self.P, self._chrom, check_values))
         if det and not rest:
             return None, det
         return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
@@ -119,16 +126,17 @@ class PerRealisationTermsMixin:
             tab = self._scratch_tabs[name] = tuple(dv.empty(sh) for sh in shapes)
         return tab[0] if len(shapes) == 1 else tab
 
-    def _term_batches(self, params, add, struct, rows, R, step, out, accumulate):
+    def _term_batches(self, params, add, struct, rows, R, step, out, accumulate, draw=None):
         """out[R, n_toa] (+)= a term in batches of `step` realisations: per batch the entry `params` fills the tables of the filled
         ctypes struct, then the entry `add` walks the engine's tiles.  rows: [(field, tensor or None, bytes per row)], the members of
-        the struct that follow the batch (None stays NULL)."""
+        the struct that follow the batch (None stays NULL).  draw = (seed, r0): `params` draws, and takes (seed, first realisation of the
+        batch) behind the struct."""
         s = dv.stream_ptr()
         for lo in range(0, R, step):
             n = min(step, R - lo)
             for field, t, nbytes in rows:
                 setattr(struct, field, None if t is None else t.data_ptr() + nbytes * lo)
-            _lib.call(params, ctypes.byref(struct), n, s)
+            _lib.call(params, ctypes.byref(struct), *(() if draw is None else (draw[0], draw[1] + lo)), n, s)
             _lib.call(add, ctypes.byref(self.plan), ctypes.byref(struct), n, ctypes.c_void_p(out.data_ptr() + 8 * lo * out.stride(0)),
                       out.stride(0), 1 if accumulate else 0, s)
         return out
@@ -215,6 +223,41 @@ class PerRealisationTermsMixin:
         b.ld_src, b.coef, b.t0_s = src.stride(0), coef.data_ptr(), t0.data_ptr()
         self._term_batches("pta_engine_bwm_params", "pta_engine_bwm_add", b, [("src", src, 8 * src.stride(0))], R, step, out, accumulate)
         self._keep["bwm"] = src   # the launches above read it asynchronously
+        return out
+
+    # ---------------------------------------------------------------- chromatic process ---------
+    def _chrom_theta_device(self, det, R):
+        """validated chromatic keys of theta -> (log10_A, gamma) contiguous float64 device tensors [R, P], a key not given filled with
+        the configured values, pulsars configured without the process NaN amplitudes (they keep none); (None, None) without keys"""
+        if not _chrom.has_keys(det):
+            return None, None
+        conf = _chrom.configured(self._chrom)
+        lA, g = (dv.as_f64(det[k]) if k in det else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, self.P))))
+                 for k, c in zip(_chrom.KEYS, conf))
+        none = np.flatnonzero(np.isnan(conf[0]))
+        if len(none) and _chrom.A_KEY in det:
+            lA = lA.clone()
+            lA[:, dv.i64(none)] = float("nan")
+        return lA, g
+
+    def _chrom_apply(self, det, R, r0, out, accumulate=True):
+        """out[R, n_toa] (+)= the chromatic term of realisations r0 .. r0+R-1 (row r = realisation r0 + r), with theta's chrom_* keys
+        of `det` where it has them: pta_engine_chrom_coef (coef [n, P, K_c], drawn from stream (10, pulsar)) -> pta_engine_chrom_add, in
+        batches of max_batch().  The coefficient table stays outside the workspace budget."""
+        if not self._prepared:
+            self.prepare()
+        t = self._chrom_t
+        P, Kc = self.P, t["K"]
+        lA, g = self._chrom_theta_device(det, R)
+        step = min(R, self.max_batch())
+        c = _lib.ChromEngine()
+        c.n_psr, c.k, c.rng_fast = P, Kc, int(self.rng_fast)
+        c.Ft, c.ldf, c.amp, c.f, c.tspan = t["Ft"].data_ptr(), t["Ft"].stride(0), t["amp"].data_ptr(), t["f"].data_ptr(), t["tspan"].data_ptr()
+        c.ld_theta = P
+        c.coef = self._scratch("chrom_coef", (step, P, Kc)).data_ptr()
+        rows = [("log10_A", lA, 8 * P), ("gamma", g, 8 * P)]
+        self._term_batches("pta_engine_chrom_coef", "pta_engine_chrom_add", c, rows, R, step, out, accumulate, draw=(self.seed, r0))
+        self._keep["chrom"] = (lA, g)   # the launches above read them asynchronously
         return out
 
     # ---------------------------------------------------------------- white noise ---------------
@@ -327,8 +370,8 @@ class PerRealisationTermsMixin:
 
     def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        wn_prior = getattr(self, "_wn_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None:
+        wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None:
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
@@ -349,6 +392,13 @@ class PerRealisationTermsMixin:
                 raise ValueError(f"sample_theta: the {k} boxes are for {len(box[0])} groups but the engine now has {n_groups}: "
                                  "call set_hyper_prior again")
             theta[k] = self._uniform_table("pta_hyper_uniform_field", k, wn_prior, lambda: box, R, r0, mid=(len(box[0]), _wn_hyper.FIELD[k]))
+        if chrom_prior is not None and self._chrom is None:
+            raise ValueError("sample_theta: chromatic boxes given but no chromatic process is configured (set_chromatic_noise)")
+        for k, box in (chrom_prior or {}).items():   # streams (7, 6 .. 7): pair = pulsar, whatever else is sampled
+            theta[k] = self._uniform_table("pta_hyper_uniform_field", k, chrom_prior, lambda: box, R, r0, mid=(self.P, _chrom.FIELD[k]))
+            none = np.flatnonzero(np.isnan(_chrom.configured(self._chrom)[0]))
+            if len(none):   # pulsars configured without the process keep none: their labels are NaN
+                theta[k][:, dv.i64(none)] = float("nan")
         if prior is None:
             return theta
         box = _hyper.spec_bounds(prior)

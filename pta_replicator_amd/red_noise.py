@@ -91,7 +91,15 @@ def add_red_noise(psr, log10_amplitude, spectral_index, components=30, seed=None
     ``psr`` may be a LIST of pulsars with per-pulsar ``log10_amplitude`` / ``spectral_index`` / ``seed`` lists (an amplitude of
     None skips that pulsar): the loop of single calls with one upload, one download and no synchronisation in between."""
     if isinstance(psr, (list, tuple)):
-        return _add_red_noise_list(list(psr), log10_amplitude, spectral_index, components, seed, modes, libstempo_convention)
+        for p_, lA, g, dt in _red_noise_delays_list(list(psr), log10_amplitude, spectral_index, components, seed, modes, libstempo_convention):
+            _record_red_noise(p_, lA, g, dt * u.s)
+        return
+    _record_red_noise(psr, log10_amplitude, spectral_index,
+                      _red_noise_delay(psr, log10_amplitude, spectral_index, components, seed, modes, libstempo_convention) * u.s)
+
+
+def _red_noise_delay(psr, log10_amplitude, spectral_index, components, seed, modes, libstempo_convention):
+    """the delay [s] add_red_noise gives one pulsar (NumPy array): the legacy draws in the reference's order, pta_rn_basis -> pta_rn_synth"""
     if seed is not None:
         np.random.seed(seed)
     if modes is not None:
@@ -106,10 +114,12 @@ def add_red_noise(psr, log10_amplitude, spectral_index, components=30, seed=None
     _lib.call("pta_rn_basis", dv.ptr(t_d), n, ctypes.c_double(t_ref), dv.ptr(f_d), None, nm, 1 if libstempo_convention else 0, dv.ptr(Ft), n, s)
     out = dv.empty((1, n))
     _lib.call("pta_rn_synth", dv.ptr(Ft), n, n, K, dv.ptr(y_d), K, 1, dv.ptr(out), n, 0, s)
-    _record_red_noise(psr, log10_amplitude, spectral_index, dv.download(out[0]) * u.s)
+    return dv.download(out[0])
 
 
-def _add_red_noise_list(psrs, log10_amplitude, spectral_index, components, seed, modes, libstempo_convention):
+def _red_noise_delays_list(psrs, log10_amplitude, spectral_index, components, seed, modes, libstempo_convention):
+    """[(pulsar, log10_A, gamma, delay [s])] of the pulsars of a list call that have a process: the loop of single calls with one
+    upload, one download and no synchronisation in between"""
     P = len(psrs)
     lA = list(log10_amplitude) if isinstance(log10_amplitude, (list, tuple, np.ndarray)) else [log10_amplitude] * P
     gm = list(spectral_index) if isinstance(spectral_index, (list, tuple, np.ndarray)) else [spectral_index] * P
@@ -143,10 +153,35 @@ def _add_red_noise_list(psrs, log10_amplitude, spectral_index, components, seed,
         tp = ctypes.c_void_p(t_all.data_ptr() + 8 * int(off[k]))
         _lib.call("pta_rn_basis", tp, n, ctypes.c_double(t_ref), dv.ptr(f_d), None, nm, 1 if libstempo_convention else 0, dv.ptr(Ft), n, s)
         _lib.call("pta_rn_synth", dv.ptr(Ft), n, n, K, dv.ptr(y_d), K, 1, ctypes.c_void_p(out.data_ptr() + 8 * int(off[k])), n, 0, s)
-    if live:
-        res = dv.download(out[0])
-        for k, a in enumerate(live):
-            _record_red_noise(psrs[a], lA[a], gm[a], res[off[k]:off[k + 1]] * u.s)
+    if not live:
+        return []
+    res = dv.download(out[0])
+    return [(psrs[a], lA[a], gm[a], res[off[k]:off[k + 1]]) for k, a in enumerate(live)]
+
+
+def add_chromatic_noise(psr, log10_amplitude, spectral_index, components=30, index=2.0, ref_freq_mhz=1400.0, seed=None, modes=None,
+                        Tspan=None, libstempo_convention=False):
+    """Add a chromatic power-law Gaussian process, dt_i = (ref_freq_mhz / nu_i)^index sum_k F_ik y_k: add_red_noise argument for
+    argument - the same legacy NumPy draws in the same order through the same pta_rn_basis / pta_rn_synth path - with the row weights
+    w_i = (nu_ref / nu_i)^index applied to the result (index 2 = DM variations).  The radio frequencies come from psr.toas.freqs_mhz,
+    else psr.toas.get_freqs(); a non-finite or non-positive one is refused by name.  Recorded as '{name}_chromatic_noise'.  ``psr`` may
+    be a LIST of pulsars wherever add_red_noise accepts one."""
+    from . import _chrom
+    _chrom.check_scalars(index, ref_freq_mhz, components, "add_chromatic_noise")
+    many = isinstance(psr, (list, tuple))
+    # weights first: a refusal leaves every pulsar and the legacy stream untouched
+    w = {id(p_): _chrom.weights(_chrom.toa_freqs(p_), index, ref_freq_mhz, name=f"pulsar {p_.name}") for p_ in (psr if many else [psr])}
+    if many:
+        done = _red_noise_delays_list(list(psr), log10_amplitude, spectral_index, components, seed, modes, libstempo_convention)
+    else:
+        done = [(psr, log10_amplitude, spectral_index,
+                 _red_noise_delay(psr, log10_amplitude, spectral_index, components, seed, modes, libstempo_convention))]
+    for p_, lA, g, dt in done:
+        dt = (w[id(p_)] * dt) * u.s
+        p_.update_added_signals("{}_chromatic_noise".format(p_.name),
+                                {"amplitude": lA, "spectral_index": g, "index": index, "ref_freq_mhz": ref_freq_mhz}, dt)
+        p_.toas.adjust_TOAs(TimeDelta(dt.to("day")))
+        p_.update_residuals()
 
 
 # ------------------------------------------------------------------------------------------------
