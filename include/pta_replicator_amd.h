@@ -912,6 +912,35 @@ int pta_lnl_apply(const double *Lt, const double *logdet, const double *b, int P
 /* pta_lnl_reduce: lnl[g * ld_lnl + r] = sum_a lnl_pulsar[g * ld_g + a * ld_a + r], pulsars in ascending order.                          */
 int pta_lnl_reduce(const double *lnl_pulsar, int64_t ld_g, int64_t ld_a, int P, int G, int R, double *lnl, int64_t ld_lnl, void *stream);
 
+/* ---- likelihood ratio of a correlated common process on a (log10_A, gamma) grid (ABI 8, additive) ----
+ * ln L(r | common process with ORF Gamma and spectrum g) - ln L(r | noise only) under the configured intrinsic noise (white noise,
+ * ECORR, red noise, chromatic columns; timing model marginalised): with Gamma = B B^T, B [P, rho], Y = W r the projections of
+ * pta_os_project on the C = 2 n_f columns of the array-wide Fourier basis scaled by the unit spectrum at gamma_ref, and
+ * T [n, n], n = rho C, T[(i, k), (j, l)] = sum_a B[a, i] B[a, j] Z_a[k, l] (host: optimal_statistic.clnl_plan),
+ *     M_g = I + D_g T D_g = L_g L_g^T,  D_g = I_rho (x) diag(d_g),  d_g,k = 10^log10_A[g] (f_k yr)^((gamma_ref - gamma[g]) / 2),  f_k = (k / 2 + 1) / Tspan
+ *     lnl_ratio[g, r] = 1/2 || L_g^-1 D_g Y'_r ||^2 - sum_i ln L_g,ii,   Y'_r[i C + k] = sum_a B[a, i] Y[r, a, k].
+ * M_g has eigenvalues >= 1 for every finite grid point.  One ORF per call; the factorisation between pta_clnl_assemble and
+ * pta_clnl_solve is pta_potrf_batched_ex (lda = n, strideA = n n, B = G).  1 <= C <= 64, n <= 65535, G <= 65535 per call, NULL
+ * operands and short leading dimensions: PTA_E_ARG before any device call.  Every value (g, r) is bit-identical whatever R, G, the
+ * leading dimensions and the chunks it is computed in; no atomics.
+ *
+ * pta_clnl_mix: Yp[r * ld_yp + i * C + k] = sum_a Bt[i * P + a] Y[r * ld_y + a * C + k], Bt = B^T [rho, P], pulsars in ascending order,
+ * one workgroup per realisation with its Y in LDS (P C <= 8192).                                                                      */
+int pta_clnl_mix(const double *Y, int64_t ld_y, int P, int C, int R, const double *Bt, int rho, double *Yp, int64_t ld_yp, void *stream);
+/* pta_clnl_assemble: M[g] [n, n] row-major for g < G: the diagonal and the lower triangle of M_g from T [n, n] (row-major, symmetric; the
+ * lower triangle is read), zeros above the diagonal; log10_A, gamma [G].                                                              */
+int pta_clnl_assemble(const double *T, int rho, int C, double gamma_ref, double Tspan, const double *log10_A, const double *gamma, int G,
+                      double *M, void *stream);
+/* pta_clnl_rhs: V[(g * n + i) * ld_v + r] = d_g,(i mod C) Yp[r * ld_yp + i] for g < G, i < n, r < R (ld_v >= R).                         */
+int pta_clnl_rhs(const double *Yp, int64_t ld_yp, int rho, int C, int R, double gamma_ref, double Tspan, const double *log10_A,
+                 const double *gamma, int G, double *V, int64_t ld_v, void *stream);
+/* pta_clnl_solve: V[g] <- L_g^-1 V[g] in place and quad[g * ld_quad + r] = sum_i V[g][i, r]^2 (rows ascending), L [G, n, n] the factors
+ * (the lower triangle is read).  Blocked forward substitution over blocks of 64 rows: the blocks left of the diagonal by pta_dgemm
+ * (fp64 matrix cores, batch = grid points), the diagonal block from LDS with one column per thread.                                   */
+int pta_clnl_solve(const double *L, int n, int G, double *V, int64_t ld_v, int R, double *quad, int64_t ld_quad, void *stream);
+/* pta_clnl_finish: lnl_ratio[g * ld_g + r] = quad[g * ld_quad + r] / 2 - sum_i ln L[g][i, i], the logarithms summed in a fixed order.    */
+int pta_clnl_finish(const double *L, int n, int G, const double *quad, int64_t ld_quad, int R, double *lnl_ratio, int64_t ld_g, void *stream);
+
 /* ---- continuous-wave F-statistics per realisation (ABI 8, additive) ----
  * Fixed-noise Fp (incoherent, per GW frequency) and earth-term Fe (coherent, per GW frequency and sky point).  Host NumPy
  * (pta_replicator_amd/f_statistic.py) builds per pulsar W_a [2 J, N_a] (rows 2 j, 2 j + 1 = [sin, cos](2 pi f_j t)^T P_a^-1), the

@@ -200,6 +200,11 @@ _SIGNATURES = {
     "pta_lnl_factor": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_lnl_apply": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, c_int64, _P]),
     "pta_lnl_reduce": (c_int, [_P, c_int64, c_int64, c_int, c_int, c_int, _P, c_int64, _P]),
+    "pta_clnl_mix": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, c_int, _P, c_int64, _P]),
+    "pta_clnl_assemble": (c_int, [_P, c_int, c_int, c_double, c_double, _P, _P, c_int, _P, _P]),
+    "pta_clnl_rhs": (c_int, [_P, c_int64, c_int, c_int, c_int, c_double, c_double, _P, _P, c_int, _P, c_int64, _P]),
+    "pta_clnl_solve": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, _P, c_int64, _P]),
+    "pta_clnl_finish": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, _P, c_int64, _P]),
     "pta_fstat_project": (c_int, [_P, c_int64, c_int, _P, c_int, _P, c_int64, c_int, _P, c_int64, _P]),
     "pta_fstat_fp": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     "pta_fstat_fe_tiles": (c_int64, [c_int]),
@@ -227,6 +232,9 @@ OS_NORF = 8          # PTA_OS_NORF: ORFs (weight rows) of one pta_os_pairs call
 OSM_KMAX = 128       # PTA_OSM_KMAX
 LNL_KMAX = 128       # PTA_LNL_KMAX
 LNL_MMAX = 16        # PTA_LNL_MMAX
+CLNL_CMAX = 64       # PTA_CLNL_CMAX (csrc/pta_clnl.h)
+CLNL_NORF = 4        # ORFs of one prepare_correlated_likelihood
+CLNL_YMAX = 8192     # P * C doubles of one realisation's projections in the LDS of pta_clnl_mix
 FSTAT_CMAX = 4096    # PTA_FSTAT_CMAX
 FSTAT_PMAX = 128     # PTA_FSTAT_PMAX
 TD_STRIP = 256      # PTA_TD_STRIP

@@ -32,6 +32,7 @@ from . import white_noise as wn
 from ._position import ra_dec
 from .constants import DAY_IN_SEC, YEAR_IN_SEC
 from .engine_bwm import BwmStatisticMixin
+from .engine_clnl import CorrelatedLikelihoodMixin
 from .engine_fstat import FStatisticMixin
 from .engine_lnl import LikelihoodMixin
 from .engine_os import OptimalStatisticMixin
@@ -53,7 +54,8 @@ def stream_id(kind, pulsar):
     return ((kind << 24) | (pulsar & 0xFFFFFF)) & 0xFFFFFFFF
 
 
-class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, FStatisticMixin, BwmStatisticMixin):
+class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticMixin, LikelihoodMixin, CorrelatedLikelihoodMixin, FStatisticMixin,
+                    BwmStatisticMixin):
     def __init__(self, psrs, seed=0):
         # pulsars with the reference's SimulatedPulsar surface are used as they are; enterprise-style ones (toas [s] / toaerrs [s] /
         # flags / pos as plain arrays: what simulate.py:91-95 hands on) are wrapped once through simulate.from_enterprise

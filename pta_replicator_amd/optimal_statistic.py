@@ -767,3 +767,149 @@ def theta_grid(P=None, **axes):
             flat = np.ascontiguousarray(np.repeat(flat[:, None], int(P), axis=1))
         grid[k] = flat
     return grid, tuple(len(v) for v in vals)
+
+
+# ---------------------------------------------------------------- likelihood ratio of a correlated common process -------------
+# The intrinsic noise C_a stays the configured one (white noise, ECORR, red noise, chromatic columns; no GWB auto-term: prepare with
+# gw_amp2 = 0), the timing model is marginalised, and only the common process varies: coefficient covariance Gamma (x) diag(phi_g) on
+# the array-wide Fourier basis, phi_g,k = A_g^2 unit_spectrum(gamma_g)_k, Gamma the [P, P] ORF.  With Gamma = B B^T (B [P, rho]), the
+# plan's W_a = S^1/2 F_a^T P~_a and Z_a = W_a F_a S^1/2 at gamma_ref, Y_a = W_a r_a and d_g,k = sqrt(phi_g,k / S_k),
+#
+#     T   = (B^T (x) I) blockdiag(Z_a) (B (x) I)     [rho C, rho C]   T[(i, k), (j, l)] = sum_a B[a, i] B[a, j] Z_a[k, l]
+#     Y'  = (B^T (x) I) Y                            [rho C]
+#     M_g = I + D_g T D_g = L_g L_g^T,  D_g = I_rho (x) diag(d_g)     eigenvalues >= 1
+#     ln L(r | g, Gamma) - ln L(r | noise only) = 1/2 || L_g^-1 D_g Y' ||^2 - sum_i ln L_g,ii
+#
+# (Woodbury and the determinant lemma on C + F (Gamma (x) phi) F^T.)  T depends on the ORF alone, M_g on (grid point, ORF): one
+# factorisation serves every realisation (pta_clnl_assemble, pta_potrf_batched_ex, pta_clnl_solve).
+CLNL_ORF_NAMES = ("hd", "monopole", "dipole", "curn")
+
+
+def _orf_from_pairs(name, pair_a, pair_b, cos_zeta, P):
+    if name not in CLNL_ORF_NAMES:
+        raise ValueError(f"unknown ORF {name!r}: expected one of {CLNL_ORF_NAMES} or a [P, P] array")
+    cz = np.asarray(cos_zeta, dtype=np.float64)
+    v = {"hd": hd(cz), "monopole": np.ones_like(cz), "dipole": cz, "curn": np.zeros_like(cz)}[name]
+    G = np.eye(P)
+    G[pair_a, pair_b] = v
+    G[pair_b, pair_a] = v
+    return G
+
+
+def _symmetric(m):
+    """symmetric to rounding: |m - m^T| <= 1e-12 max|m|"""
+    return bool(np.all(np.abs(m - m.T) <= 1e-12 * max(float(np.max(np.abs(m))), 1e-300)))
+
+
+def _orf_array(o, P):
+    m = np.asarray(o, dtype=np.float64)
+    if m.shape != (P, P) or not np.all(np.isfinite(m)):
+        raise ValueError(f"a user ORF must be a finite [{P}, {P}] array, got shape {m.shape}")
+    if not _symmetric(m):
+        raise ValueError("a user ORF must be symmetric")
+    return 0.5 * (m + m.T)
+
+
+def orf_matrix(name_or_array, pos):
+    """Gamma [P, P] of unit vectors pos [P, 3]: a name of CLNL_ORF_NAMES ("hd": the Hellings-Downs curve of the pair angles,
+    "monopole": 1, "dipole": cos zeta, "curn": 0 off the diagonal; unit diagonal), or a symmetric finite [P, P] array, used as given."""
+    pos = np.asarray(pos, dtype=np.float64)
+    P = len(pos)
+    if isinstance(name_or_array, str):
+        return _orf_from_pairs(name_or_array, *pair_geometry(pos), P)
+    return _orf_array(name_or_array, P)
+
+
+def orf_factor(Gamma):
+    """B [P, rho] with B B^T = Gamma by numpy.linalg.eigh: the eigenvalues above 1e-12 lambda_max are kept (a singular ORF has
+    rho < P: monopole 1, dipole 3); an eigenvalue below -1e-10 lambda_max (not positive semi-definite) and rank 0 are refused."""
+    Gamma = np.asarray(Gamma, dtype=np.float64)
+    if Gamma.ndim != 2 or Gamma.shape[0] != Gamma.shape[1] or not np.all(np.isfinite(Gamma)):
+        raise ValueError(f"an ORF must be a finite square array, got shape {Gamma.shape}")
+    if not _symmetric(Gamma):
+        raise ValueError("an ORF must be symmetric")
+    w, V = np.linalg.eigh(0.5 * (Gamma + Gamma.T))
+    wmax = float(w[-1])
+    if not wmax > 0:
+        raise ValueError("an ORF of rank 0 (no positive eigenvalue) describes no common process")
+    if w[0] < -1e-10 * wmax:
+        raise ValueError(f"the ORF is not positive semi-definite: eigenvalue {w[0]:.3g} (largest {wmax:.3g})")
+    keep = w > 1e-12 * wmax
+    return V[:, keep] * np.sqrt(w[keep])[None, :]
+
+
+class ClnlPlan:
+    """operands of the correlated likelihood ratio: the OSPlan (prepared with gw_amp2 = 0) and per ORF its name, Gamma, B [P, rho]
+    and T [rho C, rho C]"""
+
+    def __init__(self, os_plan, names, Gammas, Bs, Ts, gamma_ref):
+        self.os, self.names, self.Gamma, self.B, self.T_orf = os_plan, names, Gammas, Bs, Ts
+        self.P, self.C, self.nf, self.T = os_plan.P, os_plan.C, os_plan.C // 2, float(os_plan.T)
+        self.gamma_ref = float(gamma_ref)
+        self.rho = [b.shape[1] for b in Bs]
+        self.n = [r * self.C for r in self.rho]
+
+
+def clnl_plan(os_plan, orfs, gamma_ref=13. / 3.):
+    """ClnlPlan of an OSPlan built with gw_amp2 = 0 at gamma_ref, and 1 .. 4 ORFs (names of CLNL_ORF_NAMES or [P, P] arrays)."""
+    orfs = (orfs,) if isinstance(orfs, str) else tuple(orfs)
+    if not 1 <= len(orfs) <= 4:
+        raise ValueError(f"{len(orfs)} ORFs: one plan holds 1 .. 4")
+    P, C = os_plan.P, os_plan.C
+    names, Gs, Bs, Ts = [], [], [], []
+    for k, o in enumerate(orfs):
+        if isinstance(o, str):
+            G = _orf_from_pairs(o, os_plan.pair_a, os_plan.pair_b, os_plan.cos_zeta, P)
+            names.append(o)
+        else:
+            G = _orf_array(o, P)
+            names.append(f"orf{k}")
+        B = orf_factor(G)
+        T = np.einsum("ai,aj,akl->ikjl", B, B, os_plan.Z).reshape(B.shape[1] * C, B.shape[1] * C)
+        Gs.append(G)
+        Bs.append(B)
+        Ts.append(0.5 * (T + T.T))
+    return ClnlPlan(os_plan, names, Gs, Bs, Ts, gamma_ref)
+
+
+def clnl_scale(nf, T, gamma_ref, log10_A, gamma):
+    """d [G, 2 nf]: d_g,k = 10^log10_A_g (f_k yr)^((gamma_ref - gamma_g) / 2), the square root of the grid point's spectrum over the
+    unit spectrum at gamma_ref (pta_clnl_scale of csrc/pta_clnl.h, same operations)"""
+    lA, g = np.atleast_1d(np.asarray(log10_A, dtype=np.float64)), np.atleast_1d(np.asarray(gamma, dtype=np.float64))
+    f = np.repeat(np.arange(1, int(nf) + 1) / float(T), 2)
+    return 10.0 ** lA[:, None] * (f[None, :] * YEAR_IN_SEC) ** ((float(gamma_ref) - g[:, None]) / 2.0)
+
+
+def clnl_ratio(T, Yp, D, form="cholesky"):
+    """(lnl_ratio [R, G], scale [R, G]) of one ORF: T [n, n], Yp [R, n] the mixed projections, D [G, n] the diagonals of D_g.
+    M_g = I + D_g T D_g, v = D_g Y'; form "cholesky" is the device's route (factor M_g, substitution, sum of squares, sum of ln L_ii);
+    "solve" goes through np.linalg.solve and slogdet without a factor, for error bars.  scale = v^T v / 2 + | ln det M_g |: the size
+    of the two terms the ratio is the difference of."""
+    T, Yp, D = np.asarray(T, dtype=np.float64), np.atleast_2d(np.asarray(Yp, dtype=np.float64)), np.atleast_2d(np.asarray(D, dtype=np.float64))
+    M = np.eye(T.shape[0])[None] + D[:, :, None] * T[None] * D[:, None, :]
+    v = D[:, :, None] * Yp.T[None]                                                      # [G, n, R]
+    if form == "cholesky":
+        L = np.linalg.cholesky(M)
+        half_logdet = np.sum(np.log(np.diagonal(L, axis1=-2, axis2=-1)), axis=-1)
+        quad = np.sum(np.linalg.solve(L, v) ** 2, axis=1)
+    elif form == "solve":
+        half_logdet = 0.5 * np.linalg.slogdet(M)[1]
+        quad = np.sum(v * np.linalg.solve(M, v), axis=1)
+    else:
+        raise ValueError(f"form={form!r}: 'cholesky' or 'solve'")
+    return (0.5 * quad - half_logdet[:, None]).T, (0.5 * np.sum(v * v, axis=1) + 2.0 * np.abs(half_logdet)[:, None]).T
+
+
+def clnl_from_rows(plan, rows, log10_A, gamma, form="cholesky", with_scale=False):
+    """lnl_ratio [R, n_orf, G] of rows [R, sum N_a] at the grid points (log10_A [G], gamma [G]), in NumPy, in one of the two forms of
+    clnl_ratio; with_scale: (lnl_ratio, scale), scale [R, n_orf, G] the size of the terms it is the difference of."""
+    rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+    Y = project(plan.os, rows)
+    R, C = rows.shape[0], plan.C
+    d = clnl_scale(plan.nf, plan.T, plan.gamma_ref, log10_A, gamma)
+    out, scale = np.zeros((R, len(plan.names), d.shape[0])), np.zeros((R, len(plan.names), d.shape[0]))
+    for o, (B, T) in enumerate(zip(plan.B, plan.T_orf)):
+        rho = B.shape[1]
+        Yp = np.einsum("ai,rac->ric", B, Y).reshape(R, rho * C)
+        out[:, o, :], scale[:, o, :] = clnl_ratio(T, Yp, np.tile(d, (1, rho)), form)
+    return (out, scale) if with_scale else out
