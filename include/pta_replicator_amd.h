@@ -986,6 +986,44 @@ int pta_bwm_stat(const double *Q, int64_t ld_q, int P, int C, int J, int R, cons
                  int64_t ld_fb, double *amp, int64_t ld_amp, double *fb_max, int64_t ld_max, int32_t *fb_arg, int64_t ld_arg, double *part_val,
                  int32_t *part_arg, void *stream);
 
+/* ---- a binned binary population per realisation: Poisson counts, loudest-k, residual spectrum (ABI 8, additive) ----
+ * The model, the sampler and the validation: pta_replicator_amd/_pop.py, csrc/pta_pop.h.  B cells, of which n_sorted lie inside the F
+ * frequency bins; the sorted tables list those bin by bin (cell_ptr), inside a bin by (regime of the rate, rate).                  */
+#define PTA_POP_KMAX 128 /* loudest cells kept per (realisation, bin)          */
+#define PTA_POP_FMAX 64  /* frequency bins                                      */
+#define PTA_POP_CHUNK 1024 /* cells a workgroup of pta_pop_draw_select takes per step (256 threads x 4) */
+typedef struct {
+  int32_t n_cells;         /* B: original cells = the length of a counts row and of the label tables                  */
+  int32_t n_sorted;        /* cells inside the bin edges                                                              */
+  int32_t n_bins;          /* F <= PTA_POP_FMAX                                                                       */
+  int32_t k;               /* outlier_per_bin, 1 .. PTA_POP_KMAX                                                      */
+  double t_obs;            /* [s]                                                                                     */
+  const int32_t *cell_ptr; /* [F + 1] bin k owns sorted cells cell_ptr[k] .. cell_ptr[k + 1] - 1                      */
+  const double *number;    /* [n_sorted] expected count of the cell                                                   */
+  const double *hs2;       /* [n_sorted] squared source strain                                                        */
+  const double *fo;        /* [n_sorted] observed frequency [Hz]                                                      */
+  const int32_t *orig;     /* [n_sorted] original cell index                                                          */
+  const double *log10_mc;  /* [B] log10 observer-frame chirp mass [Msun], by original index                           */
+  const double *log10_fo;  /* [B] log10 observed frequency [Hz]                                                       */
+  const double *log10_dl;  /* [B] log10 luminosity distance [Mpc]                                                     */
+} pta_pop_plan;
+/* pta_pop_draw_select: one workgroup per (realisation r0 + r, bin).  N of every cell of the bin is drawn (pta_pop_poisson: stream (11,
+ * attempt), pair = original cell index) or, with counts != NULL, read from counts[r * ld_counts + original index]; w = ((N hs2) fo)
+ * t_obs; the k cells with the largest w > 0 are kept (ties: the lower original index first) and the rest summed.  Outputs:
+ * sel_cell, sel_number, sel_w [R, F, k] (entries below sel_count[r, bin] are written, loudest first), sel_count [R, F], free_spec
+ * [R, F] = 1e-100 + the sum of the rest; counts_out != NULL also receives N at [r * ld_counts_out + original index] (cells outside the
+ * edges are not touched).  No global atomics and no split over workgroups: a (realisation, bin) result does not depend on R, r0 or
+ * the other rows of the launch.  Allocates nothing, synchronises nothing.                                                        */
+int pta_pop_draw_select(const pta_pop_plan *plan, uint64_t seed, uint64_t r0, int R, const double *counts, int64_t ld_counts,
+                        double *counts_out, int64_t ld_counts_out, int32_t *sel_cell, double *sel_number, double *sel_w, int32_t *sel_count,
+                        double *free_spec, void *stream);
+/* pta_pop_theta: one workgroup per realisation: the selection concatenated bin-major into rows of S = F k entries, log10_mc, log10_fgw,
+ * log10_dist, pop_number [R, S] (NaN past the count) and pop_cell [R, S] (-1 past it) gathered from the label tables, cw_count [R], and
+ * gwb_log10_hc[r * ld_hc + bin] = 0.5 log10(free_spec).                                                                          */
+int pta_pop_theta(const pta_pop_plan *plan, int R, const int32_t *sel_cell, const double *sel_number, const int32_t *sel_count,
+                  const double *free_spec, double *log10_mc, double *log10_fgw, double *log10_dist, double *pop_number, int32_t *pop_cell,
+                  int32_t *cw_count, double *gwb_log10_hc, int64_t ld_hc, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU -------- */
 /* The path's one collective (BASELINE.json north_star: "RCCL over xGMI only to all-gather the final residual arrays
  * back to rank 0"): realisations are sharded by contiguous row ranges - rank r owns rows [a_r, b_r) of the [total_rows x n_cols]

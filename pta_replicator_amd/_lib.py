@@ -113,6 +113,14 @@ class ChromEngine(ctypes.Structure):
     ]
 
 
+class PopPlan(ctypes.Structure):
+    """pta_pop_plan (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_cells", c_int32), ("n_sorted", c_int32), ("n_bins", c_int32), ("k", c_int32), ("t_obs", c_double),
+        ("cell_ptr", _P), ("number", _P), ("hs2", _P), ("fo", _P), ("orig", _P), ("log10_mc", _P), ("log10_fo", _P), ("log10_dl", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -216,6 +224,8 @@ _SIGNATURES = {
     "pta_microbench": (c_int, [c_int, c_int64, c_int, c_int, POINTER(c_double)]),
     "pta_clock_probe": (c_int, [_P, c_int, c_int, c_int, _P]),
     "pta_selftest_mfma_f64": (c_int, [POINTER(c_double)]),
+    "pta_pop_draw_select": (c_int, [POINTER(PopPlan), c_uint64, c_uint64, c_int, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    "pta_pop_theta": (c_int, [POINTER(PopPlan), c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_gwb_spectrum_scale_user": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P]),
     "pta_hyper_uniform_field": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_os_matched_prior_spec": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, c_int, _P, c_int64, _P, _P, _P]),
@@ -235,6 +245,9 @@ LNL_MMAX = 16        # PTA_LNL_MMAX
 CLNL_CMAX = 64       # PTA_CLNL_CMAX (csrc/pta_clnl.h)
 CLNL_NORF = 4        # ORFs of one prepare_correlated_likelihood
 CLNL_YMAX = 8192     # P * C doubles of one realisation's projections in the LDS of pta_clnl_mix
+POP_KMAX = 128       # PTA_POP_KMAX: loudest cells kept per (realisation, frequency bin)
+POP_FMAX = 64        # PTA_POP_FMAX
+POP_CHUNK = 1024     # PTA_POP_CHUNK
 FSTAT_CMAX = 4096    # PTA_FSTAT_CMAX
 FSTAT_PMAX = 128     # PTA_FSTAT_PMAX
 TD_STRIP = 256      # PTA_TD_STRIP

@@ -46,6 +46,26 @@ def gw_strain_source(mchirp, dcom, freq_rest_orb):
     return const * mchirp * np.power(2.0 * mchirp * freq_rest_orb, 2.0 / 3.0) / dcom
 
 
+def f_centers(fobs):
+    """centres of the frequency bins with edges fobs [F + 1], as the reference forms them (deterministic.py:620)."""
+    fobs = np.asarray(fobs, dtype=np.float64)
+    return np.array([(fobs[i + 1] + fobs[i]) / 2 for i in range(fobs.size - 1)])
+
+
+def cell_quantities(vals, population=None):
+    """(mc [g, observer frame], dl [cm], hs, fo [Hz]) of every cell of vals [4, B] (Mtot, q, z, f_obs), in the reference's operation
+    order (deterministic.py:623-633)."""
+    population = population or Population
+    vals = np.asarray(vals, dtype=np.float64)
+    mc = population.chirp_mass(*population.component_masses(vals[0], vals[1]))   # rest frame
+    rz = vals[2, :]
+    frst = vals[3] * (1.0 + rz)
+    dc = population.comoving_distance_cm(rz)
+    dl = np.copy(dc) * (1.0 + rz)
+    hs = population.gw_strain_source(mc, dc, frst / 2)
+    return mc * (1.0 + rz), dl, hs, vals[-1]
+
+
 class Population:
     """bundle handed to add_gwb_plus_outlier_cws; replace any member with holodeck's function to use holodeck's own numbers"""
     component_masses = staticmethod(component_masses)

@@ -200,20 +200,11 @@ def split_population(vals, weights, fobs, T_obs, outlier_per_bin=100, population
     of each frequency bin set aside (padded slots stay zero), the remainder summed into the free spectrum.
     Returns (f_centers, free_spec, outlier_hs, outlier_fo, outlier_mc [Msun, observer frame], outlier_dl [Mpc])."""
     from . import _population as pop
-    population = population or pop.Population
-    vals = np.asarray(vals, dtype=np.float64)
     weights = np.asarray(weights, dtype=np.float64)
     fobs = np.asarray(fobs, dtype=np.float64)
 
-    f_centers = np.array([(fobs[i + 1] + fobs[i]) / 2 for i in range(fobs.size - 1)])
-    mc = population.chirp_mass(*population.component_masses(vals[0], vals[1]))   # rest frame
-    rz = vals[2, :]
-    frst = vals[3] * (1.0 + rz)
-    dc = population.comoving_distance_cm(rz)
-    dl = np.copy(dc) * (1.0 + rz)
-    hs = population.gw_strain_source(mc, dc, frst / 2)
-    fo = vals[-1]
-    mc = mc * (1.0 + rz)                                                          # observer frame for the injections
+    f_centers = pop.f_centers(fobs)
+    mc, dl, hs, fo = pop.cell_quantities(vals, population)                        # mc: observer frame for the injections
 
     nbin = fobs.shape[0] - 1
     freq_idxs = np.digitize(fo, fobs)

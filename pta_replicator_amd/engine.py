@@ -80,6 +80,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._delays = None
         self._cw = None      # one CW source per realisation (set_cw), parameters from theta / set_cw_prior
         self._bwm = False    # one burst with memory per realisation (set_bwm), parameters from theta / set_bwm_prior
+        self._pop = self._popd = None   # a binary population per realisation (set_population): host tables, their device copies
         self._chrom = None   # one chromatic Gaussian process per pulsar (set_chromatic_noise), added after the fused launch
         self._chrom_t = None   # its device tables, built by prepare()
         # state of the per-realisation terms (engine_terms.py): per term the buffers its queued launches still read, replaced when the
@@ -724,10 +725,12 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         comes back as gwb_clm [R, n_lm] (columns l >= 1 from stream (7, 2), pair = column; column 0 the configured c_00) with
         gwb_orf_info [R] int32: 0, or the 1-based pivot at which the row's ORF stopped being positive definite - such a realisation is
         all NaN and flagged, not raised.  Sampled white noise comes back as wn_efac, wn_log10_equad [R, G_wn] and wn_log10_ecorr
-        [R, G_ec], group j drawn from stream (7, 3), (7, 4), (7, 5), pair j: no other label or residual moves."""
+        [R, G_ec], group j drawn from stream (7, 3), (7, 4), (7, 5), pair j: no other label or residual moves.  With set_population()
+        theta also holds population_theta(R, r0): gwb_log10_hc [R, F], the cw_* keys [R, S] with cw_count [R], and the labels pop_cell,
+        pop_number [R, S] (streams (11, attempt) and (8, s))."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None:
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and getattr(self, "_pop", None) is None:
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if chrom_prior is not None and self._chrom is None:
             raise ValueError("generate_sampled: chromatic boxes given but no chromatic process is configured (set_chromatic_noise)")

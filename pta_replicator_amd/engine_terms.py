@@ -1,5 +1,6 @@
 """The per-realisation terms of the ReplicaEngine: theta split into its parts, the terms added after the fused launch (one CW source
-or a catalogue, a burst with memory, white noise per group) and theta drawn on chip from uniform boxes (set_*_prior, sample_theta).
+or a catalogue, a burst with memory, white noise per group), theta drawn on chip from uniform boxes (set_*_prior, sample_theta) and theta
+made on chip from a binned binary population (set_population, population_theta: Poisson counts, loudest-k, residual spectrum).
 What the terms share is written once: the params -> add batch loop (_term_batches), the reused device tables grown on demand
 (_scratch), the buffers queued launches still read (self._keep, one entry per term) and the box draw (_uniform_table).  The fixed model,
 prepare(), the workspace and the generate* calls stay in engine.py.
@@ -9,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _chrom, _cw, _hyper, _lib, _wn_hyper, device as dv
+from . import _bwm, _chrom, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
 from ._position import ra_dec
 
 
@@ -77,6 +78,53 @@ class PerRealisationTermsMixin:
         self._prior, self._wn_prior = prior, wn_prior   # new dicts: the device copies of the previous boxes are not theirs (_uniform_table)
         return self
 
+    def set_population(self, vals, number=None, fobs=None, T_obs=None, outlier_per_bin=100, population=None):
+        """a binned binary population PER REALISATION (the reference's add_gwb_plus_outlier_cws, deterministic.py:565-715, with the
+        Poisson sampling of the counts in front of it): vals [4, B] (Mtot, q, z, f_obs), number [B] >= 0 the expected count of every
+        cell, fobs [F + 1] the bin edges, T_obs [s].  Realisation rho draws N_b ~ Poisson(number_b) (stream (11, attempt), pair = cell:
+        csrc/pta_pop.h), forms w_b = ((N_b hs2_b) fo_b) T_obs, makes the outlier_per_bin <= 128 loudest cells of every bin (w > 0;
+        ties: the lower cell index) CW sources and sums the rest into the free spectrum: population_theta().  Needs
+        set_gwb(..., userSpec=U) with U[:, 0] = _population.f_centers(fobs) and set_cw(...); refused next to set_cw_prior and a
+        gwb_log10_hc prior, which define the same keys, and in TD mode; F <= 64.  sample_theta / generate_sampled then include it.
+        population: the holodeck-equivalent helpers (_population.Population).  set_population(None) removes it.  No prepare() needed."""
+        if vals is None:
+            self._pop = self._popd = None
+            return self
+        tab = _pop.make_tables(vals, number, fobs, T_obs, outlier_per_bin, population)
+        _pop.check_engine(tab, self._gw, self._cw, getattr(self, "_cw_prior", None), getattr(self, "_prior", None),
+                          getattr(self, "_td_prepared", False))
+        self._pop, self._popd = tab, None   # _popd: the device copies, made by the first population_theta()
+        return self
+
+    def population_theta(self, R, r0=0, counts=None, raw=False):
+        """theta of realisations r0 .. r0+R-1 of the population (set_population), made on chip by pta_pop_draw_select -> pta_pop_theta
+        in batches bounded by workspace_bytes: {gwb_log10_hc [R, F], the cw_* source keys [R, S] with cw_log10_dist, S = F
+        outlier_per_bin, bin-major, NaN past cw_count [R] (int32), pop_cell [R, S] (int32, -1 past the count), pop_number [R, S]}.  The
+        orientation keys are pta_cw_catalog_uniform's, source s from stream (8, s).  counts [R, B]: the cell counts of every row (in
+        the caller's cell order) instead of the Poisson draw - the reference's own `weights`.  raw=True adds the kernels' own
+        outputs: pop_free_spec [R, F], pop_sel_w [R, F, k], pop_sel_count [R, F] and, without counts, pop_counts [R, B] (the drawn N;
+        NaN for cells outside the bin edges) - for tests and measurements, not theta keys.  A row is a function of (seed, r0 + r)
+        alone."""
+        tab = getattr(self, "_pop", None)
+        if tab is None:
+            raise ValueError("population_theta: no population configured (set_population)")
+        _pop.check_engine(tab, self._gw, self._cw, getattr(self, "_cw_prior", None), getattr(self, "_prior", None),
+                          getattr(self, "_td_prepared", False))
+        if counts is not None:
+            counts = _pop.check_counts(counts, R, tab["B"])
+        if self._popd is None:
+            self._popd = population_device_tables(tab)
+        S = tab["F"] * tab["k"]
+        per_real = 20 * S + 12 * tab["F"]   # the selection scratch and the two [F] rows of one realisation, bytes
+        step = int(max(1, min(R, self.workspace_bytes // per_real)))
+        out = population_run(self._popd, self.seed, R, r0, counts=counts, raw=raw, step=step, scratch=self._scratch)
+        prior = self._popd.setdefault("prior", _pop.orientation_prior(self.P, S))
+        catalog = self._uniform_table("pta_cw_catalog_uniform", "pop", prior, lambda: _cw.prior_bounds(prior, self.P), R, r0, mid=(S,),
+                                      shape=(R, S, _cw.N_SRC))
+        theta = _cw.labels(None, prior, self.P, catalog)
+        theta.update(out)
+        return theta
+
     # ---------------------------------------------------------------- theta -> its parts --------
     def _theta_parts(self, theta, R, td=False, check_values=True):
         """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
@@ -88,6 +136,8 @@ class PerRealisationTermsMixin:
             return None, {}
         if _hyper.ORF_INFO_KEY in theta:   # a label of sampled theta, no parameter
             theta = {k: v for k, v in theta.items() if k != _hyper.ORF_INFO_KEY}
+        if isinstance(theta, dict):
+            theta = _pop.strip_labels(theta)                  # and so are the population's pop_cell / pop_number
         rest, wnk = _wn_hyper.split(theta)   # ahead of _hyper.check_theta, whose key list stays the GWB / red-noise one
         rest, chk = _chrom.split(rest)
         rest, cw = _cw.split(rest)
@@ -371,11 +421,14 @@ class PerRealisationTermsMixin:
     def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None:
+        pop = getattr(self, "_pop", None)
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and pop is None:
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
         theta = {}
+        if pop is not None:         # streams (11, attempt), pair = cell, and (8, s) for the orientations: whatever else is sampled
+            theta.update(self.population_theta(R, r0))
         if bwm_prior is not None:   # stream (9, 0): pair j = label column j, whatever else is sampled
             theta.update(_bwm.labels(self._uniform_table("pta_bwm_uniform", "bwm", bwm_prior, lambda: _bwm.prior_bounds(bwm_prior), R, r0, mid=())))
         if cw_prior is not None:    # stream (8, 0): pair j = label column j, whatever else is sampled
@@ -424,3 +477,57 @@ class PerRealisationTermsMixin:
                 if k in theta and len(none):   # pulsars configured without red noise keep none: their labels are NaN
                     theta[k][:, none] = float("nan")
         return theta
+
+
+# ---------------------------------------------------------------- population: device tables and the batch loop -----------------------
+def population_device_tables(tab):
+    """the host tables of _pop.make_tables on the device and the pta_pop_plan that points at them"""
+    d = {k: (dv.i32 if k in ("cell_ptr", "orig") else dv.f64)(tab[k])
+         for k in ("cell_ptr", "number", "hs2", "fo", "orig", "log10_mc", "log10_fo", "log10_dl")}
+    p = _lib.PopPlan()
+    p.n_cells, p.n_sorted, p.n_bins, p.k, p.t_obs = tab["B"], len(tab["orig"]), tab["F"], tab["k"], tab["T_obs"]
+    for k, t in d.items():
+        setattr(p, k, t.data_ptr())
+    d["plan"] = p
+    return d
+
+
+def population_run(d, seed, R, r0=0, counts=None, raw=False, step=None, scratch=None):
+    """pta_pop_draw_select -> pta_pop_theta for realisations r0 .. r0+R-1 in batches of `step` over the device tables d
+    (population_device_tables): {gwb_log10_hc [R, F], cw_log10_mc, cw_log10_fgw, cw_log10_dist, pop_number [R, S], pop_cell [R, S] int32,
+    cw_count [R] int32}; raw=True adds pop_free_spec, pop_sel_w, pop_sel_count and (drawn counts) pop_counts.  counts: [R, B] NumPy
+    array or tensor, or None to draw.  scratch: the engine's _scratch (the selection tables are reused across calls); None allocates."""
+    dev = dv.require_gpu()
+    p = d["plan"]
+    B, F, k = p.n_cells, p.n_bins, p.k
+    S = F * k
+    step = R if step is None else max(1, min(int(step), R))
+    n_sel = step * S
+    words = 2 * n_sel + (n_sel + 1) // 2   # sel_number, sel_w (float64) and sel_cell (int32) of one batch
+    buf = dv.empty((words,)) if scratch is None else scratch("pop_sel", (words,))
+    sel_number, sel_w, sel_cell = buf[:n_sel], buf[n_sel:2 * n_sel], buf[2 * n_sel:].view(torch.int32)
+    f64 = lambda *sh: dv.empty(sh)   # noqa: E731
+    out = {_hyper.SPEC_KEY: f64(R, F), "cw_log10_mc": f64(R, S), "cw_log10_fgw": f64(R, S), "cw_log10_dist": f64(R, S),
+           _cw.COUNT_KEY: dv.empty((R,), dtype=torch.int32), "pop_cell": dv.empty((R, S), dtype=torch.int32), "pop_number": f64(R, S)}
+    free_spec, sel_count = f64(R, F), dv.empty((R, F), dtype=torch.int32)
+    if counts is not None:
+        counts = (counts.to(device=dev, dtype=torch.float64) if hasattr(counts, "data_ptr") else dv.f64(counts)).contiguous()
+    counts_out = torch.full((R, B), float("nan"), dtype=torch.float64, device=dev) if raw and counts is None else None
+    all_w = dv.zeros((R, F, k)) if raw else None
+    s = dv.stream_ptr()
+    for lo in range(0, R, step):
+        n = min(step, R - lo)
+        _lib.call("pta_pop_draw_select", ctypes.byref(p), seed, r0 + lo, n, dv.row_ptr(counts, lo), B, dv.row_ptr(counts_out, lo), B,
+                  dv.ptr(sel_cell), dv.ptr(sel_number), dv.ptr(sel_w), dv.row_ptr(sel_count, lo), dv.row_ptr(free_spec, lo), s)
+        _lib.call("pta_pop_theta", ctypes.byref(p), n, dv.ptr(sel_cell), dv.ptr(sel_number), dv.row_ptr(sel_count, lo), dv.row_ptr(free_spec, lo),
+                  dv.row_ptr(out["cw_log10_mc"], lo), dv.row_ptr(out["cw_log10_fgw"], lo), dv.row_ptr(out["cw_log10_dist"], lo),
+                  dv.row_ptr(out["pop_number"], lo), dv.row_ptr(out["pop_cell"], lo), dv.row_ptr(out[_cw.COUNT_KEY], lo),
+                  dv.row_ptr(out[_hyper.SPEC_KEY], lo), F, s)
+        if raw:   # entries at or past sel_count are whatever the scratch held: masked below
+            all_w[lo:lo + n] = sel_w[:n * S].view(n, F, k)
+    if raw:
+        live = torch.arange(k, device=dev)[None, None, :] < sel_count[:, :, None]
+        out.update(pop_free_spec=free_spec, pop_sel_w=torch.where(live, all_w, torch.zeros_like(all_w)), pop_sel_count=sel_count)
+        if counts_out is not None:
+            out["pop_counts"] = counts_out
+    return out
