@@ -681,6 +681,46 @@ int pta_engine_chrom_coef(const pta_chrom_engine *chrom_host, uint64_t seed, uin
 int pta_engine_chrom_add(const pta_engine_plan *plan_host, const pta_chrom_engine *chrom_host, int R, double *out, int64_t ld_out,
                          int accumulate, void *stream);
 
+/* ---------------------------------------------------------------- common red processes with an ORF each (ABI 8, additive) */
+/* Up to PTA_CPROC_MAX Gaussian processes common to the array (clock error = monopole, ephemeris error = dipole, CURN, HD, any
+ * positive semi-definite [P, P] ORF), all on the array-wide Fourier basis f_k = k / T, sin column then cos column:
+ *   dt_{a,i} += sum_c F_ic y_ac,  y_ac = sum_p sqrt(phi_pc) sum_j B_p[a, j] z_pcj,  B_p B_p^T = Gamma_p,
+ * phi the red-noise prior at tspan = T, z from stream (CPROC = 12, p) of the realisation.  Added after the fused synthesis, like the
+ * terms above.  Device pointers.                                                                                                 */
+#define PTA_CPROC_MAX 4         /* processes per engine */
+#define PTA_CPROC_KMAX 64       /* columns: 2 x 32 frequencies */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_proc;             /* 1 .. PTA_CPROC_MAX */
+  int32_t k;                  /* K = 2 x the most components of any process, even, <= PTA_CPROC_KMAX */
+  int32_t rng_fast;           /* the Gaussian transform of the plan's rng_fast */
+  int32_t kp[PTA_CPROC_MAX];  /* columns of process p, even, 2 .. k: it leaves columns >= kp untouched */
+  int32_t rho[PTA_CPROC_MAX]; /* rank of its ORF factor, 1 .. P */
+  const double *B[PTA_CPROC_MAX]; /* [n_psr x rho] row-major factor of its ORF */
+  const double *amp;          /* [n_proc x k] configured sqrt(phi) */
+  double tspan;               /* T [s]: f_k = k / T, and the Tspan of the prior */
+  const double *log10_A;      /* [R x ld_theta] labels of realisation r0 + r, NaN = as configured; NULL = all as configured */
+  const double *gamma;        /* [R x ld_theta] likewise (needed beside log10_A) */
+  int64_t ld_theta;           /* >= n_proc */
+  const double *sc1;          /* [n_toa x 2] (sin, cos)(2 pi frac(t / T)) of every TOA, 16-byte aligned (read by pta_engine_cproc_add) */
+  double *coef;               /* [R x n_psr x k] y, written by pta_engine_cproc_coef, read by pta_engine_cproc_add; 16-byte aligned */
+} pta_cproc_engine;
+
+/* coef[(r * P + a) * k + c] = sum over the processes p with c < kp[p], ascending, of amp(r, p, c) * sum_j B_p[a * rho + j] z_j (ascending j,
+ * one fma per term), z_j = deviate n = c rho + j of stream (CPROC, p) of realisation r0 + r: pair n >> 1, branch n & 1.  amp = the
+ * configured table, or - log10_A given and not NaN at (r, p) - sqrt(A^2 (f / f_yr)^-gamma / (12 pi^2 T) yr^3) at f = (c / 2 + 1) / T.
+ * One workgroup per (r, c): the deviates are drawn once into LDS, one thread per pulsar mixes them.  No atomics.                  */
+int pta_engine_cproc_coef(const pta_cproc_engine *cproc_host, uint64_t seed, uint64_t r0, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum_k coef[(r * P + a) * k + 2 k'] sin(2 pi (k' + 1) x_i) + coef[.. + 2 k' + 1] cos(2 pi (k' + 1) x_i) for r < R, a
+ * the pulsar of TOA i, x_i = frac(t_i / T) (accumulate = 1 adds, 0 writes), over the plan's TOA tiles (tile_psr / tile_start /
+ * tile_count, n_tiles, n_psr, n_toa; nothing else of the plan is read).  No design matrix: harmonic k' + 1 comes from harmonic k' by a
+ * rotation through sc1 in registers, in one fixed order: a realisation's term is bit-identical in every batch, row slot and view.
+ * Two adjacent TOAs per lane and 16-byte accesses wherever the row's address allows; out and ld_out need 8-byte alignment only.
+ * Nothing outside the tiles' columns is touched.  No atomics.                                                                    */
+int pta_engine_cproc_add(const pta_engine_plan *plan_host, const pta_cproc_engine *cproc_host, int R, double *out, int64_t ld_out,
+                         int accumulate, void *stream);
+
 /* ---------------------------------------------------------------- TD mode ---------- */
 /* Dense time-domain path named by BASELINE.json's north_star (no counterpart in the reference,
  * which never forms an N_toa x N_toa object: SURVEY.md §0.2, App. A.1).

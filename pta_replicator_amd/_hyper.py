@@ -174,9 +174,10 @@ def check_theta_os(theta, R, P, rn, gwb_auto, check_values=True, gw=None):
     source is not part of the noise model, and so is gwb_clm: the auto-term stays the isotropic one).  gw: the engine's GWB configuration; given, the spectrum key gwb_log10_hc is accepted too
     (its nodes are the configured userSpec's; left out, as by the likelihood grid, the key is unknown).  Returns {key: array} of the
     GWB / red-noise keys."""
-    from . import _chrom, _cw, _wn_hyper
+    from . import _chrom, _cproc, _cw, _wn_hyper
     _wn_hyper.refuse_noise_model(theta)   # the matched statistics hold white noise fixed: said so, instead of "unknown keys"
     _chrom.refuse_noise_model(theta)      # and carry no chromatic term
+    _cproc.refuse_noise_model(theta)
     theta, _ = _cw.split(theta)
     if gw is not None:
         theta = {k: v for k, v in theta.items() if k not in (CLM_KEY, ORF_INFO_KEY)}

@@ -121,6 +121,14 @@ class PopPlan(ctypes.Structure):
     ]
 
 
+class CprocEngine(ctypes.Structure):
+    """pta_cproc_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_proc", c_int32), ("k", c_int32), ("rng_fast", c_int32), ("kp", c_int32 * 4), ("rho", c_int32 * 4), ("B", _P * 4),
+        ("amp", _P), ("tspan", c_double), ("log10_A", _P), ("gamma", _P), ("ld_theta", c_int64), ("sc1", _P), ("coef", _P),
+    ]
+
+
 _SIGNATURES = {
     "pta_abi_version": (c_int, []),
     "pta_last_error": (c_char_p, []),
@@ -189,6 +197,8 @@ _SIGNATURES = {
     "pta_engine_wn_add": (c_int, [POINTER(EnginePlan), POINTER(WnHyper), c_uint64, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "pta_engine_chrom_coef": (c_int, [POINTER(ChromEngine), c_uint64, c_uint64, c_int, _P]),
     "pta_engine_chrom_add": (c_int, [POINTER(EnginePlan), POINTER(ChromEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_engine_cproc_coef": (c_int, [POINTER(CprocEngine), c_uint64, c_uint64, c_int, _P]),
+    "pta_engine_cproc_add": (c_int, [POINTER(EnginePlan), POINTER(CprocEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_synth": (c_int, [POINTER(EnginePlan), c_uint64, c_uint64, c_int, _P, c_int64, _P]),
     "pta_td_cov_assemble": (c_int, [_P, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P]),
     "pta_td_cov_assemble_all": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
@@ -237,6 +247,9 @@ CW_ENGINE_NPAR = 16  # PTA_CW_ENGINE_NPAR
 CW_CATALOG_NPAR = (16, 8, 8)  # by mode: PTA_CW_CATALOG_NPAR_EVOLVE, PTA_CW_CATALOG_NPAR_FOLDED (phase_approx, monochromatic)
 WN_HYPER_GMAX = 16   # PTA_WN_HYPER_GMAX
 CHROM_RG = 16        # PTA_CHROM_RG (csrc/pta_chrom.h): realisations per workgroup of pta_engine_chrom_add
+CPROC_RG = 16        # PTA_CPROC_RG (csrc/pta_cproc.h): realisations per workgroup of pta_engine_cproc_add
+CPROC_MAX = 4        # PTA_CPROC_MAX: common processes per engine
+CPROC_KMAX = 64      # PTA_CPROC_KMAX: columns (2 x 32 frequencies)
 OS_CMAX = 64         # PTA_OS_CMAX
 OS_NORF = 8          # PTA_OS_NORF: ORFs (weight rows) of one pta_os_pairs call
 OSM_KMAX = 128       # PTA_OSM_KMAX

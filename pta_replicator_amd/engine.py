@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _chrom, _cw, _hyper, _lib, _wn_hyper, device as dv
+from . import _bwm, _chrom, _cproc, _cw, _hyper, _lib, _wn_hyper, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -48,6 +48,8 @@ STREAM_CW = 8      # per-realisation CW source labels (generate_sampled): stream
 STREAM_BWM = 9     # per-realisation burst-with-memory labels (generate_sampled): stream_id(9, 0), pair = label column (_bwm.COLUMNS)
 STREAM_CHROM = _chrom.STREAM_CHROM   # 10: the chromatic process, stream_id(10, pulsar), pair c >> 1, branch c & 1 = coefficient c (as STREAM_RN);
                                      # its prior boxes: stream_id(7, 6 .. 7), pair = pulsar (_chrom.FIELD)
+STREAM_CPROC = _cproc.STREAM_CPROC   # 12: the common processes, stream_id(12, process), deviate n = c rho + j: pair n >> 1, branch n & 1;
+                                     # their prior boxes: stream_id(7, 8 .. 9), pair = process (_cproc.FIELD).  (11: the population, _pop)
 
 
 def stream_id(kind, pulsar):
@@ -83,6 +85,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._pop = self._popd = None   # a binary population per realisation (set_population): host tables, their device copies
         self._chrom = None   # one chromatic Gaussian process per pulsar (set_chromatic_noise), added after the fused launch
         self._chrom_t = None   # its device tables, built by prepare()
+        self._cproc = None   # up to four common red processes with an ORF each (add_common_process), added after the chromatic term
+        self._cproc_t = None   # their device tables, built by prepare()
         # state of the per-realisation terms (engine_terms.py): per term the buffers its queued launches still read, replaced when the
         # term next runs; the reused device tables (_scratch); the device copies of the prior boxes (_uniform_table)
         self._keep, self._scratch_tabs, self._boxes = {}, {}, {}
@@ -124,6 +128,51 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         parameters per realisation (_chrom).  Not available in TD mode, nor under the theta-matched OS and the likelihood."""
         self._chrom = _chrom.make_config(self.P, log10_amplitude, spectral_index, components, index, ref_freq_mhz)
         self._prepared = False
+
+    def add_common_process(self, log10_amplitude, spectral_index, orf="curn", components=14):
+        """one more common power-law Gaussian process (at most four) with an ORF of its own: "hd", "monopole" (a clock error), "dipole"
+        (an ephemeris error), "curn" (no correlations) or a symmetric positive semi-definite [P, P] array.  On the array-wide basis
+        f_k = k / T, k <= components <= 32 (T = the span of the whole array; the basis the likelihoods and the OS model a common
+        process on), dt_{a,i} += sum_c F_ic sqrt(phi_c) sum_j B[a, j] z_cj with B B^T = the ORF and phi the red-noise prior at
+        Tspan = T.  Drawn from stream (12, process) and added after the fused launch and the chromatic term (pta_engine_cproc_coef ->
+        pta_engine_cproc_add); theta's cp_log10_A / cp_gamma [R, n_proc] give the processes parameters per realisation (_cproc).  Works
+        with or without set_gwb and for a single pulsar.  Not available in TD mode, nor under the theta-matched OS and the likelihood."""
+        proc = _cproc.make_process(self._unit_vectors(), log10_amplitude, spectral_index, orf, components)
+        self._cproc = _cproc.add(self._cproc, proc)
+        self._prepared = False
+        return self
+
+    @property
+    def common_processes(self):
+        """the configured common processes, in the order of the calls: [{log10_amplitude, spectral_index, orf, components, rank}]"""
+        return [dict(log10_amplitude=p["A"], spectral_index=p["g"], orf=p["orf"], components=p["components"], rank=p["B"].shape[1])
+                for p in (self._cproc or [])]
+
+    def _unit_vectors(self):
+        """unit vectors [P, 3] of the pulsars from their right ascension and declination (the ORFs of the common processes and of
+        prepare_correlated_likelihood)"""
+        from ._position import ra_dec
+        pos = []
+        for p in self.psrs:
+            ra, dec = ra_dec(p, default=(0.0, 0.0))
+            pos.append([np.cos(dec) * np.cos(ra), np.cos(dec) * np.sin(ra), np.sin(dec)])
+        return np.array(pos)
+
+    def _cproc_toas(self):
+        """the times [s] of the array-wide basis, per pulsar: those of _stats_noise_model"""
+        return [m * 86400.0 for m in self.mjd]
+
+    def _prepare_cproc(self):
+        """the tables of the common processes (self._cproc_t): two doubles per TOA (sin, cos)(2 pi frac(t / T)) evaluated in long double
+        on the host, the ORF factors, and the configured amplitudes [n_proc, K]"""
+        t = _cproc.host_tables(self._cproc, self._cproc_toas())
+        t.update(sc1=dv.f64(t["sc1_host"]), amp=dv.f64(t["amp_host"]), B=[dv.f64(b) for b in t["B_host"]])
+        self._cproc_t = t
+
+    def _cproc_low_rank_host(self):
+        """(F [P][N_a, K], phi [P][K]): the auto-term of every common process on the array-wide basis, sum_p Gamma_p,aa phi_p - the columns
+        the fixed-noise statistics add to the low-rank part of C_a.  NumPy alone."""
+        return _cproc.low_rank_host(self._cproc, self._cproc_toas())
 
     def set_white_noise(self, efac=1.0, log10_equad=None, flagid="f", flags=None, tnequad=False):
         """EFAC/EQUAD (white_noise.py:47-125).  Scalars, per-pulsar lists of scalars, or (with `flags`, a per-pulsar
@@ -179,6 +228,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._hy = None  # and the hyper path's tables describe the previous configuration
         self._wnh = None  # and so do the group tables of the per-realisation white noise
         self._chrom_t = None  # and the tables of the chromatic process
+        self._cproc_t = None  # and those of the common processes
         self._td_prepared = False  # and so do the dense factors of TD mode
         self._gw_grid_ready = False
         s = dv.stream_ptr()
@@ -367,6 +417,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             pl.det = self.d_det.data_ptr()
         if self._chrom is not None:
             self._prepare_chrom()
+        if self._cproc:
+            self._prepare_cproc()
         self._prepared = True
         # set-up time is where one-off driver costs belong: with measurement noise configured the dense path can follow, and the
         # factorisation's internal streams (hardware queues, ~10 ms each on this stack: profiles/r05_prepare_td_first_call.txt) are
@@ -650,6 +702,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             self._det_apply(cw, R, out)
         if self._chrom is not None:   # last, so that a row is the row of the engine without the process plus the term: one add
             self._chrom_apply(cw, R, r0, out)
+        if self._cproc:   # after it, by the same rule: the engine without the processes plus generate_per_signal()["common"], one add
+            self._cproc_apply(cw, R, r0, out)
         return out
 
     def _theta_device(self, th, R, mask_unconfigured=True):
@@ -729,9 +783,12 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         theta also holds population_theta(R, r0): gwb_log10_hc [R, F], the cw_* keys [R, S] with cw_count [R], and the labels pop_cell,
         pop_number [R, S] (streams (11, attempt) and (8, s))."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and getattr(self, "_pop", None) is None:
+        wn_prior, chrom_prior, cp_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None), getattr(self, "_cproc_prior", None)
+        if (prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None
+                and getattr(self, "_pop", None) is None):
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
+        if cp_prior is not None and not self._cproc:
+            raise ValueError("generate_sampled: common-process boxes given but no common process is configured (add_common_process)")
         if chrom_prior is not None and self._chrom is None:
             raise ValueError("generate_sampled: chromatic boxes given but no chromatic process is configured (set_chromatic_noise)")
         if prior is not None:
@@ -840,6 +897,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             out["bwm"] = self._bwm_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         if self._chrom is not None:
             out["chrom"] = self._chrom_apply(cw, R, r0, dv.empty((R, self.n_toa)), accumulate=False)
+        if self._cproc:   # 'common': the sum of the common processes (add_common_process), pta_engine_cproc_add writing its own buffer
+            out["common"] = self._cproc_apply(cw, R, r0, dv.empty((R, self.n_toa)), accumulate=False)
         return out
 
     def stream_to_host(self, total, chunk=480, r0=0):
@@ -923,6 +982,14 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
                 buf = dv.empty((Kc,))
                 _lib.call("pta_rng_fill_normal", self.seed, r, 1, stream_id(STREAM_CHROM, a), Kc // 2, 1, dv.ptr(buf), None, Kc, int(self.rng_fast), s)
                 d["chrom"].append(buf.cpu().numpy())
+        if self._cproc:   # 'common': per process z [2 n_f, rho], column c major, factor column j minor
+            t = self._cproc_t
+            d["common"] = []
+            for p, (kp, rho) in enumerate(zip(t["kp"], t["rho"])):
+                npair = (kp * rho + 1) // 2
+                buf = dv.empty((2 * npair,))
+                _lib.call("pta_rng_fill_normal", self.seed, r, 1, stream_id(STREAM_CPROC, p), npair, 1, dv.ptr(buf), None, 2 * npair, int(self.rng_fast), s)
+                d["common"].append(buf.cpu().numpy()[:kp * rho].reshape(kp, rho))
         return d
 
     def replay(self, draws_list, per_signal=False):
@@ -965,6 +1032,13 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
                           ctypes.c_void_p(ccoef_d.data_ptr() + 8 * a * Kc), P * Kc, R,
                           ctypes.c_void_p(out.data_ptr() + 8 * int(self.off[a])), N, 0, s)
             sig["chrom"] = out
+        if self._cproc:   # the coefficients on the host from the given draws, then the add kernel writing a buffer of its own
+            t = self._cproc_t
+            coef = np.zeros((R, P, t["K"]))
+            for r, d in enumerate(draws_list):
+                for p, (kp, B) in enumerate(zip(t["kp"], t["B_host"])):
+                    coef[r, :, :kp] += t["amp_host"][p, :kp][None, :] * (B @ np.asarray(d["common"][p]).T)
+            sig["common"] = self._cproc_add_coef(dv.f64(coef), R, dv.zeros((R, N)))
         if pl.gw_npts:
             Nf, npts = self.grid["Nf"], pl.gw_npts
             w = np.zeros((R, P, Nf, 2))
@@ -1005,7 +1079,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             del keep
             sig["ecorr"] = out
         total = dv.zeros((R, N))
-        for k in ("rn", "chrom", "gwb", "wn", "ecorr"):
+        for k in ("rn", "chrom", "common", "gwb", "wn", "ecorr"):
             if k in sig:
                 total += sig[k]
         if pl.det:

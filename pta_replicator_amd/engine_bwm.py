@@ -22,7 +22,7 @@ state checks are its base StatisticsMixin's, shared with the optimal statistic a
 """
 import torch
 
-from . import _chrom, _cw, _lib, device as dv
+from . import _chrom, _cproc, _cw, _lib, device as dv
 from . import bwm_statistic as bst
 from . import f_statistic as fst
 from ._position import ra_dec
@@ -127,6 +127,7 @@ class BwmStatisticMixin(SkyStatisticsMixin):
         self._bs_modes("generate_bwm_statistic", sky_max, amplitudes)
         if td:
             _chrom.refuse_td(self._chrom, "generate_bwm_statistic(td=True)")
+            _cproc.refuse_td(self._cproc, "generate_bwm_statistic(td=True)")
         st = self._bs_state("generate_bwm_statistic")
         out = self._sky_generate("generate_bwm_statistic", st, lambda: self._bs_state("generate_bwm_statistic"), self._bs_launch,
                                  lambda R: self._bs_out(st, R, sky_max, amplitudes), R, r0, theta, td, chunk, sky_max)

@@ -26,13 +26,12 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _chrom, _lib, device as dv
+from . import _chrom, _cproc, _lib, device as dv
 from . import optimal_statistic as ost
-from ._position import ra_dec
 from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 GRID_KEYS = ("gwb_log10_A", "gwb_gamma")
-_FIXED_PREFIXES = ("rn_", "wn_", "chrom_", "cw_", "bwm_")
+_FIXED_PREFIXES = ("rn_", "wn_", "chrom_", "cp_", "cw_", "bwm_")
 _FIXED_KEYS = ("gwb_log10_hc", "gwb_clm")
 
 
@@ -112,12 +111,8 @@ class CorrelatedLikelihoodMixin(StatisticsMixin):
                              "holds in LDS: fewer components")
         self._stats_need_noise("the correlated likelihood")
         toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M = self._stats_noise_model(timing_model)
-        pos = []
-        for p in self.psrs:
-            ra, dec = ra_dec(p, default=(0.0, 0.0))
-            pos.append([np.cos(dec) * np.cos(ra), np.cos(dec) * np.sin(ra), np.sin(dec)])
         # the OSPlan wants an ORF that does not vanish on every pair; the weights it derives from it are not used here
-        osp = _os_plan(toas, sigma2, np.array(pos), int(components), float(gamma), epoch_of, ecorr, F_rn, phi_rn, M)
+        osp = _os_plan(toas, sigma2, self._unit_vectors(), int(components), float(gamma), epoch_of, ecorr, F_rn, phi_rn, M)
         plan = ost.clnl_plan(osp, orfs, gamma_ref=float(gamma))
         off_yp = np.concatenate([[0], np.cumsum(plan.n)]).astype(np.int64)
         self._clnl = dict(plan=plan, engine_plan=self.plan, C=plan.C, n_orf=len(plan.names), names=list(plan.names), rho=list(plan.rho),
@@ -220,6 +215,7 @@ class CorrelatedLikelihoodMixin(StatisticsMixin):
         the statistic weights with the configured noise, as the fixed-noise OS does."""
         if td:
             _chrom.refuse_td(self._chrom, "generate_correlated_lnl(td=True)")
+            _cproc.refuse_td(self._cproc, "generate_correlated_lnl(td=True)")
         check_grid_keys(grid)
         st = self._clnl_state("generate_correlated_lnl")
         R, r0, chunk = int(R), int(r0), int(chunk)

@@ -24,7 +24,7 @@ state checks are its base StatisticsMixin's, shared with the optimal statistic a
 """
 import torch
 
-from . import _chrom, _cw, _lib, device as dv
+from . import _chrom, _cproc, _cw, _lib, device as dv
 from . import f_statistic as fst
 from ._position import ra_dec
 from .engine_stats import SkyStatisticsMixin, check_components, check_timing_model
@@ -126,6 +126,7 @@ class FStatisticMixin(SkyStatisticsMixin):
         stay the configured ones."""
         if td:
             _chrom.refuse_td(self._chrom, "generate_f_statistic(td=True)")
+            _cproc.refuse_td(self._cproc, "generate_f_statistic(td=True)")
         st = self._fs_state("generate_f_statistic", sky_max)
         out = self._sky_generate("generate_f_statistic", st, lambda: self._fs_state("generate_f_statistic"), self._fs_launch,
                                  lambda R: self._fs_out(st, R, sky_max), R, r0, theta, td, chunk, sky_max)

@@ -22,7 +22,7 @@ buffer) is shared too: engine_stats.StatisticsMixin.
 """
 import ctypes
 
-from . import _chrom, _cw, _hyper, _lib, device as dv
+from . import _chrom, _cproc, _cw, _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
@@ -38,6 +38,7 @@ class LikelihoodMixin(StatisticsMixin):
         check_components(components)
         check_timing_model(timing_model)
         _chrom.refuse_matched(self._chrom, "prepare_likelihood")
+        _cproc.refuse_matched(self._cproc, "prepare_likelihood")
         self._stats_need_noise("the likelihood")
         gw_lA = self._stats_gwb_auto(gwb_auto)
         K_rn = 2 * self._rn["components"] if self._rn is not None else 0
@@ -157,6 +158,7 @@ class LikelihoodMixin(StatisticsMixin):
         {"lnl_pulsar": [R, P, G]} (device tensors, views with free strides); lnl is the sum of lnl_pulsar over the pulsars in
         ascending order.  G and R are cut into chunks that keep the workspace within workspace_bytes."""
         _chrom.refuse_noise_model(grid)
+        _cproc.refuse_noise_model(grid)
         st = self._lnl_state("log_likelihood")
         R = self._stats_check_rows(rows)
         th, G = self._lnl_check_grid(st, grid)
@@ -174,7 +176,9 @@ class LikelihoodMixin(StatisticsMixin):
         the buffer and the likelihood's workspace stay within workspace_bytes."""
         if td:
             _chrom.refuse_td(self._chrom, "generate_lnl(td=True)")
+            _cproc.refuse_td(self._cproc, "generate_lnl(td=True)")
         _chrom.refuse_noise_model(grid)
+        _cproc.refuse_noise_model(grid)
         st = self._lnl_state("generate_lnl")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:

@@ -33,7 +33,7 @@ import ctypes
 
 import numpy as np
 
-from . import _chrom, _hyper, _lib, device as dv
+from . import _chrom, _cproc, _hyper, _lib, device as dv
 from . import optimal_statistic as ost
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -61,6 +61,7 @@ class OptimalStatisticMixin(StatisticsMixin):
         check_components(components)
         if matched:
             _chrom.refuse_matched(self._chrom, "prepare_optimal_statistic(matched=True)")
+            _cproc.refuse_matched(self._cproc, "prepare_optimal_statistic(matched=True)")
         if anisotropy_lmax is not None:
             if isinstance(anisotropy_lmax, bool) or not isinstance(anisotropy_lmax, (int, np.integer)) or not 0 <= anisotropy_lmax <= anis.LMAX_SUPPORTED:
                 raise ValueError(f"anisotropy_lmax={anisotropy_lmax!r}: an integer 0 .. {anis.LMAX_SUPPORTED}")
@@ -128,6 +129,7 @@ class OptimalStatisticMixin(StatisticsMixin):
         configured with a userSpec, the statistic prepared with the GW auto-term) the GW auto-term of row r follows its own spectrum;
         the broadband template S(gamma) stays the prepared one."""
         _chrom.refuse_noise_model(theta)
+        _cproc.refuse_noise_model(theta)
         st = self._os_state("optimal_statistic")
         R = self._stats_check_rows(rows)
         if theta is not None:
@@ -199,8 +201,10 @@ class OptimalStatisticMixin(StatisticsMixin):
         with anisotropy_lmax the result also has a2clm, clm_sigma and clm_cov (not with matched=True)."""
         if td:
             _chrom.refuse_td(self._chrom, "generate_os(td=True)")
+            _cproc.refuse_td(self._cproc, "generate_os(td=True)")
         if matched:
             _chrom.refuse_noise_model(theta)
+            _cproc.refuse_noise_model(theta)
         st = self._os_state("generate_os")
         R, r0, chunk = int(R), int(r0), int(chunk)
         if R < 1 or chunk < 1 or r0 < 0:

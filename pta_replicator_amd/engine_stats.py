@@ -63,6 +63,10 @@ class StatisticsMixin:
             F_ch, phi_ch = self._chrom_low_rank_host()
             F_rn = F_ch if F_rn is None else [np.concatenate([x, y], axis=1) for x, y in zip(F_rn, F_ch)]
             phi_rn = phi_ch if phi_rn is None else [np.concatenate([x, y]) for x, y in zip(phi_rn, phi_ch)]
+        if self._cproc:   # and the auto-term of every common process (add_common_process): F with sum_p Gamma_p,aa phi_p, in the same place
+            F_cp, phi_cp = self._cproc_low_rank_host()
+            F_rn = F_cp if F_rn is None else [np.concatenate([x, y], axis=1) for x, y in zip(F_rn, F_cp)]
+            phi_rn = phi_cp if phi_rn is None else [np.concatenate([x, y]) for x, y in zip(phi_rn, phi_cp)]
         M = None if timing_model is None else [timing_design_matrix(t, model=timing_model)[0] for t in toas]
         return toas, sigma2, epoch_of, ecorr, F_rn, phi_rn, M
 

@@ -30,7 +30,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _chrom, _lib, device as dv
+from . import _chrom, _cproc, _lib, device as dv
 
 STREAM_TD, STREAM_TDGW = 5, 6
 
@@ -60,6 +60,7 @@ class TimeDomainMixin:
     def prepare_td(self, lookahead=True):
         """assemble and factor the dense covariances (once per array and noise model)."""
         _chrom.refuse_td(self._chrom, "prepare_td")
+        _cproc.refuse_td(self._cproc, "prepare_td")
         if not self._prepared:
             self.prepare()
         if self._wn is None:
@@ -346,6 +347,7 @@ class TimeDomainMixin:
         chunks of 256 against 31.2 ms as one chunk - every chunk streams the 13.6 GB of factors again, and the preparation kernels are
         VALU work on the ALUs the matrix pipe shares, not idle time to fill."""
         _chrom.refuse_td(self._chrom, "generate_td")
+        _cproc.refuse_td(self._cproc, "generate_td")
         _, cw = self._theta_parts(theta, R, td=True)   # only deterministic keys (cw_*, bwm_*), added after the batch
         if not getattr(self, "_td_prepared", False) or not self._prepared:
             self.prepare_td()

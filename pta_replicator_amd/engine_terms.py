@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _chrom, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
+from . import _bwm, _chrom, _cproc, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
 from ._position import ra_dec
 
 
@@ -55,7 +55,8 @@ class PerRealisationTermsMixin:
         return self
 
     def set_hyper_prior(self, gwb_log10_A=None, gwb_gamma=None, rn_log10_A=None, rn_gamma=None, gwb_log10_hc=None, gwb_clm=None,
-                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None, chrom_log10_A=None, chrom_gamma=None):
+                        wn_efac=None, wn_log10_equad=None, wn_log10_ecorr=None, chrom_log10_A=None, chrom_gamma=None, cp_log10_A=None,
+                        cp_gamma=None):
         """uniform boxes of generate_sampled(): GWB keys (lo, hi); red-noise keys (lo, hi) for every pulsar or a [P, 2] array;
         gwb_log10_hc (needs set_gwb(userSpec=U [M, 2])): (lo, hi) for every node or [M, 2], box j for row j of U as given - a free
         spectrum per realisation.  gwb_clm (needs set_gwb(lmax=L >= 1)): (lo, hi) for every c_lm with l >= 1 or [(L+1)^2 - 1, 2], box j for
@@ -65,16 +66,19 @@ class PerRealisationTermsMixin:
         wider box may draw skies that are not, which come back flagged (generate_sampled).  wn_efac, wn_log10_equad (need
         set_white_noise) and wn_log10_ecorr (needs set_jitter): (lo, hi) for every group or [G, 2], G = len(wn_groups) or
         len(ecorr_groups), box j for group j.  chrom_log10_A, chrom_gamma (need set_chromatic_noise): (lo, hi) for every pulsar or [P, 2],
-        drawn from stream (7, 6) and (7, 7), pair = pulsar (_chrom.FIELD).  Parameters left out keep their configured values.  No prepare()
+        drawn from stream (7, 6) and (7, 7), pair = pulsar (_chrom.FIELD).  cp_log10_A, cp_gamma (need add_common_process): (lo, hi) for
+        every common process or [n_proc, 2], drawn from stream (7, 8) and (7, 9), pair = process (_cproc.FIELD).  Parameters left out keep their configured values.  No prepare()
         needed after a change."""
         wn_prior = _wn_hyper.make_prior(len(self.wn_groups), len(self.ecorr_groups), wn_efac=wn_efac, wn_log10_equad=wn_log10_equad,
                                         wn_log10_ecorr=wn_log10_ecorr) or None
         chrom_prior = _chrom.make_prior(self.P, chrom_log10_A=chrom_log10_A, chrom_gamma=chrom_gamma) or None
+        cp_prior = _cproc.make_prior(len(self._cproc or []), cp_log10_A=cp_log10_A, cp_gamma=cp_gamma) or None
         prior = None   # (white-noise or chromatic boxes alone are a prior; nothing at all is _hyper.make_prior's "no parameter given")
-        if (wn_prior is None and chrom_prior is None) or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
+        if (wn_prior is None and chrom_prior is None and cp_prior is None) or any(x is not None for x in (gwb_log10_A, gwb_gamma, rn_log10_A, rn_gamma, gwb_log10_hc, gwb_clm)):
             prior = _hyper.make_prior(self.P, _hyper._n_nodes(self._gw), _hyper.n_lm(self._gw), gwb_log10_A=gwb_log10_A, gwb_gamma=gwb_gamma,
                                       rn_log10_A=rn_log10_A, rn_gamma=rn_gamma, gwb_log10_hc=gwb_log10_hc, gwb_clm=gwb_clm)
         self._chrom_prior = chrom_prior
+        self._cproc_prior = cp_prior
         self._prior, self._wn_prior = prior, wn_prior   # new dicts: the device copies of the previous boxes are not theirs (_uniform_table)
         return self
 
@@ -140,10 +144,12 @@ class PerRealisationTermsMixin:
             theta = _pop.strip_labels(theta)                  # and so are the population's pop_cell / pop_number
         rest, wnk = _wn_hyper.split(theta)   # ahead of _hyper.check_theta, whose key list stays the GWB / red-noise one
         rest, chk = _chrom.split(rest)
+        rest, cpk = _cproc.split(rest)
         rest, cw = _cw.split(rest)
         rest, bwm = _bwm.split(rest)
         if td:
             _chrom.refuse_td(self._chrom)
+            _cproc.refuse_td(self._cproc)
             _wn_hyper.refuse_td(wnk)
         if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
@@ -152,6 +158,7 @@ class PerRealisationTermsMixin:
         det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
         det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
         det.update(_chrom.check_theta(chk, R, self.P, self._chrom, check_values))
+        det.update(_cproc.check_theta(cpk, R, self._cproc, check_values))
         if det and not rest:
             return None, det
         return _hyper.check_theta(rest, R, self.P, self._gw, self._rn, self.gwb_mode, check_values), det
@@ -310,6 +317,51 @@ class PerRealisationTermsMixin:
         self._keep["chrom"] = (lA, g)   # the launches above read them asynchronously
         return out
 
+    # ---------------------------------------------------------------- common processes ----------
+    def _cproc_theta_device(self, det, R):
+        """validated cp_* keys of theta -> (log10_A, gamma) contiguous float64 device tensors [R, n_proc], a key not given filled with
+        the configured values; (None, None) without keys"""
+        if not _cproc.has_keys(det):
+            return None, None
+        n = len(self._cproc)
+        return tuple(dv.as_f64(det[k]) if k in det else dv.f64(np.ascontiguousarray(np.broadcast_to(c, (R, n))))
+                     for k, c in zip(_cproc.KEYS, _cproc.configured(self._cproc)))
+
+    def _cproc_struct(self):
+        """pta_cproc_engine of the prepared tables, the per-batch members (log10_A, gamma, coef) left NULL"""
+        t = self._cproc_t
+        c = _lib.CprocEngine()
+        c.n_psr, c.n_proc, c.k, c.rng_fast = self.P, len(t["kp"]), t["K"], int(self.rng_fast)
+        for p, (kp, rho, B) in enumerate(zip(t["kp"], t["rho"], t["B"])):
+            c.kp[p], c.rho[p], c.B[p] = kp, rho, B.data_ptr()
+        c.amp, c.tspan, c.sc1, c.ld_theta = t["amp"].data_ptr(), t["T"], t["sc1"].data_ptr(), len(t["kp"])
+        return c
+
+    def _cproc_apply(self, det, R, r0, out, accumulate=True):
+        """out[R, n_toa] (+)= the sum of the common processes of realisations r0 .. r0+R-1 (row r = realisation r0 + r), with theta's
+        cp_* keys of `det` where it has them: pta_engine_cproc_coef (coef [n, P, K], drawn from stream (12, process)) ->
+        pta_engine_cproc_add, in batches of max_batch().  The coefficient table stays outside the workspace budget."""
+        if not self._prepared:
+            self.prepare()
+        n_proc = len(self._cproc)
+        lA, g = self._cproc_theta_device(det, R)
+        step = min(R, self.max_batch())
+        c = self._cproc_struct()
+        c.coef = self._scratch("cproc_coef", (step, self.P, self._cproc_t["K"])).data_ptr()
+        rows = [("log10_A", lA, 8 * n_proc), ("gamma", g, 8 * n_proc)]
+        self._term_batches("pta_engine_cproc_coef", "pta_engine_cproc_add", c, rows, R, step, out, accumulate, draw=(self.seed, r0))
+        self._keep["cproc"] = (lA, g)   # the launches above read them asynchronously
+        return out
+
+    def _cproc_add_coef(self, coef, R, out, accumulate=False):
+        """out[R, n_toa] (+)= the synthesis of given coefficients coef [R, P, K] (device): pta_engine_cproc_add alone (replay)"""
+        c = self._cproc_struct()
+        c.coef = coef.data_ptr()
+        _lib.call("pta_engine_cproc_add", ctypes.byref(self.plan), ctypes.byref(c), R, ctypes.c_void_p(out.data_ptr()), out.stride(0),
+                  1 if accumulate else 0, dv.stream_ptr())
+        self._keep["cproc_coef"] = coef
+        return out
+
     # ---------------------------------------------------------------- white noise ---------------
     def _wn_tables(self):
         """theta-independent device tables of the per-realisation white noise, built once per prepare(): sigma [n_toa], the white-noise
@@ -420,9 +472,9 @@ class PerRealisationTermsMixin:
 
     def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
-        wn_prior, chrom_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None)
+        wn_prior, chrom_prior, cp_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None), getattr(self, "_cproc_prior", None)
         pop = getattr(self, "_pop", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and pop is None:
+        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None and pop is None:
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
@@ -452,6 +504,13 @@ class PerRealisationTermsMixin:
             none = np.flatnonzero(np.isnan(_chrom.configured(self._chrom)[0]))
             if len(none):   # pulsars configured without the process keep none: their labels are NaN
                 theta[k][:, dv.i64(none)] = float("nan")
+        if cp_prior is not None and not self._cproc:
+            raise ValueError("sample_theta: common-process boxes given but no common process is configured (add_common_process)")
+        for k, box in (cp_prior or {}).items():   # streams (7, 8 .. 9): pair = process, whatever else is sampled
+            if len(box[0]) != len(self._cproc):
+                raise ValueError(f"sample_theta: the {k} boxes are for {len(box[0])} processes but the engine now has {len(self._cproc)}: "
+                                 "call set_hyper_prior again")
+            theta[k] = self._uniform_table("pta_hyper_uniform_field", k, cp_prior, lambda: box, R, r0, mid=(len(box[0]), _cproc.FIELD[k]))
         if prior is None:
             return theta
         box = _hyper.spec_bounds(prior)

@@ -184,6 +184,55 @@ def add_chromatic_noise(psr, log10_amplitude, spectral_index, components=30, ind
         p_.update_residuals()
 
 
+def add_common_process(psrs, log10_amplitude, spectral_index, orf="curn", components=14, Tspan=None, seed=None):
+    """Add one common power-law Gaussian process with an ORF of its own to a LIST of pulsars (one pulsar: a list of one): "hd",
+    "monopole" (a clock error), "dipole" (an ephemeris error), "curn" (no correlations) or a symmetric positive semi-definite [P, P]
+    array.  dt_{a,i} = sum_c F_ic sqrt(phi_c) sum_j B[a, j] z_cj on the array-wide basis f_k = k / T, k <= components <= 32 (times
+    mjd * 86400; T = Tspan [s], None = the span of all the pulsars' TOAs), B B^T = the ORF (optimal_statistic.orf_factor), phi the
+    red-noise prior at Tspan = T: the list twin of ReplicaEngine.add_common_process.  The deviates are the legacy NumPy ones with
+    add_red_noise's seed convention (np.random.seed(seed) when given, then one np.random.randn of 2 components x rank values, column c
+    major, factor column j minor); they are mixed on the host and synthesised by pta_engine_cproc_add with R = 1 (the entry that draws,
+    pta_engine_cproc_coef, serves the engine's counter-based stream).  Recorded as '{name}_common_process'."""
+    from . import _cproc
+    from ._position import ra_dec
+    if not isinstance(psrs, (list, tuple)) or not psrs:
+        raise ValueError("add_common_process: psrs must be a non-empty list of pulsars (the process is common to them)")
+    psrs = list(psrs)
+    pos = []
+    for p_ in psrs:
+        ra, dec = ra_dec(p_, default=(0.0, 0.0))
+        pos.append([np.cos(dec) * np.cos(ra), np.cos(dec) * np.sin(ra), np.sin(dec)])
+    proc = _cproc.make_process(np.array(pos), log10_amplitude, spectral_index, orf, components)   # refusals first: nothing is touched
+    toas = [np.asarray(p_.toas.get_mjds().value, dtype=np.float64) * 86400.0 for p_ in psrs]
+    T = _cproc.span(toas) if Tspan is None else float(Tspan)
+    if not (np.isfinite(T) and T > 0):
+        raise ValueError(f"add_common_process: Tspan={Tspan!r} must be finite and positive (None: the TOAs must span some time)")
+    if seed is not None:
+        np.random.seed(seed)
+    P, K, B = len(psrs), 2 * proc["components"], proc["B"]
+    z = np.random.randn(K * B.shape[1]).reshape(K, B.shape[1])
+    coef = np.ascontiguousarray(np.sqrt(_cproc.prior_phi(proc["components"], T, proc["A"], proc["g"]))[None, :] * (B @ z.T))   # [P, K]
+    counts = np.array([len(t) for t in toas])
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    tiles = [(a, int(off[a]) + i0, min(_lib.ENGINE_TILE, int(counts[a]) - i0)) for a in range(P) for i0 in range(0, int(counts[a]), _lib.ENGINE_TILE)]
+    t_psr, t_start, t_count = (dv.i32(np.array([t[k] for t in tiles], dtype=np.int32)) for k in range(3))
+    sc1, coef_d = dv.f64(np.concatenate([_cproc.sincos1(t, T) for t in toas])), dv.f64(coef)
+    plan = _lib.EnginePlan()
+    plan.n_toa, plan.n_psr, plan.n_tiles = int(off[-1]), P, len(tiles)
+    plan.tile_psr, plan.tile_start, plan.tile_count = t_psr.data_ptr(), t_start.data_ptr(), t_count.data_ptr()
+    c = _lib.CprocEngine()
+    c.n_psr, c.n_proc, c.k, c.sc1, c.coef = P, 1, K, sc1.data_ptr(), coef_d.data_ptr()
+    out = dv.empty((1, int(off[-1])))
+    _lib.call("pta_engine_cproc_add", ctypes.byref(plan), ctypes.byref(c), 1, dv.ptr(out), int(off[-1]), 0, dv.stream_ptr())
+    res = dv.download(out[0])
+    for a, p_ in enumerate(psrs):
+        dt = res[off[a]:off[a + 1]] * u.s
+        p_.update_added_signals("{}_common_process".format(p_.name),
+                                {"amplitude": log10_amplitude, "spectral_index": spectral_index, "orf": proc["orf"], "components": proc["components"]}, dt)
+        p_.toas.adjust_TOAs(TimeDelta(dt.to("day")))
+        p_.update_residuals()
+
+
 # ------------------------------------------------------------------------------------------------
 # GWB
 # ------------------------------------------------------------------------------------------------
