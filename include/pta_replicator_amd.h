@@ -1108,6 +1108,26 @@ int pta_clock_probe(uint64_t *samples, int max_samples, int us, int period_us, v
  * product with asymmetric operands matches the scalar result on the device.                */
 int pta_selftest_mfma_f64(double *max_err_host);
 
+/* ---------------------------------------------------------------- launch plans ----- */
+/* What a launcher chooses from the sizes of a launch (additive to ABI 8): each entry runs the very function its launcher calls and
+ * writes the choice to `plan`.  No device call, so they work without a GPU; bad sizes are refused with PTA_E_ARG as the launcher
+ * refuses them.  The choice only regroups realisations, grid points or tiles: an output value does not depend on it (the tests hold
+ * every instance to that, tests/launch_cases.py).
+ *   pta_os_project_plan        plan[0..2] = rw (16-realisation tiles per wave, 1 or 2), ct = ceil(C / 16) (1..4), grid.x
+ *   pta_lnl_apply_plan         plan[0..2] = kt = ceil(K / 16) (1..8), g_per (grid points per workgroup, 1..16), gz = ceil(G / g_per)
+ *   pta_fstat_project_plan     plan[0..1] = bm, bn (realisations x columns of a workgroup's tile: 128 or 64 x 128, 64 or 32)
+ *   pta_gwb_mix_batched_plan   plan[0..2] = nta = ceil(P / 16) (1..5), tpw (64-sample tiles per workgroup), grid.x; all three 0 when the
+ *                              launch goes to the batched GEMM (variant != 0 or P > 80)
+ *   pta_fstat_fe_plan, pta_bwm_stat_plan   plan[0..2] = ks = ceil(P / 4) (1..32), rchunk (realisations per workgroup), ngz = ceil(R / rchunk)
+ *   pta_tm_project_plan        plan[0..1] = m (the instance, 1..12), grid.y                                                        */
+int pta_os_project_plan(int C, int P, int R, int32_t *plan);
+int pta_lnl_apply_plan(int P, int K, int G, int R, int32_t *plan);
+int pta_fstat_project_plan(int C, int P, int R, int32_t *plan);
+int pta_gwb_mix_batched_plan(int P, int R, int npts, int variant, int32_t *plan);
+int pta_fstat_fe_plan(int P, int J, int R, int S, int32_t *plan);
+int pta_bwm_stat_plan(int P, int J, int R, int S, int32_t *plan);
+int pta_tm_project_plan(int m, int P, int R, int32_t *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,10 +236,37 @@ _SIGNATURES = {
     "pta_selftest_mfma_f64": (c_int, [POINTER(c_double)]),
     "pta_pop_draw_select": (c_int, [POINTER(PopPlan), c_uint64, c_uint64, c_int, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     "pta_pop_theta": (c_int, [POINTER(PopPlan), c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P]),
+    "pta_os_project_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_lnl_apply_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_fstat_project_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_gwb_mix_batched_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_fstat_fe_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_bwm_stat_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_tm_project_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
     "pta_gwb_spectrum_scale_user": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P]),
     "pta_hyper_uniform_field": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_os_matched_prior_spec": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, c_int, _P, c_int64, _P, _P, _P]),
 }
+
+# the values a pta_*_plan entry writes, in order (include/pta_replicator_amd.h)
+_PLAN_FIELDS = {
+    "pta_os_project": ("rw", "ct", "grid_x"),
+    "pta_lnl_apply": ("kt", "g_per", "gz"),
+    "pta_fstat_project": ("bm", "bn"),
+    "pta_gwb_mix_batched": ("nta", "tpw", "grid_x"),
+    "pta_fstat_fe": ("ks", "rchunk", "ngz"),
+    "pta_bwm_stat": ("ks", "rchunk", "ngz"),
+    "pta_tm_project": ("m", "grid_y"),
+}
+
+
+def launch_plan(launcher, *sizes):
+    """What `launcher` would choose for a launch of these sizes (the arguments of its pta_*_plan entry, without `plan`), as a dict.
+    No device call."""
+    out = (c_int32 * 4)()
+    check(getattr(lib, launcher + "_plan")(*[int(v) for v in sizes], out), launcher + "_plan")
+    return {k: int(out[i]) for i, k in enumerate(_PLAN_FIELDS[launcher])}
+
 
 ENGINE_TILE = 256   # PTA_ENGINE_TILE
 ENGINE_EPMAX = 132  # PTA_ENGINE_EPMAX

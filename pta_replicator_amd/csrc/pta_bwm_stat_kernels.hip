@@ -22,6 +22,8 @@ struct bwm_stat {
   }
 };
 
+extern "C" int pta_bwm_stat_plan(int P, int J, int R, int S, int32_t *plan) { return pta_sky_stat_plan<bwm_stat>("pta_bwm_stat_plan", P, J, R, S, plan); }
+
 extern "C" int pta_bwm_stat(const double *Q, int64_t ld_q, int P, int C, int J, int R, const double *phi, int S, const double *Minv, double *fb,
                             int64_t ld_fb, double *amp, int64_t ld_amp, double *fb_max, int64_t ld_max, int32_t *fb_arg, int64_t ld_arg,
                             double *part_val, int32_t *part_arg, void *stream) {

@@ -72,13 +72,30 @@ __global__ __launch_bounds__(256) void k_tm_project(const double *__restrict__ Q
   }
 }
 
+// The launch plan of pta_tm_project, the one place it is decided: the k_tm_project<m> instance and ng workgroups along the
+// realisations.  `who` names the entry in the refusals.
+static int pta_tm_project_choose(const char *who, int m, int P, int R, unsigned &ng) {
+  PTA_REQUIRE(m >= 1 && m <= PTA_FIT_MMAX && P > 0 && P <= 65535 && R > 0, PTA_E_ARG, "%s: m=%d (1..%d) P=%d R=%d", who, m, PTA_FIT_MMAX, P, R);
+  ng = pta_cdiv(R, PTA_FIT_RB);
+  PTA_REQUIRE(ng <= 65535u, PTA_E_ARG, "%s: R=%d exceeds one launch (<= %d)", who, R, 65535 * PTA_FIT_RB);
+  return PTA_OK;
+}
+
+extern "C" int pta_tm_project_plan(int m, int P, int R, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_tm_project_plan: NULL argument");
+  unsigned ng;
+  const int rc = pta_tm_project_choose("pta_tm_project_plan", m, P, R, ng);
+  if (rc != PTA_OK) return rc;
+  plan[0] = m, plan[1] = (int32_t)ng;
+  return PTA_OK;
+}
+
 extern "C" int pta_tm_project(const double *Qt, const double *Mt, int64_t ld, int m, const int32_t *psr_off, int P, double *rows,
                               int64_t ld_rows, int R, void *stream) {
   PTA_REQUIRE(Qt && Mt && psr_off && rows, PTA_E_ARG, "pta_tm_project: NULL argument");
-  PTA_REQUIRE(m >= 1 && m <= PTA_FIT_MMAX && P > 0 && P <= 65535 && R > 0, PTA_E_ARG, "pta_tm_project: m=%d (1..%d) P=%d R=%d", m, PTA_FIT_MMAX, P,
-              R);
-  const unsigned ng = pta_cdiv(R, PTA_FIT_RB);
-  PTA_REQUIRE(ng <= 65535u, PTA_E_ARG, "pta_tm_project: R=%d exceeds one launch (<= %d)", R, 65535 * PTA_FIT_RB);
+  unsigned ng;
+  const int rc = pta_tm_project_choose("pta_tm_project", m, P, R, ng);
+  if (rc != PTA_OK) return rc;
   dim3 g(P, ng), b(256);
   hipStream_t s = pta_stream(stream);
 #define PTA_TM_CASE(MM) \

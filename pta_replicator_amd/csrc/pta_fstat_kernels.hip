@@ -175,23 +175,41 @@ int pta_fstat_reduce_launch(const double *part_val, const int32_t *part_arg, int
   return PTA_OK;
 }
 
-extern "C" int pta_fstat_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R,
-                                 double *Q, int64_t ld_q, void *stream) {
-  PTA_REQUIRE(Wt && psr_off && rows && Q, PTA_E_ARG, "pta_fstat_project: NULL argument");
+// The launch plan of pta_fstat_project, the one place it is decided: the bm x bn (realisations x columns) tile of a workgroup.  `who`
+// names the entry in the refusals.
+static int pta_fstat_project_choose(const char *who, int C, int P, int R, int &bm, int &bn) {
   PTA_REQUIRE(C >= 2 && C % 2 == 0 && C <= PTA_FSTAT_CMAX && P > 0 && P <= 65535 && R > 0, PTA_E_ARG,
-              "pta_fstat_project: C=%d (even, 2..%d) P=%d (1..65535) R=%d", C, PTA_FSTAT_CMAX, P, R);
-  PTA_REQUIRE(ld_q >= (int64_t)P * C && ldw >= 1 && ld_rows >= 1, PTA_E_ARG, "pta_fstat_project: ld_q=%lld < P*C=%lld or ldw / ld_rows < 1",
-              (long long)ld_q, (long long)P * C);
-  PTA_REQUIRE(pta_cdiv(R, 64) <= 65535u, PTA_E_ARG, "pta_fstat_project: R=%d exceeds one launch (64 * 65535 realisations)", R);
-  hipStream_t s = pta_stream(stream);
-  dim3 block(256);
+              "%s: C=%d (even, 2..%d) P=%d (1..65535) R=%d", who, C, PTA_FSTAT_CMAX, P, R);
+  PTA_REQUIRE(pta_cdiv(R, 64) <= 65535u, PTA_E_ARG, "%s: R=%d exceeds one launch (64 * 65535 realisations)", who, R);
   // The tile follows the launch's size alone - a realisation's Q does not depend on it (every output is its own MFMA chain over
   // ascending slabs).  128 x 128 while that leaves FS_FILL workgroups; else 64 rows, then 64 columns: a workgroup walks its whole
   // pulsar, so with few workgroups the longest pulsar of a ragged array sets the launch's time, and a smaller tile shortens that walk.
-  int bm = 128, bn = C > 64 ? 128 : (C > 32 ? 64 : 32);
+  bm = 128, bn = C > 64 ? 128 : (C > 32 ? 64 : 32);
   auto wgs = [&]() { return (long long)P * pta_cdiv(R, bm) * pta_cdiv(C, bn); };
   if (wgs() < FS_FILL) bm = 64;
   if (wgs() < FS_FILL && bn == 128) bn = 64;
+  return PTA_OK;
+}
+
+extern "C" int pta_fstat_project_plan(int C, int P, int R, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_fstat_project_plan: NULL argument");
+  int bm, bn;
+  const int rc = pta_fstat_project_choose("pta_fstat_project_plan", C, P, R, bm, bn);
+  if (rc != PTA_OK) return rc;
+  plan[0] = bm, plan[1] = bn;
+  return PTA_OK;
+}
+
+extern "C" int pta_fstat_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R,
+                                 double *Q, int64_t ld_q, void *stream) {
+  PTA_REQUIRE(Wt && psr_off && rows && Q, PTA_E_ARG, "pta_fstat_project: NULL argument");
+  int bm, bn;
+  const int rc = pta_fstat_project_choose("pta_fstat_project", C, P, R, bm, bn);
+  if (rc != PTA_OK) return rc;
+  PTA_REQUIRE(ld_q >= (int64_t)P * C && ldw >= 1 && ld_rows >= 1, PTA_E_ARG, "pta_fstat_project: ld_q=%lld < P*C=%lld or ldw / ld_rows < 1",
+              (long long)ld_q, (long long)P * C);
+  hipStream_t s = pta_stream(stream);
+  dim3 block(256);
   const dim3 grid(pta_cdiv(C, bn), pta_cdiv(R, bm), P);
 #define PTA_FS_PROJ(TM_, TN_) \
   hipLaunchKernelGGL((k_fstat_project<TM_, TN_>), grid, block, 0, s, Wt, ldw, C, psr_off, rows, ld_rows, R, Q, ld_q)
@@ -223,6 +241,8 @@ extern "C" int pta_fstat_fp(const double *Q, int64_t ld_q, int P, int J, int R, 
 }
 
 extern "C" int64_t pta_fstat_fe_tiles(int S) { return S < 1 ? 0 : (int64_t)((S + SKY_ST - 1) / SKY_ST) * (SKY_ST / 16); }
+
+extern "C" int pta_fstat_fe_plan(int P, int J, int R, int S, int32_t *plan) { return pta_sky_stat_plan<fe_stat>("pta_fstat_fe_plan", P, J, R, S, plan); }
 
 extern "C" int pta_fstat_fe(const double *Q, int64_t ld_q, int P, int J, int R, const double *phi, int S, const double *Minv, double *fe,
                             int64_t ld_fe, double *fe_max, int64_t ld_max, int32_t *fe_arg, int64_t ld_arg, double *part_val, int32_t *part_arg,

@@ -218,6 +218,32 @@ __global__ __launch_bounds__(256) void k_gwb_mix_batched(const double *__restric
   }
 }
 
+// The launch plan of pta_gwb_mix_batched, the one place it is decided: the k_gwb_mix_batched<nta> instance, tpw 64-sample tiles per
+// workgroup and gx workgroups per realisation; nta = 0: the batched GEMM (variant != 0 or P > PTA_ORF_PMAX), which has no such choice.
+// `who` names the entry in the refusals.
+static int pta_gwb_mix_batched_choose(const char *who, int P, int R, int npts, int variant, int &nta, int &tpw, unsigned &gx) {
+  PTA_REQUIRE(P > 0 && R > 0 && npts > 0, PTA_E_ARG, "%s: P=%d R=%d npts=%d", who, P, R, npts);
+  nta = tpw = 0, gx = 0;
+  if (variant != 0 || P > PTA_ORF_PMAX) return PTA_OK;
+  nta = (P + 15) / 16;
+  const int ntile = (int)pta_cdiv(npts, MIXB_JT);
+  // a workgroup keeps its factor for all tiles of the realisation once the realisations alone fill the chip, else for four
+  tpw = (R >= 512 || ntile <= 4) ? ntile : 4;
+  gx = pta_cdiv(ntile, tpw);
+  PTA_REQUIRE(R <= 65535, PTA_E_ARG, "%s: R=%d too large for one launch", who, R);
+  return PTA_OK;
+}
+
+extern "C" int pta_gwb_mix_batched_plan(int P, int R, int npts, int variant, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_gwb_mix_batched_plan: NULL argument");
+  int nta, tpw;
+  unsigned gx;
+  const int rc = pta_gwb_mix_batched_choose("pta_gwb_mix_batched_plan", P, R, npts, variant, nta, tpw, gx);
+  if (rc != PTA_OK) return rc;
+  plan[0] = nta, plan[1] = tpw, plan[2] = (int32_t)gx;
+  return PTA_OK;
+}
+
 // variant: as pta_gwb_mix (0 = the LDS kernel when P <= 80, else the batched MFMA GEMM; 1 = always that GEMM; 2 = the VALU reference GEMM)
 extern "C" int pta_gwb_mix_batched(const double *Mchol, int64_t ld_m, int P, const double *G0, int R, int npts, int64_t ldg, double *G,
                                    int variant, void *stream) {
@@ -225,14 +251,14 @@ extern "C" int pta_gwb_mix_batched(const double *Mchol, int64_t ld_m, int P, con
   PTA_REQUIRE(P > 0 && R > 0 && npts > 0 && ldg >= npts && ld_m >= (int64_t)P * P, PTA_E_ARG,
               "pta_gwb_mix_batched: P=%d R=%d npts=%d ldg=%lld ld_m=%lld", P, R, npts, (long long)ldg, (long long)ld_m);
   const int64_t sr = (int64_t)P * ldg;
-  if (variant == 0 && P <= PTA_ORF_PMAX) {
-    const int nta = (P + 15) / 16, kp = (P + 3) & ~3;
-    const int ntile = (int)pta_cdiv(npts, MIXB_JT);
-    // a workgroup keeps its factor for all tiles of the realisation once the realisations alone fill the chip, else for four
-    const int tpw = (R >= 512 || ntile <= 4) ? ntile : 4;
+  int nta, tpw;
+  unsigned gx;
+  const int rc0 = pta_gwb_mix_batched_choose("pta_gwb_mix_batched", P, R, npts, variant, nta, tpw, gx);
+  if (rc0 != PTA_OK) return rc0;
+  if (nta) {
+    const int kp = (P + 3) & ~3;
     const size_t shmem = (size_t)kp * nta * 16 * sizeof(double);
-    dim3 g(pta_cdiv(ntile, tpw), R);
-    PTA_REQUIRE(g.y <= 65535u, PTA_E_ARG, "pta_gwb_mix_batched: R=%d too large for one launch", R);
+    dim3 g(gx, R);
 #define PTA_MIXB(N) hipLaunchKernelGGL(k_gwb_mix_batched<N>, g, dim3(256), shmem, pta_stream(stream), Mchol, ld_m, P, G0, npts, ldg, G, tpw)
     switch (nta) {
       case 1: PTA_MIXB(1); break;

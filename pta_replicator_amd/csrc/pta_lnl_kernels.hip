@@ -263,6 +263,32 @@ static int pta_lnl_apply_launch(dim3 grid, size_t shmem, hipStream_t st, const d
   return PTA_OK;
 }
 
+// The launch plan of pta_lnl_apply, the one place it is decided: the k_lnl_apply<kt> instance, g_per grid points per workgroup and gz
+// workgroups along the grid.  `who` names the entry in the refusals.
+static int pta_lnl_apply_choose(const char *who, int P, int K, int G, int R, int &kt, int &g_per, unsigned &gz) {
+  PTA_REQUIRE(K >= 1 && K <= PTA_LNL_KMAX, PTA_E_ARG, "%s: K=%d (1..%d)", who, K, PTA_LNL_KMAX);
+  PTA_REQUIRE(P > 0 && P <= 65535 && G > 0 && R > 0, PTA_E_ARG, "%s: P=%d G=%d R=%d", who, P, G, R);
+  kt = (K + 15) / 16;
+  const unsigned rb = pta_cdiv(R, 64 * PTA_LNL_RW);
+  // grid points per workgroup (they share the projections held in registers): as many as leave the device a few thousand workgroups
+  long long gp = (long long)G * P * rb / 4096;
+  gp = gp < 1 ? 1 : (gp > 16 ? 16 : gp);
+  g_per = (int)gp;
+  gz = pta_cdiv(G, gp);
+  PTA_REQUIRE(gz <= 65535u, PTA_E_ARG, "%s: G=%d exceeds one launch", who, G);
+  return PTA_OK;
+}
+
+extern "C" int pta_lnl_apply_plan(int P, int K, int G, int R, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_lnl_apply_plan: NULL argument");
+  int kt, g_per;
+  unsigned gz;
+  const int rc = pta_lnl_apply_choose("pta_lnl_apply_plan", P, K, G, R, kt, g_per, gz);
+  if (rc != PTA_OK) return rc;
+  plan[0] = kt, plan[1] = g_per, plan[2] = (int32_t)gz;
+  return PTA_OK;
+}
+
 extern "C" int pta_lnl_apply(const double *Lt, const double *logdet, const double *b, int P, int K, int C, int G, const double *q, int64_t ld_q, int q_block, int Kt,
                              int R, const double *r0, const double *s, const double *c, double *lnl_pulsar, int64_t ld_g, int64_t ld_a,
                              void *stream) {
@@ -272,19 +298,18 @@ extern "C" int pta_lnl_apply(const double *Lt, const double *logdet, const doubl
   PTA_REQUIRE(P > 0 && P <= 65535 && G > 0 && R > 0, PTA_E_ARG, "pta_lnl_apply: P=%d G=%d R=%d", P, G, R);
   PTA_REQUIRE(q_block >= 1 && ld_q >= (int64_t)P * Kt && ld_a >= R && ld_g >= 1, PTA_E_ARG,
               "pta_lnl_apply: q_block=%d ld_q=%lld (>= P * Kt) ld_a=%lld (>= R)", q_block, (long long)ld_q, (long long)ld_a);
-  const int kt = (K + 15) / 16, kp = 16 * kt, S = kp | 16;
+  int kt, g_per;
+  unsigned gz;
+  const int rc = pta_lnl_apply_choose("pta_lnl_apply", P, K, G, R, kt, g_per, gz);
+  if (rc != PTA_OK) return rc;
+  const int kp = 16 * kt, S = kp | 16;
   const unsigned rb = pta_cdiv(R, 64 * PTA_LNL_RW);
-  // grid points per workgroup (they share the projections held in registers): as many as leave the device a few thousand workgroups
-  long long g_per = (long long)G * P * rb / 4096;
-  g_per = g_per < 1 ? 1 : (g_per > 16 ? 16 : g_per);
-  const unsigned gz = pta_cdiv(G, g_per);
-  PTA_REQUIRE(gz <= 65535u, PTA_E_ARG, "pta_lnl_apply: G=%d exceeds one launch", G);
   const size_t shmem = ((size_t)4 * ((K + 3) / 4) * S + kp) * sizeof(double);
   dim3 grid(rb, P, gz);
   hipStream_t st = pta_stream(stream);
 #define PTA_LNL_CASE(KT_) \
   case KT_:               \
-    return pta_lnl_apply_launch<KT_>(grid, shmem, st, Lt, logdet, b, P, K, G, (int)g_per, q, ld_q, q_block, Kt, R, r0, s, c, lnl_pulsar, ld_g, ld_a);
+    return pta_lnl_apply_launch<KT_>(grid, shmem, st, Lt, logdet, b, P, K, G, g_per, q, ld_q, q_block, Kt, R, r0, s, c, lnl_pulsar, ld_g, ld_a);
   switch (kt) {
     PTA_LNL_CASE(1) PTA_LNL_CASE(2) PTA_LNL_CASE(3) PTA_LNL_CASE(4) PTA_LNL_CASE(5) PTA_LNL_CASE(6) PTA_LNL_CASE(7) PTA_LNL_CASE(8)
   }

@@ -132,21 +132,40 @@ __global__ __launch_bounds__(256) void k_os_pairs(const double *__restrict__ Y, 
   if (t < n_orf) A2[r * ld_a2 + t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
 }
 
+// The launch plan of pta_os_project, the one place it is decided: rw 16-realisation tiles per wave, ct 16-column tiles of W, ng
+// workgroups along the realisations.  `who` names the entry in the refusals.
+static int pta_os_project_choose(const char *who, int C, int P, int R, int &rw, int &ct, unsigned &ng) {
+  PTA_REQUIRE(C >= 1 && C <= PTA_OS_CMAX && P > 0 && P <= 65535 && R > 0, PTA_E_ARG, "%s: C=%d (1..%d) P=%d R=%d", who, C, PTA_OS_CMAX, P, R);
+  // two 16-realisation tiles per wave when that still leaves every CU a few workgroups (halves the W re-reads); the choice only
+  // regroups realisations, the per-realisation sums are the same
+  rw = ((long long)pta_cdiv(R, 128) * P >= 1024) ? 2 : 1;
+  ng = pta_cdiv(R, 64 * rw);
+  PTA_REQUIRE(ng <= 0x7fffffffu, PTA_E_ARG, "%s: R=%d exceeds one launch", who, R);
+  ct = (C + 15) / 16;
+  return PTA_OK;
+}
+
+extern "C" int pta_os_project_plan(int C, int P, int R, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_os_project_plan: NULL argument");
+  int rw, ct;
+  unsigned ng;
+  const int rc = pta_os_project_choose("pta_os_project_plan", C, P, R, rw, ct, ng);
+  if (rc != PTA_OK) return rc;
+  plan[0] = rw, plan[1] = ct, plan[2] = (int32_t)ng;
+  return PTA_OK;
+}
+
 extern "C" int pta_os_project(const double *Wt, int64_t ldw, int C, const int32_t *psr_off, int P, const double *rows, int64_t ld_rows, int R,
                               double *Y, int64_t ld_y, void *stream) {
   PTA_REQUIRE(Wt && psr_off && rows && Y, PTA_E_ARG, "pta_os_project: NULL argument");
-  PTA_REQUIRE(C >= 1 && C <= PTA_OS_CMAX && P > 0 && P <= 65535 && R > 0, PTA_E_ARG, "pta_os_project: C=%d (1..%d) P=%d R=%d", C, PTA_OS_CMAX,
-              P, R);
+  int rw, ct;
+  unsigned ng;
+  const int rc = pta_os_project_choose("pta_os_project", C, P, R, rw, ct, ng);
+  if (rc != PTA_OK) return rc;
   PTA_REQUIRE(ld_y >= (int64_t)P * C && ldw >= 1 && ld_rows >= 1, PTA_E_ARG, "pta_os_project: ld_y=%lld < P*C=%d or ldw / ld_rows < 1",
               (long long)ld_y, P * C);
-  // two 16-realisation tiles per wave when that still leaves every CU a few workgroups (halves the W re-reads); the choice only
-  // regroups realisations, the per-realisation sums are the same
-  const int rw = ((long long)pta_cdiv(R, 128) * P >= 1024) ? 2 : 1;
-  const unsigned ng = pta_cdiv(R, 64 * rw);
-  PTA_REQUIRE(ng <= 0x7fffffffu, PTA_E_ARG, "pta_os_project: R=%d exceeds one launch", R);
   dim3 grid(ng, P), block(256);
   hipStream_t s = pta_stream(stream);
-  const int ct = (C + 15) / 16;
 #define PTA_OS_CASE(CT_)                                                                                                  \
   case CT_:                                                                                                               \
     if (rw == 2)                                                                                                          \

@@ -133,6 +133,37 @@ __global__ __launch_bounds__(256) void k_sky_stat(const double *__restrict__ Q, 
   }
 }
 
+// The launch plan of a sky statistic, the one place it is decided: ks MFMA steps of four pulsars (the k_sky_stat<Stat, ks, mode>
+// instance), rchunk realisations per workgroup, and the grid nst x njb x ngz.  `who` names the entry in the refusals.
+template <class Stat>
+static int pta_sky_stat_choose(const char *who, int P, int J, int R, int S, int &ks, int &rchunk, unsigned &nst, unsigned &njb, unsigned &ngz) {
+  PTA_REQUIRE(P >= 2 && P <= PTA_FSTAT_PMAX && J >= 1 && Stat::QPJ * J <= PTA_FSTAT_CMAX && R > 0 && S >= 1, PTA_E_ARG,
+              "%s: P=%d (2..%d) J=%d (1..%d) R=%d S=%d", who, P, PTA_FSTAT_PMAX, J, PTA_FSTAT_CMAX / Stat::QPJ, R, S);
+  nst = pta_cdiv(S, SKY_ST), njb = pta_cdiv(J, Stat::JB);
+  // realisations per workgroup: enough workgroups to fill the chip, never fewer than 8 realisations per walk (phi and M^-1 are
+  // loaded once per workgroup); the split only regroups realisations
+  long long nz = 4096 / ((long long)nst * njb);
+  if (nz < 1) nz = 1;
+  if (nz > (R + 7) / 8) nz = (R + 7) / 8;
+  if (nz > 65535) nz = 65535;
+  rchunk = (int)((R + nz - 1) / nz);
+  ngz = pta_cdiv(R, rchunk);
+  ks = (P + 3) / 4;  // MFMA steps of four pulsars
+  return PTA_OK;
+}
+
+// plan[0..2] = ks, rchunk, ngz: what the pta_*_plan entry of a sky statistic returns
+template <class Stat>
+static int pta_sky_stat_plan(const char *who, int P, int J, int R, int S, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "%s: NULL argument", who);
+  int ks, rchunk;
+  unsigned nst, njb, ngz;
+  const int rc = pta_sky_stat_choose<Stat>(who, P, J, R, S, ks, rchunk, nst, njb, ngz);
+  if (rc != PTA_OK) return rc;
+  plan[0] = ks, plan[1] = rchunk, plan[2] = (int32_t)ngz;
+  return PTA_OK;
+}
+
 // The output-mode refusals, the grid, the KS = ceil(P / 4) x mode dispatch and the fold of the maxima.  The entry has checked Q, phi,
 // Minv, the sizes and ld_q; `entry` and `map` are its name and the name of its map argument, for the wording.  out != NULL: the full
 // map (and amp); out == NULL: vmax / varg through the workspaces part_val / part_arg [R * J * pta_fstat_fe_tiles(S)].
@@ -154,19 +185,13 @@ static int pta_sky_stat_launch(const char *entry, const char *map, const double 
                   "%s: ld_amp=%lld (even, >= 2*J*S=%lld), amp 16-byte aligned", entry, (long long)ld_amp, (long long)2 * J * S);
     }
   }
-  const unsigned nst = pta_cdiv(S, SKY_ST), njb = pta_cdiv(J, Stat::JB);
-  // realisations per workgroup: enough workgroups to fill the chip, never fewer than 8 realisations per walk (phi and M^-1 are
-  // loaded once per workgroup); the split only regroups realisations
-  long long nz = 4096 / ((long long)nst * njb);
-  if (nz < 1) nz = 1;
-  if (nz > (R + 7) / 8) nz = (R + 7) / 8;
-  if (nz > 65535) nz = 65535;
-  const int rchunk = (int)((R + nz - 1) / nz);
-  const unsigned ngz = pta_cdiv(R, rchunk);
+  int ks, rchunk;
+  unsigned nst, njb, ngz;
+  const int rc = pta_sky_stat_choose<Stat>(entry, P, J, R, S, ks, rchunk, nst, njb, ngz);
+  if (rc != PTA_OK) return rc;
   const int ntile = (int)pta_fstat_fe_tiles(S);
   dim3 grid(nst, njb, ngz), block(256);
   hipStream_t s = pta_stream(stream);
-  const int ks = (P + 3) / 4;  // MFMA steps of four pulsars
 #define PTA_SKY_CASE(KS_)                                                                                                                    \
   case KS_:                                                                                                                                  \
     if (maxmode)                                                                                                                             \

@@ -145,7 +145,7 @@ EX_FLAGS = ("0", "SUBSTITUTION", "VALU", "NO_LOOKAHEAD")
 RAGGED_ORDERS = ((258, 130, 64, 2, 520, 384), (700, 698, 256, 254))
 RAGGED_FLAGS = ("0", "LEFT", "CHAINS3", "NO_LOOKAHEAD")
 FUSED_ORDERS, FUSED_KF = (386, 520), (0, 29, 60, 64)
-ASM_K, ASM_ORDERS = (1, 2, 29, 60, 64), (2, 254, 256, 258, 514)
+ASM_K, ASM_ORDERS = (1, 2, 29, 40, 60, 64), (2, 254, 256, 258, 514)     # K = 40: the walk kernel's 12 k-steps (K = 33 .. 48)
 DRAW_ORDERS, DRAW_R = (1, 2, 17, 256, 257, 513), (1, 5, 70)
 ORF_ORDERS = (1, 2, 17, 80, 81, 130)                    # pta_gwb_orf_factor: the LDS factorisation up to P = 80, the batched one above
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_cases as lc
 from test_bwm_statistic_host import SKY, T0_MJD, dense_bwm, rel
 from test_gpu_fstat import _dense_projectors, _phat
 from test_gpu_os import _engine, _psrs
@@ -66,6 +67,58 @@ def test_bwm_stat_vs_numpy_all_modes(P, J, S, R):
         _lib.call("pta_bwm_stat", ctypes.c_void_p(dQ.data_ptr() + 8 * 5 * P * C), P * C, P, C, J, 4, dv.ptr(dphi), S, dv.ptr(dM), dv.ptr(fb3), J * S, None, 0,
                   None, 0, None, 0, None, None, s)
         assert np.array_equal(fb3.cpu().numpy(), got[5:9, :J * S])
+
+
+def _bwm_launch(dQ, P, C, J, R, dphi, S, dM):
+    """(Fb [R, J S], amplitudes [R, 2 J S], maxima [R, J], argmaxima [R, J]) of pta_bwm_stat: the map with the amplitudes, and the maxima"""
+    from pta_replicator_amd import _lib, device as dv
+    s = dv.stream_ptr()
+    fb, amp = dv.zeros((R, J * S)), dv.zeros((R, 2 * J * S))
+    _lib.call("pta_bwm_stat", dQ, P * C, P, C, J, R, dv.ptr(dphi), S, dv.ptr(dM), dv.ptr(fb), J * S, dv.ptr(amp), 2 * J * S, None, 0, None, 0, None, None, s)
+    nt = int(_lib.lib.pta_fstat_fe_tiles(S))
+    mx, arg = dv.zeros((R, J)), torch.full((R, J), -1, dtype=torch.int32, device=fb.device)
+    pv, pa = dv.empty((R * J * nt,)), torch.empty((R * J * nt,), dtype=torch.int32, device=fb.device)
+    _lib.call("pta_bwm_stat", dQ, P * C, P, C, J, R, dv.ptr(dphi), S, dv.ptr(dM), None, 0, None, 0, dv.ptr(mx), J, dv.ptr(arg), J, dv.ptr(pv), dv.ptr(pa), s)
+    return fb, amp, mx, arg
+
+
+def _bwm_case(P, J, S, R, windows, what):
+    """the map, the amplitudes and the maxima against bwm_from_Q (the file's 1e-12; the maxima against the map bit for bit); then the
+    realisations of each window (first, count) in a launch of their own, which one workgroup walks: bit for bit the large launch's"""
+    from pta_replicator_amd import bwm_statistic as bst, device as dv
+    Q, phi, Minv, C = _operands(P, J, S, R, P + J + S)
+    dQ, dphi, dM = dv.f64(Q.reshape(R, -1)), dv.f64(phi), dv.f64(_packed(Minv))
+    ref_f, ref_a = bst.bwm_from_Q(phi, Minv, Q[:, :, :J])
+    fb, amp, mx, arg = _bwm_launch(dv.ptr(dQ), P, C, J, R, dphi, S, dM)
+    full = fb.cpu().numpy().reshape(R, J, S)
+    err, err_a = rel(full, ref_f), rel(amp.cpu().numpy().reshape(R, J, S, 2), ref_a)
+    print(f"pta_bwm_stat {what} P={P} J={J} S={S} R={R}: Fb rel = {err:.2e}, A rel = {err_a:.2e}, error / bound {max(err, err_a) / 1e-12:.4f}")
+    assert err < 1e-12 and err_a < 1e-12
+    assert np.array_equal(mx.cpu().numpy(), full.max(axis=2))
+    assert np.array_equal(arg.cpu().numpy(), full.argmax(axis=2))        # NumPy's argmax is the first = lowest index
+    for lo, n in windows:
+        assert lc.plan("pta_bwm_stat", P, J, n, S)["ngz"] == 1
+        sub = _bwm_launch(dv.row_ptr(dQ, lo), P, C, J, n, dphi, S, dM)
+        assert all(torch.equal(x, y[lo:lo + n]) for x, y in zip(sub, (fb, amp, mx, arg))), (lo, n)
+
+
+@pytest.mark.parametrize("shape", lc.SKY_CHUNK["pta_bwm_stat"], ids=lambda c: f"rchunk{c['rchunk']}")
+def test_bwm_stat_realisation_chunks(shape):
+    """rchunk, the realisations one workgroup of k_sky_stat walks: 9 (a sky grid of more than 512 workgroups: the chunk is no multiple
+    of the 4 realisations that share a scan of the maxima, so the flush ends a chunk part-way), 8, and all of 7 realisations in one
+    workgroup.  Measured on one MI355X: worst relative error 4.0e-16 (Fb), 2.3e-16 (A), error / bound 0.0004."""
+    P, J, S, R = (shape[k] for k in "PJSR")
+    assert lc.plan("pta_bwm_stat", P, J, R, S)["rchunk"] == shape["rchunk"]
+    _bwm_case(P, J, S, R, shape["windows"], f"rchunk={shape['rchunk']}")
+
+
+@pytest.mark.parametrize("P", lc.SKY_KS_P)
+def test_bwm_stat_every_pulsar_step_count(P):
+    """k_sky_stat<bwm_stat, KS, mode> for every KS = ceil(P / 4) = 1 .. 32 in both modes (the other tests reach six of them), full steps
+    (P = 4 k) and steps of one pulsar (P = 4 k + 1).  Measured on one MI355X: worst relative error 9.4e-16 (Fb), 6.8e-16 (A), error / bound 0.0009."""
+    J, S, R = (lc.SKY_KS_SHAPE[k] for k in "JSR")
+    assert lc.plan("pta_bwm_stat", P, J, R, S)["ks"] == (P + 3) // 4
+    _bwm_case(P, J, S, R, ((R - 1, 1),), f"ks={(P + 3) // 4}")
 
 
 def test_bwm_stat_ties_take_the_lowest_index():

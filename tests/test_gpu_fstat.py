@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_cases as lc
 from oracle import pta_oracle as po
 from test_gpu_os import _engine, _psrs
 
@@ -49,12 +50,14 @@ def test_fstat_project_vs_numpy(C, R):
         assert np.array_equal(Q2.cpu().numpy(), got[13:16, :P * C])
 
 
-@pytest.mark.parametrize("P, C", [(64, 512), (33, 512), (256, 64), (256, 30)])
+@pytest.mark.parametrize("P, C", lc.FSTAT_PROJECT_LARGE)
 def test_fstat_project_large_launch_tiles(P, C):
     """launches large enough for the wider tiles (128 x 128, 64 x 128, 128 x 64, 128 x 32 at R = 1000: the tile follows the number of
     workgroups, pta_fstat_kernels.hip), and the same realisations in a launch of 3, which takes the smallest: bit for bit the same"""
     from pta_replicator_amd import _lib, device as dv
-    R = 1000
+    R = lc.FSTAT_PROJECT_R
+    tile = lc.plan("pta_fstat_project", C, P, R)
+    assert (tile["bm"], tile["bn"]) == lc.FSTAT_PROJECT_TILES[P, C] and lc.plan("pta_fstat_project", C, P, 3)["bm"] == 64
     rng = np.random.default_rng(P * 1000 + C)
     counts = rng.integers(1, 41, P)
     off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -126,6 +129,63 @@ def test_fstat_fe_vs_numpy_both_modes(P, J, S, R):
         _lib.call("pta_fstat_fe", ctypes.c_void_p(dQ.data_ptr() + 8 * 5 * P * 2 * J), P * 2 * J, P, J, 4, dv.ptr(dphi), S, dv.ptr(dM), dv.ptr(fe2), J * S,
                   None, 0, None, 0, None, None, s)
         assert np.array_equal(fe2.cpu().numpy(), got[5:9, :J * S])
+
+
+def _fe_launch(dQ, ld_q, P, J, R, dphi, S, dM):
+    """(Fe [R, J S], maxima [R, J], argmaxima [R, J]) of pta_fstat_fe in its two output modes"""
+    from pta_replicator_amd import _lib, device as dv
+    s = dv.stream_ptr()
+    fe = dv.zeros((R, J * S))
+    _lib.call("pta_fstat_fe", dQ, ld_q, P, J, R, dv.ptr(dphi), S, dv.ptr(dM), dv.ptr(fe), J * S, None, 0, None, 0, None, None, s)
+    nt = int(_lib.lib.pta_fstat_fe_tiles(S))
+    mx, arg = dv.zeros((R, J)), torch.full((R, J), -1, dtype=torch.int32, device=fe.device)
+    pv, pa = dv.empty((R * J * nt,)), torch.empty((R * J * nt,), dtype=torch.int32, device=fe.device)
+    _lib.call("pta_fstat_fe", dQ, ld_q, P, J, R, dv.ptr(dphi), S, dv.ptr(dM), None, 0, dv.ptr(mx), J, dv.ptr(arg), J, dv.ptr(pv), dv.ptr(pa), s)
+    return fe, mx, arg
+
+
+def _fe_case(P, J, S, R, windows, what, ref_rows=None):
+    """both modes against fe_from_Q (the file's 1e-12; of the realisations ref_rows where the host evaluation of all would take many
+    seconds) and the maxima against the map bit for bit; then the realisations of each window (first, count) in a launch of their
+    own, which one workgroup walks: bit for bit the large launch's, in both modes"""
+    from pta_replicator_amd import device as dv, f_statistic as fst
+    Q, phi, Minv, _ = _fe_operands(P, J, S, R, P + J + S)
+    dQ, dphi, dM = dv.f64(Q.reshape(R, -1)), dv.f64(phi), dv.f64(Minv[..., fst.TRI_I, fst.TRI_J])
+    fe, mx, arg = _fe_launch(dv.ptr(dQ), P * 2 * J, P, J, R, dphi, S, dM)
+    full = fe.cpu().numpy().reshape(R, J, S)
+    rr = np.arange(R) if ref_rows is None else np.asarray(ref_rows)
+    err = _rel(full[rr], fst.fe_from_Q(phi, Minv, Q[rr]))
+    print(f"pta_fstat_fe {what} P={P} J={J} S={S} R={R}: rel = {err:.2e}, error / bound {err / 1e-12:.4f}")
+    assert err < 1e-12
+    assert np.array_equal(mx.cpu().numpy(), full.max(axis=2))            # bit for bit the map's maxima
+    assert np.array_equal(arg.cpu().numpy(), full.argmax(axis=2))        # NumPy's argmax is the first = lowest index
+    for lo, n in windows:
+        assert lc.plan("pta_fstat_fe", P, J, n, S)["ngz"] == 1
+        fe2, mx2, arg2 = _fe_launch(dv.row_ptr(dQ, lo), P * 2 * J, P, J, n, dphi, S, dM)
+        assert torch.equal(fe2, fe[lo:lo + n]) and torch.equal(mx2, mx[lo:lo + n]) and torch.equal(arg2, arg[lo:lo + n]), (lo, n)
+
+
+@pytest.mark.parametrize("shape", lc.SKY_CHUNK["pta_fstat_fe"], ids=lambda c: f"rchunk{c['rchunk']}")
+def test_fstat_fe_realisation_chunks(shape):
+    """rchunk, the realisations one workgroup of k_sky_stat walks: 9 (a sky grid of more than 512 workgroups: the chunk is no multiple
+    of the 8 realisations that share a scan of the maxima, so the flush ends a chunk part-way), 8, and all of 7 realisations in one
+    workgroup.  Measured on one MI355X: worst relative error 4.8e-16, error / bound 0.0005."""
+    P, J, S, R = (shape[k] for k in "PJSR")
+    assert lc.plan("pta_fstat_fe", P, J, R, S)["rchunk"] == shape["rchunk"]
+    ref_rows = None
+    if R * J * S > 1 << 22:   # the host map of 13 M cells takes 5 s: the first two, a middle and the last two chunks whole, and every 7th
+        c = shape["rchunk"]   # realisation (7 is coprime to the chunk and to the scan: every slot of both is met)
+        ref_rows = sorted(set(range(2 * c)) | set(range(16 * c, 17 * c)) | set(range((R - 1) // c * c - c, R)) | set(range(0, R, 7)))
+    _fe_case(P, J, S, R, shape["windows"], f"rchunk={shape['rchunk']}", ref_rows)
+
+
+@pytest.mark.parametrize("P", lc.SKY_KS_P)
+def test_fstat_fe_every_pulsar_step_count(P):
+    """k_sky_stat<fe_stat, KS, mode> for every KS = ceil(P / 4) = 1 .. 32 in both modes (the other tests reach six of them), full steps
+    (P = 4 k) and steps of one pulsar (P = 4 k + 1).  Measured on one MI355X: worst relative error 8.9e-16, error / bound 0.0009."""
+    J, S, R = (lc.SKY_KS_SHAPE[k] for k in "JSR")
+    assert lc.plan("pta_fstat_fe", P, J, R, S)["ks"] == (P + 3) // 4
+    _fe_case(P, J, S, R, ((R - 1, 1),), f"ks={(P + 3) // 4}")
 
 
 def test_fstat_fe_ties_take_the_lowest_index():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_cases as lc
 from helpers import load
 from oracle import pta_oracle as po
 
@@ -118,6 +119,48 @@ def test_mix_batched_vs_numpy(P, npts, variant):
         _lib.call("pta_gwb_mix_batched", ctypes.c_void_p(d_M.data_ptr() + 8 * 3 * ld_m), ld_m, P, ctypes.c_void_p(d_G0.data_ptr() + 8 * 3 * P * ldg),
                   2, npts, ldg, dv.ptr(G1), 0, dv.stream_ptr())
         assert np.array_equal(G1.cpu().numpy()[:, :, :npts], got[3:, :, :npts])
+
+
+@pytest.mark.parametrize("P", lc.MIX_P)
+def test_mix_batched_tiles_per_workgroup(P):
+    """tpw, the 64-sample tiles one workgroup of k_gwb_mix_batched walks with its staged factor: 4 below 512 realisations (at 5 tiles the
+    second workgroup takes tile 4 and leaves its loop at tile 5) and all 5 from 512 on, which no test had against a reference.
+    Value: the device result is one fp64 FMA chain over the P pulsars, so |got - ref| <= (P + 2) 2^-53 sum |m||g0| against a long-double
+    reference, taken for nine realisations spread over the batch; every realisation is held to twice that against the fp64 product
+    of NumPy, whose own error has the same bound.  Bit-identity: R = 511 against the first 511 of R = 512, and the last realisations
+    again in a launch of 3.  Measured on one MI355X: worst error / bound 0.38 (long double, P = 3; 0.06 at P = 80), 0.11 (fp64, all realisations)."""
+    from pta_replicator_amd import _lib, device as dv
+    npts, Rm = lc.MIX_NPTS, max(lc.MIX_R)
+    ldg, ld_m = npts + 3, P * P + 5
+    rng = np.random.default_rng(1000 * P + npts)
+    M, G0 = rng.normal(size=(Rm, ld_m)), rng.normal(size=(Rm, P, ldg))
+    Mr = M[:, :P * P].reshape(Rm, P, P)
+    ref = Mr @ G0[:, :, :npts]
+    scale = np.abs(Mr) @ np.abs(G0[:, :, :npts])
+    pick = [0, 1, 127, 255, 256, 509, 510, 511, 300]
+    ref_ld = np.stack([Mr[r].astype(np.longdouble) @ G0[r, :, :npts].astype(np.longdouble) for r in pick])
+    d_M, d_G0 = dv.f64(M), dv.f64(G0)
+    out = {}
+    for R in lc.MIX_R:
+        plan = lc.plan("pta_gwb_mix_batched", P, R, npts, 0)
+        assert plan["tpw"] == (5 if R >= 512 else 4) and plan["grid_x"] == (1 if R >= 512 else 2)
+        G = dv.f64(np.full((R, P, ldg), np.nan))             # a NaN slab: what the kernel does not write stays NaN
+        _lib.call("pta_gwb_mix_batched", dv.ptr(d_M), ld_m, P, dv.ptr(d_G0), R, npts, ldg, dv.ptr(G), 0, dv.stream_ptr())
+        got = G.cpu().numpy()
+        sel = [i for i, r in enumerate(pick) if r < R]
+        rr = [pick[i] for i in sel]
+        r_ld = float(np.max(np.abs(got[rr, :, :npts] - ref_ld[sel]) / ((P + 2) * 2.0 ** -53 * scale[rr])))
+        r_64 = float(np.max(np.abs(got[:, :, :npts] - ref[:R]) / (2 * (P + 2) * 2.0 ** -53 * scale[:R])))
+        print(f"pta_gwb_mix_batched P={P} R={R} tpw={plan['tpw']}: worst error / bound {r_ld:.3f} (long double), {r_64:.3f} (fp64, all realisations)")
+        assert r_ld <= 1.0 and r_64 <= 1.0
+        assert np.all(np.isnan(got[:, :, npts:]))            # padding columns untouched
+        out[R] = G
+    assert torch.equal(out[511][:, :, :npts], out[512][:511, :, :npts])
+    n = lc.MIX_SMALL_R
+    assert lc.plan("pta_gwb_mix_batched", P, n, npts, 0)["tpw"] == 4
+    G1 = dv.f64(np.full((n, P, ldg), np.nan))
+    _lib.call("pta_gwb_mix_batched", dv.row_ptr(d_M, Rm - n), ld_m, P, dv.row_ptr(d_G0, Rm - n), n, npts, ldg, dv.ptr(G1), 0, dv.stream_ptr())
+    assert torch.equal(G1[:, :, :npts], out[512][Rm - n:, :, :npts])
 
 
 # ---------------------------------------------------------------- engines ----------------------------------------------------

@@ -40,7 +40,7 @@ def _check(gpu, P, npts, R, rng):
     return M, G0_d, new
 
 
-@pytest.mark.parametrize("P", [1, 3, 16, 17, 68, 80])
+@pytest.mark.parametrize("P", [1, 3, 16, 17, 40, 49, 68, 80])      # 40, 49: three and four pulsar tiles, which no other size reaches
 def test_stream_equals_small_and_numpy(gpu, P):
     """Every npts in {1, 63, 64, 65, 600} x R in {1, 4, 5, 9} with ldg = npts + 3: fewer items than waves, ragged last chunk, one
     to five pulsar tiles, whole and partial last K-steps."""

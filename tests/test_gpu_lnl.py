@@ -10,13 +10,16 @@ Every such test checks delta < 1e-8 itself.  At 68 x 5000 delta also takes the d
 likelihood of three of the pulsars: the two host forms share one projection q = V r and one r^T P0' r.
 
 Measured on one MI355X (worst |d ln L| / scale, device against host): kernels 1.7e-15 (K = 2 .. 128; pta_lnl_quad 5.9e-16 of r0), engines
-with 16 pulsars 4.5e-15 with a timing model and 1.6e-13 without (delta 6.2e-14), 68 x 5000 1.1e-14 (host against dense there: 5.7e-13)."""
+with 16 pulsars 4.5e-15 with a timing model and 1.6e-13 without (delta 6.2e-14), 68 x 5000 1.1e-14 (host against dense there: 5.7e-13);
+pta_lnl_apply with 2, 3 and 16 grid points per workgroup 1.6e-15 (delta 9.7e-16), with KT = 3, 4, 5, 7 blocks 1.4e-16 (the shapes of
+tests/launch_cases.py, which the plan query holds to those instances)."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
+import launch_cases as lc
 from pta_replicator_amd import optimal_statistic as ost
 from test_gpu_os import _engine as _engine_all_rn, _psrs
 from test_lnl_host import NF, _array, _M, _q_blocked, _rn_basis, _rows
@@ -97,7 +100,7 @@ def _device_lnl(A, b, q, r0, s, c, blk, C=2):
 
 @pytest.mark.parametrize("G", [1, 5, 64])
 @pytest.mark.parametrize("R", [1, 17, 1000])
-@pytest.mark.parametrize("K", [2, 29, 88, 128])
+@pytest.mark.parametrize("K", lc.LNL_K_FIRST)
 def test_factor_apply_vs_numpy(K, R, G):
     A, b, q, r0, s, c = _problem(K, R, G)
     P = A.shape[0]
@@ -123,6 +126,54 @@ def test_factor_apply_vs_numpy(K, R, G):
     if R >= 17 and G >= 5:   # a (realisation, grid point) value does not depend on the rows or grid points that share its launch
         sub = _device_lnl(A, b[2:5], q[13:16], r0[13:16], s, c, blk)
         assert torch.equal(sub[2], lp[2:5, :, 13:16]) and torch.equal(sub[3], tot[2:5, 13:16])
+
+
+def _apply_vs_numpy(P, K, G, R, blk, what):
+    """pta_lnl_factor / pta_lnl_apply / pta_lnl_reduce on _problem(K, R, G, P) under the file's bound; returns the inputs and the outputs"""
+    inp = _problem(K, R, G, P=P)
+    A, b, q, r0, s, c = inp
+    out = _device_lnl(A, b, q, r0, s, c, blk)
+    ref = np.stack([ost.lnl_solve(A[a], b[:, a], q[:, a, :K], r0[:, a], s[a], c[a]) for a in range(P)], axis=1)                   # [R, P, G]
+    alt = np.stack([ost.lnl_solve(A[a], b[:, a], q[:, a, :K], r0[:, a], s[a], c[a], form="solve") for a in range(P)], axis=1)
+    scale = np.abs(ref) + (r0 / s[None, :])[:, :, None]
+    delta = float(np.max(np.abs(alt - ref) / scale))
+    got = out[2].permute(2, 1, 0).cpu().numpy()
+    err = float(np.max(np.abs(got - ref) / scale))
+    print(f"{what} P={P} K={K} G={G} R={R}: delta {delta:.3e}, device {err:.3e}, error / bound {err / _bound(delta):.3f}")
+    assert np.all(np.isfinite(got)) and err < _bound(delta)
+    acc = torch.zeros_like(out[3])
+    for a in range(P):                               # the fixed-order pulsar sum
+        acc = acc + out[2][:, a]
+    assert torch.equal(acc, out[3])
+    return inp, out
+
+
+@pytest.mark.parametrize("shape", lc.LNL_GROUPS, ids=lambda c: f"g_per{c['g_per']}")
+def test_apply_several_grid_points_per_workgroup(shape):
+    """g_per = 2, 3 and 16 grid points per workgroup of pta_lnl_apply (from G P cdiv(R, 128) >= 8192 on): the second and later trips of
+    the kernel's loop over grid points, with their barrier and the restaging of the operator in LDS, and the short last group (1 of 3,
+    3 of 16).  Value: the file's bound.  Bit-identity: a few grid points, those of the short last group among them, and a few
+    realisations, the last of the partial tile among them, in a launch of their own with one grid point per workgroup (the plan query
+    confirms both).  Measured on one MI355X: worst |d ln L| / scale 1.6e-15 (g_per = 16; delta 9.7e-16), error / bound 0.002."""
+    P, K, G, R = (shape[k] for k in "PKGR")
+    assert lc.plan("pta_lnl_apply", P, K, G, R)["g_per"] == shape["g_per"] > 1
+    blk = 64 if R > 1 else K + 3                     # the blocked q layout of the engine, and the plain one
+    (A, b, q, r0, s, c), (_, _, lp, tot) = _apply_vs_numpy(P, K, G, R, blk, f"g_per={shape['g_per']}")
+    gi, ri = list(shape["sub_g"]), list(shape["sub_r"])
+    assert lc.plan("pta_lnl_apply", P, K, len(gi), len(ri))["g_per"] == 1
+    sub = _device_lnl(A, b[gi], q[ri], r0[ri], s, c, blk)
+    assert torch.equal(sub[2], lp[gi][:, :, ri]) and torch.equal(sub[3], tot[gi][:, ri])
+
+
+@pytest.mark.parametrize("K", lc.LNL_K_MORE)
+def test_apply_every_block_count(K):
+    """k_lnl_apply<KT> for KT = 3, 4, 5 and 7 (test_factor_apply_vs_numpy has 1, 2, 6, 8), with K a multiple of 16, one past it and
+    neither.  Measured on one MI355X: worst |d ln L| / scale 1.4e-16 (delta 1.8e-16), error / bound 0.0001."""
+    P, G, R = (lc.LNL_KT_SHAPE[k] for k in "PGR")
+    assert lc.plan("pta_lnl_apply", P, K, G, R) == {"kt": (K + 15) // 16, "g_per": 1, "gz": G}
+    (A, b, q, r0, s, c), (_, _, lp, tot) = _apply_vs_numpy(P, K, G, R, 64, f"kt={(K + 15) // 16}")
+    sub = _device_lnl(A, b[2:5], q[13:16], r0[13:16], s, c, 64)
+    assert torch.equal(sub[2], lp[2:5, :, 13:16]) and torch.equal(sub[3], tot[2:5, 13:16])
 
 
 def test_lnl_kernels_refuse_bad_arguments():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_cases as lc
 from oracle import pta_oracle as po
 
 pytestmark = pytest.mark.gpu
@@ -41,6 +42,59 @@ def test_os_project_vs_numpy(C, R):
         _lib.call("pta_os_project", dv.ptr(dW), N, C, dv.ptr(doff), P, ctypes.c_void_p(drows.data_ptr() + 8 * 13 * ld_rows), ld_rows, 3,
                   dv.ptr(Y2), P * C, dv.stream_ptr())
         assert np.array_equal(Y2.cpu().numpy(), got[13:16, :P * C])
+
+
+_OS_LARGE = {}
+
+
+def _os_large():
+    """the 1024 ragged pulsars of tests/launch_cases.py at the largest R and C of its cases, on the host and on the device, with the
+    long-double reference and sum |w||r| of every (realisation, pulsar, column): made once, every case reads a corner of it"""
+    if not _OS_LARGE:
+        from pta_replicator_amd import device as dv
+        counts = lc.os_counts()
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        N, P, Rm, Cm = int(off[-1]), len(counts), max(lc.OS_R), max(lc.OS_C)
+        rng = np.random.default_rng(1024)
+        ld_rows = (N + 3) | 1                             # a row stride wider than the row, odd
+        W, rows = rng.normal(size=(Cm, N)), rng.normal(size=(Rm, ld_rows))
+        ref, scale = np.empty((Rm, P, Cm), dtype=np.longdouble), np.empty((Rm, P, Cm))
+        Wl, rl = W.astype(np.longdouble), rows.astype(np.longdouble)
+        for a in range(P):
+            ref[:, a] = rl[:, off[a]:off[a + 1]] @ Wl[:, off[a]:off[a + 1]].T
+            scale[:, a] = np.abs(rows[:, off[a]:off[a + 1]]) @ np.abs(W[:, off[a]:off[a + 1]]).T
+        _OS_LARGE.update(counts=counts, off=off, N=N, P=P, ld_rows=ld_rows, ref=ref, scale=scale, dW=dv.f64(W), drows=dv.f64(rows), doff=dv.i32(off))
+    return _OS_LARGE
+
+
+@pytest.mark.parametrize("C", lc.OS_C)
+@pytest.mark.parametrize("R", lc.OS_R)
+def test_os_project_two_tiles_per_wave(C, R):
+    """k_os_project<CT, 2>, which the launcher takes from cdiv(R, 128) * P >= 1024 on: 1024 ragged pulsars of 1 .. 40 TOAs, five of
+    65 .. 301 (the prefetch of the next K chunk with two tiles in flight).  Value: the device result is one fp64 FMA chain over the n
+    TOAs of the pulsar, so |got - ref| <= (n + 2) 2^-53 sum |w||r| against the long-double reference.  Bit-identity: the first and the
+    last realisations again, over a window of 8 pulsars, in launches that take one tile per wave (the plan query confirms both).
+    Measured on one MI355X: worst error / bound 0.51 (12 cases; 0.32 at C = 2, R = 1)."""
+    from pta_replicator_amd import _lib, device as dv
+    d = _os_large()
+    P, N, ld_rows = d["P"], d["N"], d["ld_rows"]
+    assert lc.plan("pta_os_project", C, P, R) == {"rw": 2, "ct": (C + 15) // 16, "grid_x": (R + 127) // 128}
+    ld_y = P * C + 2
+    Y = dv.zeros((R, ld_y))
+    _lib.call("pta_os_project", dv.ptr(d["dW"]), N, C, dv.ptr(d["doff"]), P, dv.ptr(d["drows"]), ld_rows, R, dv.ptr(Y), ld_y, dv.stream_ptr())
+    got = Y.cpu().numpy()
+    bound = (d["counts"] + 2.0)[None, :, None] * 2.0 ** -53 * d["scale"][:R, :, :C]
+    ratio = float(np.max(np.abs(got[:, :P * C].reshape(R, P, C) - d["ref"][:R, :, :C]) / bound))
+    print(f"pta_os_project rw=2 C={C} R={R}: worst error / ((n + 2) 2^-53 sum |w||r|) = {ratio:.3f}")
+    assert ratio <= 1.0
+    assert np.all(got[:, P * C:] == 0)                # nothing written past P * C
+    a0, pw = lc.OS_WINDOW
+    for lo, n in lc.os_windows(R):
+        assert lc.plan("pta_os_project", C, pw, n)["rw"] == 1
+        Y2 = dv.zeros((n, pw * C))
+        _lib.call("pta_os_project", dv.ptr(d["dW"]), N, C, ctypes.c_void_p(d["doff"].data_ptr() + 4 * a0), pw, dv.row_ptr(d["drows"], lo), ld_rows, n,
+                  dv.ptr(Y2), pw * C, dv.stream_ptr())
+        assert torch.equal(Y2, Y[lo:lo + n, a0 * C:(a0 + pw) * C]), (lo, n)
 
 
 @pytest.mark.parametrize("with_rho", [False, True])

@@ -138,6 +138,20 @@ def test_workspace_scheme_256_column_panels(gpu, n, sched, B):
     _check("ws", mats, Ls, info, 128, lambda m: tr.panels_uniform(m, 256))
 
 
+@pytest.mark.parametrize("sched", ["LEFT", "0"])
+def test_workspace_scheme_default_chains(gpu, sched):
+    """eight matrices and no PTA_POTRF_CHAINS: the default is two chains from B = 8 on and one below (pta_potrf_impl), which the other
+    batches (1, 3, 5) and the explicit CHAINS schedules never take.  Inside bound (w), and bit for bit what one chain returns: the
+    chains only divide the matrices among streams."""
+    lib = gpu["lib"]
+    mats = _batch(258, 8)
+    fl = tc.flag_bits(lib, sched) | lib.POTRF_NB(1)
+    Ls, info = _uniform(gpu, mats, fl)
+    _check("ws", mats, Ls, info, 128, lambda m: tr.panels_uniform(m, 256))
+    L1, info1 = _uniform(gpu, mats, fl | lib.POTRF_CHAINS(1))
+    assert not info1.any() and all(np.array_equal(x, y) for x, y in zip(Ls, L1))
+
+
 @pytest.mark.parametrize("n,sched", tc.WIDE_CASES)
 def test_workspace_scheme_default_panels(gpu, n, sched):
     """the default 1024-column panels just above one panel: a first panel of 1026 columns and of 1034 + 256; one matrix per case"""
