@@ -54,7 +54,9 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * EQUAD and log10 ECORR, pair j = white-noise / ECORR group j; pta_hyper_uniform_field),
  * 8 CW (pulsar field 0: per-realisation CW source labels, pair j = label column, uniform u2; pta_cw_uniform.  In a catalogue the
  * field is the source index s, pta_cw_catalog_uniform),
- * 9 BWM (pulsar field 0: per-realisation burst-with-memory labels, pair j = label column, uniform u2; pta_bwm_uniform). */
+ * 9 BWM (pulsar field 0: per-realisation burst-with-memory labels, pair j = label column, uniform u2; pta_bwm_uniform),
+ * 13 BURST (field 0: the sky labels of a per-realisation wavelet burst, field 1 + w: wavelet w; pair j = label column; pta_burst_uniform),
+ * 14 NT (field v: noise transient v of the realisation, pair j = label column; pta_transient_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -1127,6 +1129,76 @@ int pta_gwb_mix_batched_plan(int P, int R, int npts, int variant, int32_t *plan)
 int pta_fstat_fe_plan(int P, int J, int R, int S, int32_t *plan);
 int pta_bwm_stat_plan(int P, int J, int R, int S, int32_t *plan);
 int pta_tm_project_plan(int m, int P, int R, int32_t *plan);
+
+/* ---------------------------------------------------------------- sine-Gaussian wavelets per realisation (ABI 8, additive) */
+/* The reference's add_burst / add_noise_transient (deterministic.py:718-819) with the callables taken from one family,
+ *     wavelet(t) = exp(-1/2 ((t - t0) / tau)^2) cos(2 pi f (t - t0) + phi),   t = mjd * 86400, t0 = t0_mjd * 86400
+ * (formulas and the folded form: csrc/pta_burst.h).  Stream kinds 13 (burst: field 0 the sky row, field 1 + w wavelet w) and 14
+ * (transients: field v), pair = label column, uniform u2.
+ * Burst labels: sky[r * 3 + j], j: 0 cos_gwtheta, 1 gwphi, 2 psi; wavelets src[(r * W + w) * 7 + j], j: 0 t0_mjd, 1 log10_tau [s],
+ * 2 log10_f [Hz], 3 log10_a_plus [s], 4 phase_plus, 5 log10_a_cross [s], 6 phase_cross.
+ * Transient labels: src[(r * V + v) * 6 + j], j: 0 psr (an integer 0 .. P-1 held as a double), 1 t0_mjd, 2 log10_tau, 3 log10_f,
+ * 4 log10_a [s], 5 phase.                                                                                                          */
+#define PTA_BURST_NSKY 3
+#define PTA_BURST_NCOL 7
+#define PTA_NT_NCOL 6
+#define PTA_BURST_WMAX 128
+
+/* sky[R x 3] and wav[R x W x 7] drawn from the boxes lo / hi: device [10], the three sky columns first, then the seven wavelet
+ * columns (every wavelet of a realisation from the same boxes).  1 <= W <= PTA_BURST_WMAX.                                        */
+int pta_burst_uniform(uint64_t seed, uint64_t r0, int R, int W, const double *lo, const double *hi, double *sky, double *wav, void *stream);
+
+/* out[R x V x 6] drawn from the boxes lo / hi: device [6]; the caller gives column 0 the box (0, P) and the entry floors it (and keeps
+ * it <= P - 1).  1 <= V <= PTA_BURST_WMAX.                                                                                        */
+int pta_transient_uniform(uint64_t seed, uint64_t r0, int R, int V, int P, const double *lo, const double *hi, double *out, void *stream);
+
+/* The burst of every realisation of a batch.  Device pointers.                                                                    */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_wav;              /* W, 1 .. PTA_BURST_WMAX */
+  const double *phat;         /* [n_psr x 3] pulsar unit vectors (ptheta = pi/2 - dec, pphi = ra) */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *sky;          /* [R x 3] sky rows of realisation r0 + r */
+  const double *src;          /* [R x W x 7] wavelet rows */
+  const int32_t *count;       /* [R] wavelets in use, 0 .. W (clamped), or NULL = W; rows past the count are never read */
+  double *wav;                /* [R x W x 7] (t0_s, -1/2 / tau^2, f, A+ cos phi+, A+ sin phi+, Ax cos phix, Ax sin phix), written by
+                                 pta_engine_burst_params */
+  double *kk;                 /* [R x n_psr x 2] (k+, kx), written by pta_engine_burst_params */
+  const int32_t *psr_off;     /* remove_quad: [n_psr + 1] first TOA of every pulsar; else NULL */
+  const double *quad_q;       /* remove_quad: [n_toa x 3] orthonormal basis of (1, t, t^2) over every pulsar's TOAs; else NULL */
+  double *quad_c;             /* remove_quad: [R x n_psr x 3] = Q_a^T term, written by pta_engine_burst_quad */
+} pta_burst_engine;
+
+/* wav and kk from sky / src: one thread per wavelet row and per (r, a).                                                           */
+int pta_engine_burst_params(const pta_burst_engine *burst_host, int R, void *stream);
+
+/* quad_c[r, a, :] = sum_i quad_q[i, :] term_r(t_i) over the TOAs of pulsar a (0 for a pulsar of <= 3 TOAs): a workgroup per (a, r),
+ * every lane summing its TOAs in ascending order, then a binary tree over the lanes.  No atomics.  R <= 65535.                     */
+int pta_engine_burst_quad(const pta_burst_engine *burst_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum_{w < count[r]} g_w (C_raw cos + S_raw sin)(toa_s[i]) over the plan's TOA tiles (as pta_engine_bwm_add
+ * reads the plan), wavelets in ascending order in a register, one read-modify-write.  With quad_q != NULL the entry first runs
+ * pta_engine_burst_quad and the element is the term minus quad_q[i, :] . quad_c[r, a, :] (0 for a pulsar of <= 3 TOAs).  accumulate = 1
+ * leaves the rows of realisations without a wavelet untouched.  No atomics.                                                       */
+int pta_engine_burst_add(const pta_engine_plan *plan_host, const pta_burst_engine *burst_host, int R, double *out, int64_t ld_out,
+                         int accumulate, void *stream);
+
+/* The noise transients of every realisation of a batch.  Device pointers.                                                         */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_wav;              /* V, 1 .. PTA_BURST_WMAX */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *src;          /* [R x V x 6] transient rows of realisation r0 + r */
+  const int32_t *count;       /* [R] transients in use, 0 .. V (clamped), or NULL = V; rows past the count are never read */
+  double *tab;                /* [R x V x 6] (psr, t0_s, -1/2 / tau^2, f, A cos phi, -A sin phi), written by pta_engine_transient_params */
+} pta_transient_engine;
+
+int pta_engine_transient_params(const pta_transient_engine *nt_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum over the transients v < count[r] whose psr is the pulsar of TOA i, in ascending v; otherwise as
+ * pta_engine_burst_add.                                                                                                           */
+int pta_engine_transient_add(const pta_engine_plan *plan_host, const pta_transient_engine *nt_host, int R, double *out, int64_t ld_out,
+                             int accumulate, void *stream);
 
 #ifdef __cplusplus
 }

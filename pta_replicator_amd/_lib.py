@@ -94,6 +94,21 @@ class BwmEngine(ctypes.Structure):
     ]
 
 
+class BurstEngine(ctypes.Structure):
+    """pta_burst_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_wav", c_int32), ("phat", _P), ("toa_s", _P), ("sky", _P), ("src", _P), ("count", _P), ("wav", _P),
+        ("kk", _P), ("psr_off", _P), ("quad_q", _P), ("quad_c", _P),
+    ]
+
+
+class TransientEngine(ctypes.Structure):
+    """pta_transient_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_wav", c_int32), ("toa_s", _P), ("src", _P), ("count", _P), ("tab", _P),
+    ]
+
+
 class WnHyper(ctypes.Structure):
     """pta_engine_wn_hyper (include/pta_replicator_amd.h)."""
     _fields_ = [
@@ -193,6 +208,13 @@ _SIGNATURES = {
     "pta_bwm_uniform": (c_int, [c_uint64, c_uint64, c_int, _P, _P, _P, _P]),
     "pta_engine_bwm_params": (c_int, [POINTER(BwmEngine), c_int, _P]),
     "pta_engine_bwm_add": (c_int, [POINTER(EnginePlan), POINTER(BwmEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_burst_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, _P, _P, _P, _P, _P]),
+    "pta_transient_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pta_engine_burst_params": (c_int, [POINTER(BurstEngine), c_int, _P]),
+    "pta_engine_burst_quad": (c_int, [POINTER(BurstEngine), c_int, _P]),
+    "pta_engine_burst_add": (c_int, [POINTER(EnginePlan), POINTER(BurstEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_engine_transient_params": (c_int, [POINTER(TransientEngine), c_int, _P]),
+    "pta_engine_transient_add": (c_int, [POINTER(EnginePlan), POINTER(TransientEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_wn_params": (c_int, [POINTER(WnHyper), c_int, _P]),
     "pta_engine_wn_add": (c_int, [POINTER(EnginePlan), POINTER(WnHyper), c_uint64, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "pta_engine_chrom_coef": (c_int, [POINTER(ChromEngine), c_uint64, c_uint64, c_int, _P]),

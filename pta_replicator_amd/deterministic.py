@@ -299,6 +299,23 @@ def add_noise_transient(psr, waveform, tref=0, signal_name="noise_transient"):
     _record(psr, signal_name, {"waveform": waveform, "tref": tref}, waveform(toas))
 
 
+def add_wavelet_burst(psr, gwtheta, gwphi, wavelets, psi=0.0, remove_quad=False, signal_name="burst"):
+    """add_burst with the callables built from sine-Gaussian wavelets: h+ = sum_w A+_w g_w cos(2 pi f_w (t - t0_w) + phi+_w), hx likewise
+    with the cross columns, g = exp(-1/2 ((t - t0) / tau)^2), t = mjd * 86400.  wavelets: dicts with the columns of _burst.WAV_COLUMNS
+    (t0_mjd, log10_tau [s], log10_f [Hz], log10_a_plus [s], phase_plus, log10_a_cross [s], phase_cross).  The host twin of
+    ReplicaEngine.set_burst (theta's burst_* keys).  Host only."""
+    from . import _burst
+    add_burst(psr, gwtheta, gwphi, _burst.waveform(wavelets, "log10_a_plus", "phase_plus"),
+              _burst.waveform(wavelets, "log10_a_cross", "phase_cross"), psi=psi, tref=0, remove_quad=remove_quad, signal_name=signal_name)
+
+
+def add_wavelet_transient(psr, wavelets, signal_name="noise_transient"):
+    """add_noise_transient with the callable built from sine-Gaussian wavelets (dicts with t0_mjd, log10_tau, log10_f, log10_a [s],
+    phase): the host twin of ReplicaEngine.set_transients (theta's nt_* keys with nt_psr = this pulsar).  Host only."""
+    from . import _burst
+    add_noise_transient(psr, _burst.waveform(wavelets), tref=0, signal_name=signal_name)
+
+
 def add_gw_memory(psr, strain, gwtheta, gwphi, bwm_pol, t0_mjd, signal_name="gw_memory"):
     """Burst with memory: a ramp ``pol * strain * (t - t0)`` after the burst epoch (deterministic.py:822-884).  Host only."""
     fplus, fcross, _ = antenna_patterns(psr, gwtheta, gwphi)

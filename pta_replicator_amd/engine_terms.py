@@ -1,5 +1,5 @@
 """The per-realisation terms of the ReplicaEngine: theta split into its parts, the terms added after the fused launch (one CW source
-or a catalogue, a burst with memory, white noise per group), theta drawn on chip from uniform boxes (set_*_prior, sample_theta) and theta
+or a catalogue, a burst with memory, a burst of sine-Gaussian wavelets, noise transients, white noise per group), theta drawn on chip from uniform boxes (set_*_prior, sample_theta) and theta
 made on chip from a binned binary population (set_population, population_theta: Poisson counts, loudest-k, residual spectrum).
 What the terms share is written once: the params -> add batch loop (_term_batches), the reused device tables grown on demand
 (_scratch), the buffers queued launches still read (self._keep, one entry per term) and the box draw (_uniform_table).  The fixed model,
@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _bwm, _chrom, _cproc, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
+from . import _burst, _bwm, _chrom, _cproc, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
 from ._position import ra_dec
 
 
@@ -39,6 +39,44 @@ class PerRealisationTermsMixin:
         t0_mjd.  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), psi (0, pi) (isotropic sky and polarisation).  Drawn from stream (9, 0),
         pair = label column (_bwm.COLUMNS), independently of set_hyper_prior's and set_cw_prior's parameters."""
         self._bwm_prior = _bwm.make_prior(log10_h=log10_h, t0_mjd=t0_mjd, cos_gwtheta=cos_gwtheta, gwphi=gwphi, psi=psi)
+        return self
+
+    def set_burst(self, n_wavelets=1, remove_quad=False):
+        """one GW burst PER REALISATION made of n_wavelets = W <= 128 sine-Gaussian wavelets from one sky position (the reference's
+        add_burst, deterministic.py:718-793, with the callables h+ = sum_w A+_w g_w cos(2 pi f_w (t - t0_w) + phi+_w), hx likewise; g =
+        exp(-1/2 ((t - t0) / tau)^2), t = mjd * 86400), its parameters given by the burst_* keys of theta (pta_replicator_amd._burst:
+        burst_cos_gwtheta, burst_gwphi, burst_psi [R]; burst_t0_mjd, burst_log10_tau [s], burst_log10_f [Hz], burst_log10_a_plus [s],
+        burst_phase_plus, burst_log10_a_cross [s], burst_phase_cross [R, W]; optional burst_count [R], 0 = no burst) wherever the
+        bwm_* keys are accepted, or drawn from set_burst_prior() (generate_sampled).  remove_quad: subtract the unweighted quadratic
+        fit over every pulsar's TOAs, as the reference does (a pulsar of <= 3 TOAs gets a zero term).  Added after the BWM term by
+        pta_engine_burst_add.  Adds nothing by itself; no prepare() needed."""
+        self._burst = _burst.make_config(n_wavelets, remove_quad)
+        return self
+
+    def set_transients(self, n=1):
+        """n = V <= 128 noise transients PER REALISATION, each a sine-Gaussian wavelet in one pulsar (the reference's
+        add_noise_transient, deterministic.py:796-819), given by theta's nt_psr (integer 0 .. P-1), nt_t0_mjd, nt_log10_tau, nt_log10_f,
+        nt_log10_a [s], nt_phase [R, V] and the optional nt_count [R], or drawn from set_transient_prior().  Added after the burst term
+        by pta_engine_transient_add.  Adds nothing by itself; no prepare() needed."""
+        self._nt = _burst.make_nt_config(n)
+        return self
+
+    def set_burst_prior(self, t0_mjd=None, log10_tau=None, log10_f=None, log10_a_plus=None, log10_a_cross=None, cos_gwtheta=None, gwphi=None,
+                        psi=None, phase_plus=None, phase_cross=None):
+        """uniform boxes (lo, hi) of the per-realisation wavelet burst of generate_sampled() (set_burst configures it).  Required:
+        t0_mjd, log10_tau, log10_f and the two amplitudes.  Defaults: cos_gwtheta (-1, 1), gwphi (0, 2 pi), psi (0, pi), the phases
+        (0, 2 pi).  The sky labels come from stream (13, 0), wavelet w from stream (13, 1 + w), pair = label column
+        (_burst.SKY_COLUMNS / WAV_COLUMNS): no other label or residual moves.  Every wavelet is drawn from the same boxes."""
+        self._burst_prior = _burst.make_prior(t0_mjd=t0_mjd, log10_tau=log10_tau, log10_f=log10_f, log10_a_plus=log10_a_plus,
+                                              log10_a_cross=log10_a_cross, cos_gwtheta=cos_gwtheta, gwphi=gwphi, psi=psi,
+                                              phase_plus=phase_plus, phase_cross=phase_cross)
+        return self
+
+    def set_transient_prior(self, t0_mjd=None, log10_tau=None, log10_f=None, log10_a=None, phase=None):
+        """uniform boxes (lo, hi) of the per-realisation noise transients of generate_sampled() (set_transients configures them).
+        Required: t0_mjd, log10_tau, log10_f, log10_a; phase defaults to (0, 2 pi).  Transient v comes from stream (14, v), pair = label
+        column (_burst.NT_COLUMNS); nt_psr is the floor of a U(0, P) draw."""
+        self._nt_prior = _burst.make_nt_prior(t0_mjd=t0_mjd, log10_tau=log10_tau, log10_f=log10_f, log10_a=log10_a, phase=phase)
         return self
 
     def set_cw_prior(self, log10_mc=None, log10_fgw=None, log10_h=None, log10_dist=None, cos_gwtheta=None, gwphi=None, phase0=None,
@@ -133,7 +171,7 @@ class PerRealisationTermsMixin:
     def _theta_parts(self, theta, R, td=False, check_values=True):
         """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
         (_hyper.check_theta), None for the fixed-parameter path (no theta, or the keys of det alone); det: the keys whose terms are
-        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta) and the white-noise keys
+        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta), the wavelet burst and noise-transient keys (_burst.check_theta, check_nt_theta) and the white-noise keys
         (_wn_hyper.check_theta) and the chromatic keys (_chrom.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
         skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
@@ -147,15 +185,18 @@ class PerRealisationTermsMixin:
         rest, cpk = _cproc.split(rest)
         rest, cw = _cw.split(rest)
         rest, bwm = _bwm.split(rest)
+        rest, bst, ntk = _burst.split(rest)
         if td:
             _chrom.refuse_td(self._chrom)
             _cproc.refuse_td(self._cproc)
             _wn_hyper.refuse_td(wnk)
-        if td and (rest or not (cw or bwm)):   # a deterministic term leaves the factored covariance as it is
+        if td and (rest or not (cw or bwm or bst or ntk)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
-                             "cw_* and bwm_* keys are): use generate(theta=...) or generate_sampled()")
+                             "cw_*, bwm_*, burst_* and nt_* keys are): use generate(theta=...) or generate_sampled()")
         det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
         det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
+        det.update(_burst.check_theta(bst, R, getattr(self, "_burst", None), check_values))
+        det.update(_burst.check_nt_theta(ntk, R, self.P, getattr(self, "_nt", None), check_values))
         det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
         det.update(_chrom.check_theta(chk, R, self.P, self._chrom, check_values))
         det.update(_cproc.check_theta(cpk, R, self._cproc, check_values))
@@ -165,11 +206,15 @@ class PerRealisationTermsMixin:
 
     def _det_apply(self, det, R, out):
         """out[R, n_toa] += the deterministic terms of every row for the validated deterministic keys of theta (the second member of
-        _theta_parts): the CW term, then the burst with memory."""
+        _theta_parts): the CW term, then the burst with memory, then the wavelet burst, then the noise transients."""
         if _cw.has_keys(det):
             self._cw_apply(det, R, out)
         if _bwm.has_keys(det):
             self._bwm_apply(det, R, out)
+        if _burst.has_keys(det):
+            self._burst_apply(det, R, out)
+        if _burst.has_nt_keys(det):
+            self._nt_apply(det, R, out)
         return out
 
     # ---------------------------------------------------------------- what the terms share ------
@@ -280,6 +325,61 @@ class PerRealisationTermsMixin:
         b.ld_src, b.coef, b.t0_s = src.stride(0), coef.data_ptr(), t0.data_ptr()
         self._term_batches("pta_engine_bwm_params", "pta_engine_bwm_add", b, [("src", src, 8 * src.stride(0))], R, step, out, accumulate)
         self._keep["bwm"] = src   # the launches above read it asynchronously
+        return out
+
+    # ---------------------------------------------------------------- wavelet burst, transients -
+    def _count_device(self, count, R):
+        """an optional count key of theta as a contiguous int32 device tensor [R]"""
+        if count is None:
+            return None
+        return (count.to(device=dv.require_gpu(), dtype=torch.int32) if hasattr(count, "data_ptr") else dv.i32(np.asarray(count))).reshape(R).contiguous()
+
+    def _burst_quad_tables(self):
+        """theta-independent tables of remove_quad, built once per prepare(): the first TOA of every pulsar [P + 1] and the orthonormal
+        basis of (1, t, t^2) over every pulsar's TOAs [n_toa, 3] (_burst.quad_basis)"""
+        if getattr(self, "_burst_quad", None) is None or self._burst_quad[0] is not self.d_toa_s:
+            self._burst_quad = (self.d_toa_s, dv.i32(np.asarray(self.off, dtype=np.int32)), dv.f64(_burst.quad_basis([m * 86400 for m in self.mjd])))
+        return self._burst_quad[1:]
+
+    def _burst_apply(self, det, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the wavelet burst of every row for validated theta `det`: the sky [R, 3] and wavelet [R, W, 7] label
+        tables -> pta_engine_burst_params (wav [R, W, 7], kk [R, P, 2]) -> pta_engine_burst_add (with remove_quad: pta_engine_burst_quad,
+        c [R, P, 3], inside it), in batches of max_batch() bounded by the one-launch index range of the tables.  The tables are
+        R (7 W + 2 P (+ 3 P)) doubles and stay outside the workspace budget."""
+        if not self._prepared:
+            self.prepare()
+        P, W, quad = self.P, self._burst["W"], self._burst["remove_quad"]
+        sky = torch.stack([dv.as_f64(det[k]).reshape(R) for k in _burst.SKY_KEYS], dim=1).contiguous()      # [R, 3]
+        src = torch.stack([dv.as_f64(det[k]).reshape(R, W) for k in _burst.WAV_KEYS], dim=2).contiguous()   # [R, W, 7]
+        count = self._count_device(det.get(_burst.COUNT_KEY), R)
+        step = min(R, self.max_batch(), 65535, ((1 << 31) - 1) // (max(7 * W, 3 * P) + W + P))
+        wav, kk, qc = self._scratch("burst_tab", (step, W, 7), (step, P, 2), (step if quad else 0, P, 3))
+        b = _lib.BurstEngine()
+        b.n_psr, b.n_wav, b.phat, b.toa_s = P, W, self._phat_device().data_ptr(), self.d_toa_s.data_ptr()
+        b.wav, b.kk = wav.data_ptr(), kk.data_ptr()
+        if quad:
+            off, q = self._burst_quad_tables()
+            b.psr_off, b.quad_q, b.quad_c = off.data_ptr(), q.data_ptr(), qc.data_ptr()
+        rows = [("sky", sky, 8 * 3), ("src", src, 8 * 7 * W), ("count", count, 4)]
+        self._term_batches("pta_engine_burst_params", "pta_engine_burst_add", b, rows, R, step, out, accumulate)
+        self._keep["burst"] = (sky, src, count)   # the launches above read them asynchronously
+        return out
+
+    def _nt_apply(self, det, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the noise transients of every row for validated theta `det`: the [R, V, 6] label table ->
+        pta_engine_transient_params (tab [R, V, 6]) -> pta_engine_transient_add, in batches of max_batch()."""
+        if not self._prepared:
+            self.prepare()
+        V = self._nt["V"]
+        src = torch.stack([dv.as_f64(det[k]).reshape(R, V) for k in _burst.NT_KEYS], dim=2).contiguous()   # [R, V, 6]
+        count = self._count_device(det.get(_burst.NT_COUNT_KEY), R)
+        step = min(R, self.max_batch(), ((1 << 31) - 1) // (7 * V))
+        t = _lib.TransientEngine()
+        t.n_psr, t.n_wav, t.toa_s = self.P, V, self.d_toa_s.data_ptr()
+        t.tab = self._scratch("nt_tab", (step, V, 6)).data_ptr()
+        rows = [("src", src, 8 * 6 * V), ("count", count, 4)]
+        self._term_batches("pta_engine_transient_params", "pta_engine_transient_add", t, rows, R, step, out, accumulate)
+        self._keep["transient"] = (src, count)   # the launches above read them asynchronously
         return out
 
     # ---------------------------------------------------------------- chromatic process ---------
@@ -462,19 +562,25 @@ class PerRealisationTermsMixin:
         hi[j]) of bounds() -> (lo, hi).  The boxes `name` are uploaded once per prior object: the cache entry holds the prior dict it
         was built from, so a set_*_prior call, which replaces the dict, invalidates it.  mid: the entry's arguments between R and lo
         (default: the column count n)."""
-        ent = self._boxes.get(name)
-        if ent is None or ent[0] is not prior:
-            ent = self._boxes[name] = (prior, [dv.f64(x) for x in bounds()])
-        d_lo, d_hi = ent[1]
+        d_lo, d_hi = self._box_device(name, prior, bounds)
         table = dv.empty(shape or (R, d_lo.shape[0]))
         _lib.call(entry, self.seed, r0, R, *((d_lo.shape[0],) if mid is None else mid), dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(table), dv.stream_ptr())
         return table
+
+    def _box_device(self, name, prior, bounds):
+        """(lo, hi) of the boxes `name` on the device, uploaded once per prior object (_uniform_table)"""
+        ent = self._boxes.get(name)
+        if ent is None or ent[0] is not prior:
+            ent = self._boxes[name] = (prior, [dv.f64(x) for x in bounds()])
+        return ent[1]
 
     def _sample_theta(self, R, r0, orf_info):
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         wn_prior, chrom_prior, cp_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None), getattr(self, "_cproc_prior", None)
         pop = getattr(self, "_pop", None)
-        if prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None and pop is None:
+        burst_prior, nt_prior = getattr(self, "_burst_prior", None), getattr(self, "_nt_prior", None)
+        if (prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None and pop is None
+                and burst_prior is None and nt_prior is None):
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
@@ -483,6 +589,20 @@ class PerRealisationTermsMixin:
             theta.update(self.population_theta(R, r0))
         if bwm_prior is not None:   # stream (9, 0): pair j = label column j, whatever else is sampled
             theta.update(_bwm.labels(self._uniform_table("pta_bwm_uniform", "bwm", bwm_prior, lambda: _bwm.prior_bounds(bwm_prior), R, r0, mid=())))
+        if burst_prior is not None:   # streams (13, 0) and (13, 1 + w): pair j = label column j, whatever else is sampled
+            if getattr(self, "_burst", None) is None:
+                raise ValueError("sample_theta: no per-realisation wavelet burst configured (set_burst)")
+            W = self._burst["W"]
+            sky, wav = dv.empty((R, 3)), dv.empty((R, W, 7))
+            d_lo, d_hi = self._box_device("burst", burst_prior, lambda: _burst.prior_bounds(burst_prior))
+            _lib.call("pta_burst_uniform", self.seed, r0, R, W, dv.ptr(d_lo), dv.ptr(d_hi), dv.ptr(sky), dv.ptr(wav), dv.stream_ptr())
+            theta.update(_burst.labels(sky, wav))
+        if nt_prior is not None:      # stream (14, v): pair j = label column j, whatever else is sampled
+            if getattr(self, "_nt", None) is None:
+                raise ValueError("sample_theta: no per-realisation noise transients configured (set_transients)")
+            V = self._nt["V"]
+            theta.update(_burst.nt_labels(self._uniform_table("pta_transient_uniform", "nt", nt_prior, lambda: _burst.nt_prior_bounds(nt_prior, self.P),
+                                                              R, r0, mid=(V, self.P), shape=(R, V, 6))))
         if cw_prior is not None:    # stream (8, 0): pair j = label column j, whatever else is sampled
             S, cw_bounds = cw_prior["n_sources"], lambda: _cw.prior_bounds(cw_prior, self.P)
             table = catalog = None
