@@ -1121,7 +1121,20 @@ int pta_selftest_mfma_f64(double *max_err_host);
  *   pta_gwb_mix_batched_plan   plan[0..2] = nta = ceil(P / 16) (1..5), tpw (64-sample tiles per workgroup), grid.x; all three 0 when the
  *                              launch goes to the batched GEMM (variant != 0 or P > 80)
  *   pta_fstat_fe_plan, pta_bwm_stat_plan   plan[0..2] = ks = ceil(P / 4) (1..32), rchunk (realisations per workgroup), ngz = ceil(R / rchunk)
- *   pta_tm_project_plan        plan[0..1] = m (the instance, 1..12), grid.y                                                        */
+ *   pta_tm_project_plan        plan[0..1] = m (the instance, 1..12), grid.y
+ *   pta_dgemm_plan             takes everything pta_dgemm's choice reads: the shape, the strides of A and B, the byte offsets of the A and
+ *                              B pointers modulo 16 (offA, offB: 0..15), lower_only, algo and batch.  plan[0..4] =
+ *                                kernel: 0 k_dgemm_valu<false>, 1 k_dgemm_valu<true> (the template argument is transB), 2 k_dgemm_mfma<false>,
+ *                                        3 k_dgemm_mfma<true>, 4 k_dgemm_mfma128<false, false>, 5 k_dgemm_mfma128<true, false>,
+ *                                        6 k_dgemm_mfma128<true, true> (16-byte operand loads), 7 k_dgemm_glds128<false, 0> (operand slabs
+ *                                        by LDS DMA), 8 k_dgemm_glds128<false, 1> (the same with the C-tile prefetch epilogue);
+ *                                tile:   columns (= rows) of a workgroup's C tile, 128 or 64; 0 for the VALU kernels (a thread per element);
+ *                                lower:  0 lower_only off; 1 a 2-D grid whose workgroups (threads, VALU) above the diagonal leave at once;
+ *                                        2 a 1-D grid over the tiles on or below the diagonal of a square C; 3 a 1-D grid over those of a
+ *                                        trapezoid (M > N: the triangle of the top square, then the rectangle below it);
+ *                                grid.x, grid.y.
+ *                              Kernels 6..8 need transB, ska = 1, even K, lda, ldb, strideA and strideB, and offA = offB = 0; a transB
+ *                              call that misses one of these gets kernel 5.                                                        */
 int pta_os_project_plan(int C, int P, int R, int32_t *plan);
 int pta_lnl_apply_plan(int P, int K, int G, int R, int32_t *plan);
 int pta_fstat_project_plan(int C, int P, int R, int32_t *plan);
@@ -1129,6 +1142,8 @@ int pta_gwb_mix_batched_plan(int P, int R, int npts, int variant, int32_t *plan)
 int pta_fstat_fe_plan(int P, int J, int R, int S, int32_t *plan);
 int pta_bwm_stat_plan(int P, int J, int R, int S, int32_t *plan);
 int pta_tm_project_plan(int m, int P, int R, int32_t *plan);
+int pta_dgemm_plan(int transB, int M, int N, int K, int64_t lda, int64_t ska, int64_t ldb, int64_t strideA, int64_t strideB, int offA,
+                   int offB, int lower_only, int algo, int batch, int32_t *plan);
 
 /* ---------------------------------------------------------------- sine-Gaussian wavelets per realisation (ABI 8, additive) */
 /* The reference's add_burst / add_noise_transient (deterministic.py:718-819) with the callables taken from one family,

@@ -265,6 +265,8 @@ _SIGNATURES = {
     "pta_fstat_fe_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "pta_bwm_stat_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int32)]),
     "pta_tm_project_plan": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
+    "pta_dgemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
+                               POINTER(c_int32)]),
     "pta_gwb_spectrum_scale_user": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P]),
     "pta_hyper_uniform_field": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "pta_os_matched_prior_spec": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_double, _P, _P, _P, c_int, _P, c_int64, _P, _P, _P]),
@@ -279,13 +281,19 @@ _PLAN_FIELDS = {
     "pta_fstat_fe": ("ks", "rchunk", "ngz"),
     "pta_bwm_stat": ("ks", "rchunk", "ngz"),
     "pta_tm_project": ("m", "grid_y"),
+    "pta_dgemm": ("kernel", "tile", "lower_mode", "grid_x", "grid_y"),
 }
+
+# plan["kernel"] / plan["lower_mode"] of pta_dgemm_plan (include/pta_replicator_amd.h)
+DGEMM_KERNELS = ("k_dgemm_valu<false>", "k_dgemm_valu<true>", "k_dgemm_mfma<false>", "k_dgemm_mfma<true>", "k_dgemm_mfma128<false,false>",
+                 "k_dgemm_mfma128<true,false>", "k_dgemm_mfma128<true,true>", "k_dgemm_glds128<false,0>", "k_dgemm_glds128<false,1>")
+DGEMM_LOWER = ("none", "grid2d", "triangle", "trapezoid")
 
 
 def launch_plan(launcher, *sizes):
     """What `launcher` would choose for a launch of these sizes (the arguments of its pta_*_plan entry, without `plan`), as a dict.
     No device call."""
-    out = (c_int32 * 4)()
+    out = (c_int32 * 8)()
     check(getattr(lib, launcher + "_plan")(*[int(v) for v in sizes], out), launcher + "_plan")
     return {k: int(out[i]) for i, k in enumerate(_PLAN_FIELDS[launcher])}
 

@@ -604,51 +604,110 @@ __global__ void k_dgemm_valu(int M, int N, int K, double alpha, const double *__
 // launch to ONE column tile: pta_potrf_step_ws)
 int pta_dgemm_tile_n(int M, int N, int K, int algo) { return (algo >= 1 && M >= 256 && N >= 128 && K >= 32) ? HBM_T : GBN; }
 
-int pta_dgemm_launch(int transB, int M, int N, int K, double alpha, const double *A, int64_t lda, int64_t ska,
-                     const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int lower_only, int batch,
-                     int64_t sA, int64_t sB, int64_t sC, int algo, hipStream_t stream) {
-  PTA_REQUIRE(A && B && C, PTA_E_ARG, "pta_dgemm: NULL argument");
-  PTA_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535, PTA_E_ARG, "pta_dgemm: M=%d N=%d K=%d batch=%d", M, N, K, batch);
+// The launch plan of pta_dgemm, the one place it is decided: the kernel instance, its tile, how `lower_only` reaches it and the grid.
+// Everything the choice reads is an argument (of the operands only their byte offsets modulo 16); `who` names the entry in the refusals.
+enum {
+  PTA_DGEMM_VALU_N = 0,    // k_dgemm_valu<false>
+  PTA_DGEMM_VALU_T = 1,    // k_dgemm_valu<true>
+  PTA_DGEMM_MFMA_N = 2,    // k_dgemm_mfma<false>
+  PTA_DGEMM_MFMA_T = 3,    // k_dgemm_mfma<true>
+  PTA_DGEMM_M128_N = 4,    // k_dgemm_mfma128<false, false>
+  PTA_DGEMM_M128_T = 5,    // k_dgemm_mfma128<true, false>
+  PTA_DGEMM_M128_TV = 6,   // k_dgemm_mfma128<true, true>
+  PTA_DGEMM_GLDS_E0 = 7,   // k_dgemm_glds128<false, 0>
+  PTA_DGEMM_GLDS_E1 = 8    // k_dgemm_glds128<false, 1>
+};
+enum { PTA_DGEMM_LOWER_NONE = 0, PTA_DGEMM_LOWER_GRID2D = 1, PTA_DGEMM_LOWER_TRIANGLE = 2, PTA_DGEMM_LOWER_TRAPEZOID = 3 };
+struct pta_dgemm_choice {
+  int kernel, tile, lower_mode;
+  int lower_arg;  // the kernel's `lower_only`: the caller's, or 2 on a 1-D grid
+  dim3 grid;
+};
+
+static int pta_dgemm_choose(const char *who, int transB, int M, int N, int K, int64_t lda, int64_t ska, int64_t ldb, int64_t sA, int64_t sB,
+                            unsigned offA, unsigned offB, int lower_only, int algo, int batch, pta_dgemm_choice &c) {
+  PTA_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535, PTA_E_ARG, "%s: M=%d N=%d K=%d batch=%d", who, M, N, K, batch);
+  c.lower_arg = lower_only;
+  c.lower_mode = lower_only ? PTA_DGEMM_LOWER_GRID2D : PTA_DGEMM_LOWER_NONE;
   if (algo == 0) {
-    PTA_REQUIRE(M <= 65535, PTA_E_ARG, "pta_dgemm: VALU kernel supports M <= 65535 (got %d)", M);
-    dim3 g(pta_cdiv(N, 128), M, batch);
-    if (transB)
-      hipLaunchKernelGGL(k_dgemm_valu<true>, g, dim3(128), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
-    else
-      hipLaunchKernelGGL(k_dgemm_valu<false>, g, dim3(128), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
+    PTA_REQUIRE(M <= 65535, PTA_E_ARG, "%s: VALU kernel supports M <= 65535 (got %d)", who, M);
+    c.grid = dim3(pta_cdiv(N, 128), M, batch);
+    c.kernel = transB ? PTA_DGEMM_VALU_T : PTA_DGEMM_VALU_N;
+    c.tile = 0;
   } else if (algo >= 1 && M >= 256 && N >= 128 && K >= 32) {  // large operands: 128x128 tiles (algo 2: operand slabs by LDS DMA)
-    PTA_REQUIRE(pta_cdiv(M, HBM_T) <= 65535u, PTA_E_ARG, "pta_dgemm: M=%d too large", M);
+    PTA_REQUIRE(pta_cdiv(M, HBM_T) <= 65535u, PTA_E_ARG, "%s: M=%d too large", who, M);
     dim3 g(pta_cdiv(N, HBM_T), pta_cdiv(M, HBM_T), batch);
     if (lower_only && M == N) {
       const unsigned nt = pta_cdiv(M, HBM_T);
       g = dim3(nt * (nt + 1) / 2, 1, batch);
       lower_only = 2;
+      c.lower_mode = PTA_DGEMM_LOWER_TRIANGLE;
     }
     const bool vec = transB && ska == 1 && (K % 2) == 0 && (lda % 2) == 0 && (ldb % 2) == 0 && (sA % 2) == 0 && (sB % 2) == 0 &&
-                     ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0;
+                     (offA % 16) == 0 && (offB % 16) == 0;
     if (lower_only == 1 && M > N && vec && algo >= 2) {  // trapezoid (a block column with its diagonal block on top): 1-D grid over its tiles
       const unsigned nt = pta_cdiv(N, HBM_T), mt = pta_cdiv(M, HBM_T);
       g = dim3(nt * (nt + 1) / 2 + (mt - nt) * nt, 1, batch);
       lower_only = 2;
+      c.lower_mode = PTA_DGEMM_LOWER_TRAPEZOID;
     }
-    if (vec && algo >= 2) {
-      auto kern = algo == 3 ? k_dgemm_glds128<false, 1> : k_dgemm_glds128<false, 0>;
+    c.grid = g;
+    c.lower_arg = lower_only;
+    c.tile = HBM_T;
+    if (vec && algo >= 2)
+      c.kernel = algo == 3 ? PTA_DGEMM_GLDS_E1 : PTA_DGEMM_GLDS_E0;
+    else if (vec)
+      c.kernel = PTA_DGEMM_M128_TV;
+    else
+      c.kernel = transB ? PTA_DGEMM_M128_T : PTA_DGEMM_M128_N;
+  } else {
+    PTA_REQUIRE(pta_cdiv(M, GBM) <= 65535u, PTA_E_ARG, "%s: M=%d too large", who, M);
+    c.grid = dim3(pta_cdiv(N, GBN), pta_cdiv(M, GBM), batch);
+    c.kernel = transB ? PTA_DGEMM_MFMA_T : PTA_DGEMM_MFMA_N;
+    c.tile = GBN;
+  }
+  return PTA_OK;
+}
+
+extern "C" int pta_dgemm_plan(int transB, int M, int N, int K, int64_t lda, int64_t ska, int64_t ldb, int64_t strideA, int64_t strideB,
+                              int offA, int offB, int lower_only, int algo, int batch, int32_t *plan) {
+  PTA_REQUIRE(plan, PTA_E_ARG, "pta_dgemm_plan: NULL argument");
+  PTA_REQUIRE(offA >= 0 && offA < 16 && offB >= 0 && offB < 16, PTA_E_ARG, "pta_dgemm_plan: offA=%d offB=%d (byte offsets modulo 16)", offA, offB);
+  pta_dgemm_choice c;
+  const int rc = pta_dgemm_choose("pta_dgemm_plan", transB, M, N, K, lda, ska, ldb, strideA, strideB, (unsigned)offA, (unsigned)offB, lower_only,
+                                  algo, batch, c);
+  if (rc != PTA_OK) return rc;
+  plan[0] = c.kernel, plan[1] = c.tile, plan[2] = c.lower_mode, plan[3] = (int32_t)c.grid.x, plan[4] = (int32_t)c.grid.y;
+  return PTA_OK;
+}
+
+int pta_dgemm_launch(int transB, int M, int N, int K, double alpha, const double *A, int64_t lda, int64_t ska,
+                     const double *B, int64_t ldb, double beta, double *C, int64_t ldc, int lower_only, int batch,
+                     int64_t sA, int64_t sB, int64_t sC, int algo, hipStream_t stream) {
+  PTA_REQUIRE(A && B && C, PTA_E_ARG, "pta_dgemm: NULL argument");
+  pta_dgemm_choice c;
+  const int rc = pta_dgemm_choose("pta_dgemm", transB, M, N, K, lda, ska, ldb, sA, sB, (unsigned)((uintptr_t)A % 16), (unsigned)((uintptr_t)B % 16),
+                                  lower_only, algo, batch, c);
+  if (rc != PTA_OK) return rc;
+  const dim3 g = c.grid;
+  lower_only = c.lower_arg;
+#define PTA_DGEMM_GO(KERN, BLOCK) \
+  hipLaunchKernelGGL(KERN, g, dim3(BLOCK), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC)
+  switch (c.kernel) {
+    case PTA_DGEMM_VALU_N: PTA_DGEMM_GO(k_dgemm_valu<false>, 128); break;
+    case PTA_DGEMM_VALU_T: PTA_DGEMM_GO(k_dgemm_valu<true>, 128); break;
+    case PTA_DGEMM_MFMA_N: PTA_DGEMM_GO(k_dgemm_mfma<false>, 256); break;
+    case PTA_DGEMM_MFMA_T: PTA_DGEMM_GO(k_dgemm_mfma<true>, 256); break;
+    case PTA_DGEMM_M128_N: PTA_DGEMM_GO((k_dgemm_mfma128<false, false>), 256); break;
+    case PTA_DGEMM_M128_T: PTA_DGEMM_GO((k_dgemm_mfma128<true, false>), 256); break;
+    case PTA_DGEMM_M128_TV: PTA_DGEMM_GO((k_dgemm_mfma128<true, true>), 256); break;
+    default: {
+      auto kern = c.kernel == PTA_DGEMM_GLDS_E1 ? k_dgemm_glds128<false, 1> : k_dgemm_glds128<false, 0>;
       hipLaunchKernelGGL(kern, g, dim3(256), 0, stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
                          lower_only, sA, sB, sC, pta_rag{nullptr, nullptr, nullptr, 0}, 0, 0, 0, 0);
-    } else if (vec)
-      hipLaunchKernelGGL((k_dgemm_mfma128<true, true>), g, dim3(256), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
-    else if (transB)
-      hipLaunchKernelGGL((k_dgemm_mfma128<true, false>), g, dim3(256), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
-    else
-      hipLaunchKernelGGL((k_dgemm_mfma128<false, false>), g, dim3(256), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
-  } else {
-    PTA_REQUIRE(pta_cdiv(M, GBM) <= 65535u, PTA_E_ARG, "pta_dgemm: M=%d too large", M);
-    dim3 g(pta_cdiv(N, GBN), pta_cdiv(M, GBM), batch);
-    if (transB)
-      hipLaunchKernelGGL(k_dgemm_mfma<true>, g, dim3(256), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
-    else
-      hipLaunchKernelGGL(k_dgemm_mfma<false>, g, dim3(256), 0, stream, M, N, K, alpha, A, lda, ska, B, ldb, beta, C, ldc, lower_only, sA, sB, sC);
+    }
   }
+#undef PTA_DGEMM_GO
   PTA_LAUNCH_CHECK();
   return PTA_OK;
 }

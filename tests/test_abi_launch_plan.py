@@ -10,7 +10,7 @@ import numpy as np
 from test_abi import declared
 
 PLANS = ("pta_os_project_plan", "pta_lnl_apply_plan", "pta_fstat_project_plan", "pta_gwb_mix_batched_plan", "pta_fstat_fe_plan",
-         "pta_bwm_stat_plan", "pta_tm_project_plan")
+         "pta_bwm_stat_plan", "pta_tm_project_plan", "pta_dgemm_plan")
 PTA_E_ARG = -1
 
 
@@ -75,6 +75,25 @@ def test_bad_sizes_are_refused_without_gpu():
     refused("pta_tm_project_plan", 3, 8, 8 * 65535 + 1)
 
 
+def test_dgemm_plan_refuses_what_pta_dgemm_refuses():
+    from pta_replicator_amd import _lib
+    lib = _lib.lib
+    out = (ctypes.c_int32 * 8)()
+    good = dict(transB=1, M=300, N=130, K=46, lda=60, ska=1, ldb=60, sA=18000, sB=7800, offA=0, offB=0, lower=1, algo=2, batch=2)
+
+    def ask(**kw):
+        for i in range(8):
+            out[i] = -77
+        return lib.pta_dgemm_plan(*{**good, **kw}.values(), out)
+    assert ask() == 0 and list(out)[:5] == [7, 128, 3, 5, 1] and list(out)[5:] == [-77] * 3
+    assert lib.pta_dgemm_plan(*good.values(), None) == PTA_E_ARG and "NULL" in _lib.last_error()
+    for kw in (dict(M=0), dict(N=0), dict(K=0), dict(batch=0), dict(M=-1), dict(N=-1), dict(K=-1), dict(batch=65536), dict(offA=16), dict(offB=-1),
+               dict(algo=0, M=65536), dict(M=128 * 65535 + 1), dict(M=64 * 65535 + 1, N=5)):
+        assert ask(**kw) == PTA_E_ARG and "pta_dgemm_plan" in _lib.last_error(), (kw, _lib.last_error())
+        assert list(out) == [-77] * 8, "a refused query writes nothing"
+    assert ask(algo=0, M=65535) == 0 and ask(M=128 * 65535) == 0 and ask(M=64 * 65535, N=5) == 0 and ask(batch=65535) == 0
+
+
 # ---------------------------------------------------------------- the launch arithmetic, as the launchers have had it ----------
 def _os(C, P, R):
     rw = 2 if cdiv(R, 128) * P >= 1024 else 1
@@ -113,6 +132,55 @@ def _sky(jb):
 
 def _tm(m, P, R):
     return {"m": m, "grid_y": cdiv(R, 8)}
+
+
+DGEMM_VALU_N, DGEMM_VALU_T, DGEMM_MFMA_N, DGEMM_MFMA_T, DGEMM_M128_N, DGEMM_M128_T, DGEMM_M128_TV, DGEMM_GLDS_E0, DGEMM_GLDS_E1 = range(9)
+
+
+def _dgemm(transB, M, N, K, lda, ska, ldb, sA, sB, offA, offB, lower, algo, batch):
+    """pta_dgemm_launch's choice as it stood before it moved into pta_dgemm_choose"""
+    mode = 1 if lower else 0
+    if algo == 0:
+        return {"kernel": DGEMM_VALU_T if transB else DGEMM_VALU_N, "tile": 0, "lower_mode": mode, "grid_x": cdiv(N, 128), "grid_y": M}
+    if algo >= 1 and M >= 256 and N >= 128 and K >= 32:
+        gx, gy = cdiv(N, 128), cdiv(M, 128)
+        if lower and M == N:
+            nt = cdiv(M, 128)
+            gx, gy, lower, mode = nt * (nt + 1) // 2, 1, 2, 2
+        vec = bool(transB) and ska == 1 and K % 2 == 0 and lda % 2 == 0 and ldb % 2 == 0 and sA % 2 == 0 and sB % 2 == 0 and offA % 16 == 0 \
+            and offB % 16 == 0
+        if lower == 1 and M > N and vec and algo >= 2:
+            nt, mt = cdiv(N, 128), cdiv(M, 128)
+            gx, gy, mode = nt * (nt + 1) // 2 + (mt - nt) * nt, 1, 3
+        if vec and algo >= 2:
+            kern = DGEMM_GLDS_E1 if algo == 3 else DGEMM_GLDS_E0
+        elif vec:
+            kern = DGEMM_M128_TV
+        else:
+            kern = DGEMM_M128_T if transB else DGEMM_M128_N
+        return {"kernel": kern, "tile": 128, "lower_mode": mode, "grid_x": gx, "grid_y": gy}
+    return {"kernel": DGEMM_MFMA_T if transB else DGEMM_MFMA_N, "tile": 64, "lower_mode": mode, "grid_x": cdiv(N, 64), "grid_y": cdiv(M, 64)}
+
+
+def test_dgemm_plan_equals_the_launch_arithmetic_at_random_arguments():
+    from pta_replicator_amd import _lib
+    rng = np.random.default_rng(419)
+    seen = set()
+    for _ in range(20000):
+        M, N, K = (int(rng.choice([int(rng.integers(1, 700)), int(rng.integers(250, 262)), int(rng.integers(120, 136)), int(rng.integers(28, 36))]))
+                   for _ in range(3))
+        if rng.uniform() < 0.3:
+            N = M
+        near = lambda: int(rng.integers(0, 4000)) if rng.uniform() < 0.3 else 2 * int(rng.integers(0, 2000))    # mostly even
+        args = (int(rng.integers(0, 2)), M, N, K, near(), 1 if rng.uniform() < 0.8 else int(rng.integers(1, 4)), near(), near(), near(),
+                int(rng.choice([0, 0, 0, 8])), int(rng.choice([0, 0, 0, 8])), int(rng.integers(0, 2)), int(rng.integers(0, 4)), int(rng.integers(1, 5)))
+        want = _dgemm(*args)
+        got = _lib.launch_plan("pta_dgemm", *args)
+        assert got == want, (args, got, want)
+        seen.add((want["kernel"], want["lower_mode"]))
+    assert len(seen) == 25, sorted(seen)     # every (instance, lower mode) pair the launcher can produce
+    # offsets that are no multiple of 8 cannot come from a double pointer, but the predicate is "% 16 == 0"
+    assert _lib.launch_plan("pta_dgemm", 1, 256, 128, 32, 40, 1, 40, 0, 0, 4, 0, 0, 2, 1)["kernel"] == DGEMM_M128_T
 
 
 def _log_int(rng, lo, hi):
