@@ -56,7 +56,8 @@ int pta_device_info(int *cu_count, int *wavefront, char *arch, int arch_len);
  * field is the source index s, pta_cw_catalog_uniform),
  * 9 BWM (pulsar field 0: per-realisation burst-with-memory labels, pair j = label column, uniform u2; pta_bwm_uniform),
  * 13 BURST (field 0: the sky labels of a per-realisation wavelet burst, field 1 + w: wavelet w; pair j = label column; pta_burst_uniform),
- * 14 NT (field v: noise transient v of the realisation, pair j = label column; pta_transient_uniform). */
+ * 14 NT (field v: noise transient v of the realisation, pair j = label column; pta_transient_uniform),
+ * 15 CE (field e: chromatic event slot e of the realisation, pair j = label column; pta_chrom_event_uniform). */
 
 /* `rng_fast` (argument or plan field of every call that draws on chip) selects the Gaussian transform: 0 (default) = fp64
  * Box-Muller with < 1 ulp log / sincos, 1 = "fast RNG math": the same uniforms through the hardware fp32 log / sqrt / sin /
@@ -1144,6 +1145,71 @@ int pta_bwm_stat_plan(int P, int J, int R, int S, int32_t *plan);
 int pta_tm_project_plan(int m, int P, int R, int32_t *plan);
 int pta_dgemm_plan(int transB, int M, int N, int K, int64_t lda, int64_t ska, int64_t ldb, int64_t strideA, int64_t strideB, int offA,
                    int offB, int lower_only, int algo, int batch, int32_t *plan);
+
+/* ---------------------------------------------------------------- chromatic events per realisation (ABI 8, additive) */
+/* Deterministic terms in one pulsar that scale with the radio frequency nu_i [MHz] of the TOA: with t = mjd * 86400, t0 = t0_mjd * 86400,
+ * A = 10^log10_a [s at nu_ref], s = -1 if sign < 0 else +1, chi = index, tau = 10^log10_tau [s],
+ *     dt_i = s A (nu_ref / nu_i)^chi shape(t_i),
+ *     kind 0 decay   t >= t0: exp(-(t - t0) / tau),  t < t0: 0
+ *     kind 1 cusp    t >= t0: exp(-(t - t0) / tau),  t < t0: exp(-(t0 - t) / tau_pre)   (tau_pre = 10^log10_tau_pre, tau if that is NaN)
+ *     kind 2 bump    exp(-1/2 ((t - t0) / tau)^2)
+ *     kind 3 annual  sin(2 pi t / 31557600 + phase)                                     (t0, tau unused)
+ * A TOA at exactly t0 takes the t >= t0 side (formulas, the exponent fold and its rounding: csrc/pta_chrom_event.h).  Stream kind 15,
+ * field = event slot, pair = label column, uniform u2.
+ * Labels: src[(r * E + e) * 9 + j], j = PTA_CE_COL_*: 0 psr (an integer 0 .. P-1 held as a double), 1 kind (0 .. 3 held as a double),
+ * 2 t0_mjd, 3 log10_tau [s], 4 log10_tau_pre [s] or NaN, 5 log10_a [s], 6 sign, 7 index, 8 phase [rad].
+ * Table: tab[(r * E + e) * 10 + j], j = PTA_CE_TAB_*: 0 psr, 1 kind, 2 t0 [s], 3 1 / tau, 4 1 / tau_pre, 5 -1/2 / tau^2, 6 s = -1 or +1,
+ * 7 ln A = log10_a ln 10, 8 chi, 9 phase / (2 pi) [turns].                                                                          */
+#define PTA_CE_NCOL 9
+#define PTA_CE_NTAB 10
+#define PTA_CE_EMAX 128
+#define PTA_CE_COL_PSR 0
+#define PTA_CE_COL_KIND 1
+#define PTA_CE_COL_T0_MJD 2
+#define PTA_CE_COL_LOG10_TAU 3
+#define PTA_CE_COL_LOG10_TAU_PRE 4
+#define PTA_CE_COL_LOG10_A 5
+#define PTA_CE_COL_SIGN 6
+#define PTA_CE_COL_INDEX 7
+#define PTA_CE_COL_PHASE 8
+#define PTA_CE_TAB_PSR 0
+#define PTA_CE_TAB_KIND 1
+#define PTA_CE_TAB_T0 2
+#define PTA_CE_TAB_INV_TAU 3
+#define PTA_CE_TAB_INV_TAU_PRE 4
+#define PTA_CE_TAB_NH 5
+#define PTA_CE_TAB_SIGN 6
+#define PTA_CE_TAB_LNA 7
+#define PTA_CE_TAB_CHI 8
+#define PTA_CE_TAB_TURNS 9
+
+/* out[R x E x 9] drawn from per-slot boxes lo / hi: device [E x 9]; column j of slot e of realisation r0 + r is the box draw of pair j
+ * of stream (15, e) in (lo[e * 9 + j], hi[e * 9 + j]); lo == hi gives exactly lo, which is how a column is fixed (a slot's kind, a fixed
+ * pulsar, a fixed sign).  Column 0 is floored and kept in 0 .. P-1, so the box (0, P) draws the pulsar.  1 <= E <= PTA_CE_EMAX.        */
+int pta_chrom_event_uniform(uint64_t seed, uint64_t r0, int R, int E, int P, const double *lo, const double *hi, double *out, void *stream);
+
+/* The chromatic events of every realisation of a batch.  Device pointers.                                                           */
+typedef struct {
+  int32_t n_psr;              /* P */
+  int32_t n_ev;               /* E, 1 .. PTA_CE_EMAX */
+  const double *toa_s;        /* [n_toa] MJD * 86400 over the concatenated TOAs */
+  const double *lnu;          /* [n_toa] ln(nu_ref / nu_i) over the concatenated TOAs */
+  const double *src;          /* [R x E x 9] label rows of realisation r0 + r */
+  const int32_t *count;       /* [R] events in use, 0 .. E (clamped), or NULL = E; rows past the count are never read */
+  double *tab;                /* [R x E x 10] table rows, written by pta_engine_chrom_event_params */
+} pta_chrom_event_engine;
+
+/* tab from src: one thread per (r, e); rows at or past count[r] are neither read nor written.                                        */
+int pta_engine_chrom_event_params(const pta_chrom_event_engine *ce_host, int R, void *stream);
+
+/* out[r * ld_out + i] (+)= sum over the events e < count[r] whose psr is the pulsar of TOA i, in ascending e in a register, over the
+ * plan's TOA tiles (as pta_engine_bwm_add reads the plan): one exp per (event, TOA) for kinds 0 - 2, exp and a sine in turns for kind
+ * 3; needs toa_s, lnu and tab.  accumulate = 1: one read-modify-write per element of a pulsar that holds a live event of the
+ * realisation; the elements of every other (realisation, pulsar) are neither read nor written and keep their bits.  accumulate = 0:
+ * every element of rows 0 .. R-1 is written, +0.0 where there is no event.  No atomics; a realisation's term is the same bits in every
+ * batch and row slot.                                                                                                                */
+int pta_engine_chrom_event_add(const pta_engine_plan *plan_host, const pta_chrom_event_engine *ce_host, int R, double *out, int64_t ld_out,
+                               int accumulate, void *stream);
 
 /* ---------------------------------------------------------------- sine-Gaussian wavelets per realisation (ABI 8, additive) */
 /* The reference's add_burst / add_noise_transient (deterministic.py:718-819) with the callables taken from one family,

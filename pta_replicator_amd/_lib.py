@@ -109,6 +109,13 @@ class TransientEngine(ctypes.Structure):
     ]
 
 
+class ChromEventEngine(ctypes.Structure):
+    """pta_chrom_event_engine (include/pta_replicator_amd.h)."""
+    _fields_ = [
+        ("n_psr", c_int32), ("n_ev", c_int32), ("toa_s", _P), ("lnu", _P), ("src", _P), ("count", _P), ("tab", _P),
+    ]
+
+
 class WnHyper(ctypes.Structure):
     """pta_engine_wn_hyper (include/pta_replicator_amd.h)."""
     _fields_ = [
@@ -215,6 +222,9 @@ _SIGNATURES = {
     "pta_engine_burst_add": (c_int, [POINTER(EnginePlan), POINTER(BurstEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_transient_params": (c_int, [POINTER(TransientEngine), c_int, _P]),
     "pta_engine_transient_add": (c_int, [POINTER(EnginePlan), POINTER(TransientEngine), c_int, _P, c_int64, c_int, _P]),
+    "pta_chrom_event_uniform": (c_int, [c_uint64, c_uint64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "pta_engine_chrom_event_params": (c_int, [POINTER(ChromEventEngine), c_int, _P]),
+    "pta_engine_chrom_event_add": (c_int, [POINTER(EnginePlan), POINTER(ChromEventEngine), c_int, _P, c_int64, c_int, _P]),
     "pta_engine_wn_params": (c_int, [POINTER(WnHyper), c_int, _P]),
     "pta_engine_wn_add": (c_int, [POINTER(EnginePlan), POINTER(WnHyper), c_uint64, c_uint64, c_int, _P, c_int64, c_int, _P]),
     "pta_engine_chrom_coef": (c_int, [POINTER(ChromEngine), c_uint64, c_uint64, c_int, _P]),

@@ -316,6 +316,32 @@ def add_wavelet_transient(psr, wavelets, signal_name="noise_transient"):
     add_noise_transient(psr, _burst.waveform(wavelets), tref=0, signal_name=signal_name)
 
 
+def add_chromatic_event(psr, kind, log10_a, t0_mjd=None, log10_tau=None, log10_tau_pre=None, sign=-1, index=2.0, phase=0.0, ref_freq_mhz=1400.0,
+                        signal_name="chromatic_event"):
+    """A deterministic chromatic term in one pulsar, s A (nu_ref / nu_i)^index shape(t_i) with t = mjd * 86400, A = 10^log10_a [s at
+    ref_freq_mhz], s = -1 if sign < 0 else +1: kind 0 / "decay" exp(-(t - t0) / tau) after t0 (a DM dip), 1 / "cusp" the same with
+    exp(-(t0 - t) / tau_pre) before it (tau_pre = tau if log10_tau_pre is None), 2 / "bump" exp(-1/2 ((t - t0) / tau)^2), 3 / "annual"
+    sin(2 pi t / YEAR_IN_SEC + phase); tau = 10^log10_tau [s] (_chrom_event.term on the pulsar's own TOAs and radio frequencies).  The
+    host twin of ReplicaEngine.set_chromatic_events (theta's ce_* keys with ce_psr = this pulsar).  psr may be a list.  Host only."""
+    from . import _chrom, _chrom_event
+    if isinstance(psr, (list, tuple)):
+        for p in psr:
+            add_chromatic_event(p, kind, log10_a, t0_mjd, log10_tau, log10_tau_pre, sign, index, phase, ref_freq_mhz, signal_name)
+        return
+    code = _chrom_event.kind_code(kind, "add_chromatic_event")
+    if code != 3 and (t0_mjd is None or log10_tau is None):
+        raise ValueError(f"add_chromatic_event: t0_mjd and log10_tau are required for kind {_chrom_event.KINDS[code]!r}")
+    _chrom_event.make_config(1, ref_freq_mhz)
+    if float(sign) == 0:
+        raise ValueError("add_chromatic_event: sign must be non-zero")
+    freqs = _chrom.toa_freqs(psr)
+    _chrom_event.log_freq_ratio(freqs, ref_freq_mhz, name=f"pulsar {getattr(psr, 'name', '?')}")
+    row = {"kind": code, "log10_a": log10_a, "t0_mjd": t0_mjd, "log10_tau": log10_tau, "log10_tau_pre": log10_tau_pre, "sign": sign,
+           "index": index, "phase": phase}
+    toas = psr.toas.get_mjds().value * 86400
+    _record(psr, signal_name, dict(row, ref_freq_mhz=ref_freq_mhz), _chrom_event.term(np.asarray(toas, dtype=np.float64), freqs, [row], ref_freq_mhz))
+
+
 def add_gw_memory(psr, strain, gwtheta, gwphi, bwm_pol, t0_mjd, signal_name="gw_memory"):
     """Burst with memory: a ramp ``pol * strain * (t - t0)`` after the burst epoch (deterministic.py:822-884).  Host only."""
     fplus, fcross, _ = antenna_patterns(psr, gwtheta, gwphi)

@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _burst, _bwm, _chrom, _cproc, _cw, _hyper, _lib, _wn_hyper, device as dv
+from . import _burst, _bwm, _chrom, _chrom_event, _cproc, _cw, _hyper, _lib, _wn_hyper, device as dv
 from . import deterministic as det
 from . import red_noise as rn
 from . import spharmORFbasis as anis
@@ -84,6 +84,7 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         self._bwm = False    # one burst with memory per realisation (set_bwm), parameters from theta / set_bwm_prior
         self._burst = None   # a burst of sine-Gaussian wavelets per realisation (set_burst), parameters from theta / set_burst_prior
         self._nt = None      # noise transients per realisation (set_transients), parameters from theta / set_transient_prior
+        self._ce = None      # chromatic events per realisation (set_chromatic_events), parameters from theta / set_chromatic_event_prior
         self._pop = self._popd = None   # a binary population per realisation (set_population): host tables, their device copies
         self._chrom = None   # one chromatic Gaussian process per pulsar (set_chromatic_noise), added after the fused launch
         self._chrom_t = None   # its device tables, built by prepare()
@@ -578,7 +579,9 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         added once by pta_engine_cw_catalog_add.  With set_bwm(), theta may hold one burst with memory per realisation (the five bwm_*
         keys, pta_replicator_amd._bwm), added by pta_engine_bwm_add after the CW term.  With set_burst() / set_transients(), theta may hold a
         burst of sine-Gaussian wavelets and noise transients per realisation (the burst_* and nt_* keys, pta_replicator_amd._burst),
-        added after the BWM term by pta_engine_burst_add and then pta_engine_transient_add.  On an engine configured with set_gwb(lmax=L >= 1)
+        added after the BWM term by pta_engine_burst_add and then pta_engine_transient_add.  With set_chromatic_events(), theta may hold
+        chromatic events per realisation (the ce_* keys, pta_replicator_amd._chrom_event), added after the noise transients by
+        pta_engine_chrom_event_add.  On an engine configured with set_gwb(lmax=L >= 1)
         (correlated, gwb_mode "fourier") theta may hold gwb_clm [R, (L+1)^2]: row r replaces the configured clm for realisation r0 + r
         (column k = l^2 + m + l, correlated_basis' order), with the reference's semantics, ORF_r = 2 sum_k clm_r[k] basis[k],
         M_r = chol(ORF_r), G_r = M_r G0_r: pta_gwb_orf_factor fills the factors ahead of each batch and pta_gwb_mix_batched mixes with
@@ -787,12 +790,13 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         theta also holds population_theta(R, r0): gwb_log10_hc [R, F], the cw_* keys [R, S] with cw_count [R], and the labels pop_cell,
         pop_number [R, S] (streams (11, attempt) and (8, s)).  With set_burst_prior() / set_transient_prior() theta holds the burst_* keys
         (sky labels from stream (13, 0), wavelet w from stream (13, 1 + w)) and the nt_* keys (transient v from stream (14, v); nt_psr
-        int32, the floor of a U(0, P) draw)."""
+        int32, the floor of a U(0, P) draw).  With set_chromatic_event_prior() theta holds the ce_* keys (slot e from stream (15, e); ce_psr
+        and ce_kind int32)."""
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         wn_prior, chrom_prior, cp_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None), getattr(self, "_cproc_prior", None)
         burst_prior, nt_prior = getattr(self, "_burst_prior", None), getattr(self, "_nt_prior", None)
         if (prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None
-                and getattr(self, "_pop", None) is None and burst_prior is None and nt_prior is None):
+                and getattr(self, "_pop", None) is None and burst_prior is None and nt_prior is None and getattr(self, "_ce_prior", None) is None):
             raise ValueError("generate_sampled: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if cp_prior is not None and not self._cproc:
             raise ValueError("generate_sampled: common-process boxes given but no common process is configured (add_common_process)")
@@ -860,7 +864,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
         CW keys the dict also has 'cw', the per-realisation CW term (pta_engine_cw_add writing its own buffer; for a catalogue the
         sum over its sources, pta_engine_cw_catalog_add); with BWM keys 'bwm', the per-realisation burst-with-memory term alone
         (pta_engine_bwm_add writing its own buffer); with burst_* keys 'burst' and with nt_* keys 'transient', the wavelet burst and the
-        noise transients alone (pta_engine_burst_add / pta_engine_transient_add writing their own buffers); with white-noise keys (wn_efac / wn_log10_equad, wn_log10_ecorr) 'wn' and 'ecorr' are the
+        noise transients alone (pta_engine_burst_add / pta_engine_transient_add writing their own buffers); with ce_* keys 'chrom_event', the
+        chromatic events alone (pta_engine_chrom_event_add writing its own buffer); with white-noise keys (wn_efac / wn_log10_equad, wn_log10_ecorr) 'wn' and 'ecorr' are the
         per-realisation terms (pta_engine_wn_add writing its own buffer); on an engine with a chromatic process
         (set_chromatic_noise) 'chrom', that term alone (pta_engine_chrom_add writing its own buffer)."""
         hyper, cw = self._theta_parts(theta, R)
@@ -911,6 +916,8 @@ class ReplicaEngine(PerRealisationTermsMixin, TimeDomainMixin, OptimalStatisticM
             out["burst"] = self._burst_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         if _burst.has_nt_keys(cw):   # 'transient': the noise transients alone (pta_engine_transient_add writing its own buffer)
             out["transient"] = self._nt_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
+        if _chrom_event.has_keys(cw):   # 'chrom_event': the chromatic events alone (pta_engine_chrom_event_add writing its own buffer)
+            out["chrom_event"] = self._ce_apply(cw, R, dv.empty((R, self.n_toa)), accumulate=False)
         if self._chrom is not None:
             out["chrom"] = self._chrom_apply(cw, R, r0, dv.empty((R, self.n_toa)), accumulate=False)
         if self._cproc:   # 'common': the sum of the common processes (add_common_process), pta_engine_cproc_add writing its own buffer

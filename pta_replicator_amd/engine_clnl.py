@@ -31,7 +31,7 @@ from . import optimal_statistic as ost
 from .engine_stats import StatisticsMixin, check_components, check_timing_model
 
 GRID_KEYS = ("gwb_log10_A", "gwb_gamma")
-_FIXED_PREFIXES = ("rn_", "wn_", "chrom_", "cp_", "cw_", "bwm_", "burst_", "nt_")
+_FIXED_PREFIXES = ("rn_", "wn_", "chrom_", "cp_", "cw_", "bwm_", "burst_", "nt_", "ce_")
 _FIXED_KEYS = ("gwb_log10_hc", "gwb_clm")
 
 

@@ -348,7 +348,7 @@ class TimeDomainMixin:
         VALU work on the ALUs the matrix pipe shares, not idle time to fill."""
         _chrom.refuse_td(self._chrom, "generate_td")
         _cproc.refuse_td(self._cproc, "generate_td")
-        _, cw = self._theta_parts(theta, R, td=True)   # only deterministic keys (cw_*, bwm_*, burst_*, nt_*), added after the batch
+        _, cw = self._theta_parts(theta, R, td=True)   # only deterministic keys (cw_*, bwm_*, burst_*, nt_*, ce_*), added after the batch
         if not getattr(self, "_td_prepared", False) or not self._prepared:
             self.prepare_td()
         if out is None:

@@ -1,5 +1,5 @@
 """The per-realisation terms of the ReplicaEngine: theta split into its parts, the terms added after the fused launch (one CW source
-or a catalogue, a burst with memory, a burst of sine-Gaussian wavelets, noise transients, white noise per group), theta drawn on chip from uniform boxes (set_*_prior, sample_theta) and theta
+or a catalogue, a burst with memory, a burst of sine-Gaussian wavelets, noise transients, chromatic events, white noise per group), theta drawn on chip from uniform boxes (set_*_prior, sample_theta) and theta
 made on chip from a binned binary population (set_population, population_theta: Poisson counts, loudest-k, residual spectrum).
 What the terms share is written once: the params -> add batch loop (_term_batches), the reused device tables grown on demand
 (_scratch), the buffers queued launches still read (self._keep, one entry per term) and the box draw (_uniform_table).  The fixed model,
@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _burst, _bwm, _chrom, _cproc, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
+from . import _burst, _bwm, _chrom, _chrom_event, _cproc, _cw, _hyper, _lib, _pop, _wn_hyper, device as dv
 from ._position import ra_dec
 
 
@@ -77,6 +77,38 @@ class PerRealisationTermsMixin:
         Required: t0_mjd, log10_tau, log10_f, log10_a; phase defaults to (0, 2 pi).  Transient v comes from stream (14, v), pair = label
         column (_burst.NT_COLUMNS); nt_psr is the floor of a U(0, P) draw."""
         self._nt_prior = _burst.make_nt_prior(t0_mjd=t0_mjd, log10_tau=log10_tau, log10_f=log10_f, log10_a=log10_a, phase=phase)
+        return self
+
+    def set_chromatic_events(self, n=1, ref_freq_mhz=1400.0):
+        """n = E <= 128 chromatic events PER REALISATION: deterministic terms in one pulsar that scale with the TOA's radio frequency,
+        dt_i = s A (nu_ref / nu_i)^chi shape(t_i) with shape an exponential decay after t0 (kind 0, a DM dip), a cusp (1), a Gaussian bump
+        (2) or the yearly sinusoid (3) (pta_replicator_amd._chrom_event, csrc/pta_chrom_event.h), given by theta's ce_psr (integer
+        0 .. P-1), ce_kind (0 .. 3 or "decay" / "cusp" / "bump" / "annual"), ce_t0_mjd, ce_log10_tau [s], ce_log10_a [s at ref_freq_mhz]
+        [R, E], the optional ce_log10_tau_pre (NaN = symmetric), ce_sign (-1), ce_index (2), ce_phase (0) [R, E] and ce_count [R],
+        wherever the nt_* keys are accepted, or drawn from set_chromatic_event_prior().  The radio frequencies come from the pulsars
+        (toas.freqs_mhz, else toas.get_freqs()); a pulsar without them, or with a non-finite or non-positive one, is refused by name.
+        Added after the noise transients by pta_engine_chrom_event_add.  Adds nothing by itself; no prepare() needed.  A prior set for
+        another n is dropped."""
+        conf = _chrom_event.make_config(n, ref_freq_mhz)
+        for p in self.psrs:
+            _chrom_event.log_freq_ratio(_chrom.toa_freqs(p), conf["ref_freq_mhz"], name=f"pulsar {getattr(p, 'name', '?')}")
+        self._ce, self._ce_lnu = conf, None
+        if getattr(self, "_ce_prior", None) is not None and len(self._ce_prior["kind"]) != conf["E"]:
+            self._ce_prior = None
+        return self
+
+    def set_chromatic_event_prior(self, kind, log10_a, psr=None, t0_mjd=None, log10_tau=None, log10_tau_pre=None, sign=-1, index=2.0,
+                                  phase=(0.0, 2 * np.pi)):
+        """the boxes of the per-realisation chromatic events of generate_sampled() (set_chromatic_events configures them).  Every
+        argument is a scalar (the column is fixed), a box (lo, hi) (a tuple), or a list of E of those, one per slot.  kind is fixed per
+        slot and never drawn; psr=None draws the pulsar as the floor of U(0, P); sign="random" is the box (-1, 1); t0_mjd and log10_tau
+        are required for slots of kinds 0 - 2; log10_tau_pre=None is the NaN label (a symmetric cusp).  Slot e comes from stream (15, e),
+        pair = label column (_chrom_event.COLUMNS): a label row is a function of (seed, realisation, slot) alone, and no other label or
+        residual moves."""
+        if getattr(self, "_ce", None) is None:
+            raise ValueError("set_chromatic_event_prior: no per-realisation chromatic events configured (set_chromatic_events)")
+        self._ce_prior = _chrom_event.make_prior(self._ce["E"], self.P, kind, log10_a, psr=psr, t0_mjd=t0_mjd, log10_tau=log10_tau,
+                                                 log10_tau_pre=log10_tau_pre, sign=sign, index=index, phase=phase)
         return self
 
     def set_cw_prior(self, log10_mc=None, log10_fgw=None, log10_h=None, log10_dist=None, cos_gwtheta=None, gwphi=None, phase0=None,
@@ -171,7 +203,7 @@ class PerRealisationTermsMixin:
     def _theta_parts(self, theta, R, td=False, check_values=True):
         """(hyper, det): theta of R realisations split and validated before anything is launched.  hyper: its GWB / red-noise keys
         (_hyper.check_theta), None for the fixed-parameter path (no theta, or the keys of det alone); det: the keys whose terms are
-        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta), the wavelet burst and noise-transient keys (_burst.check_theta, check_nt_theta) and the white-noise keys
+        added after the fused launch, the CW keys (_cw.check_theta), the BWM keys (_bwm.check_theta), the wavelet burst and noise-transient keys (_burst.check_theta, check_nt_theta), the chromatic-event keys (_chrom_event.check_theta) and the white-noise keys
         (_wn_hyper.check_theta) and the chromatic keys (_chrom.check_theta) in one dict, {} if none.  td=True: TD mode, which takes deterministic keys only.  check_values=False
         skips the value checks (theta drawn by sample_theta)."""
         if theta is None:
@@ -186,17 +218,19 @@ class PerRealisationTermsMixin:
         rest, cw = _cw.split(rest)
         rest, bwm = _bwm.split(rest)
         rest, bst, ntk = _burst.split(rest)
+        rest, cek = _chrom_event.split(rest)
         if td:
             _chrom.refuse_td(self._chrom)
             _cproc.refuse_td(self._cproc)
             _wn_hyper.refuse_td(wnk)
-        if td and (rest or not (cw or bwm or bst or ntk)):   # a deterministic term leaves the factored covariance as it is
+        if td and (rest or not (cw or bwm or bst or ntk or cek)):   # a deterministic term leaves the factored covariance as it is
             raise ValueError("per-realisation theta is not supported in TD mode (the dense factors are built for one covariance; only "
-                             "cw_*, bwm_*, burst_* and nt_* keys are): use generate(theta=...) or generate_sampled()")
+                             "cw_*, bwm_*, burst_*, nt_* and ce_* keys are): use generate(theta=...) or generate_sampled()")
         det = dict(_cw.check_theta(cw, R, self.P, self._cw, check_values))
         det.update(_bwm.check_theta(bwm, R, self._bwm, check_values))
         det.update(_burst.check_theta(bst, R, getattr(self, "_burst", None), check_values))
         det.update(_burst.check_nt_theta(ntk, R, self.P, getattr(self, "_nt", None), check_values))
+        det.update(_chrom_event.check_theta(cek, R, self.P, getattr(self, "_ce", None), check_values))
         det.update(_wn_hyper.check_theta(wnk, R, self.P, self._wn, self._ec, self.wn_mode, check_values))
         det.update(_chrom.check_theta(chk, R, self.P, self._chrom, check_values))
         det.update(_cproc.check_theta(cpk, R, self._cproc, check_values))
@@ -206,7 +240,7 @@ class PerRealisationTermsMixin:
 
     def _det_apply(self, det, R, out):
         """out[R, n_toa] += the deterministic terms of every row for the validated deterministic keys of theta (the second member of
-        _theta_parts): the CW term, then the burst with memory, then the wavelet burst, then the noise transients."""
+        _theta_parts): the CW term, then the burst with memory, then the wavelet burst, then the noise transients, then the chromatic events."""
         if _cw.has_keys(det):
             self._cw_apply(det, R, out)
         if _bwm.has_keys(det):
@@ -215,6 +249,8 @@ class PerRealisationTermsMixin:
             self._burst_apply(det, R, out)
         if _burst.has_nt_keys(det):
             self._nt_apply(det, R, out)
+        if _chrom_event.has_keys(det):
+            self._ce_apply(det, R, out)
         return out
 
     # ---------------------------------------------------------------- what the terms share ------
@@ -380,6 +416,33 @@ class PerRealisationTermsMixin:
         rows = [("src", src, 8 * 6 * V), ("count", count, 4)]
         self._term_batches("pta_engine_transient_params", "pta_engine_transient_add", t, rows, R, step, out, accumulate)
         self._keep["transient"] = (src, count)   # the launches above read them asynchronously
+        return out
+
+    # ---------------------------------------------------------------- chromatic events ----------
+    def _ce_lnu_device(self):
+        """lnu [n_toa] = ln(nu_ref / nu_i) over the concatenated TOAs on the device, tabulated in long double and rounded to float64 once
+        per prepare() (_chrom_event.log_freq_ratio)"""
+        if getattr(self, "_ce_lnu", None) is None or self._ce_lnu[0] is not self.d_toa_s:
+            lnu = [_chrom_event.log_freq_ratio(_chrom.toa_freqs(p), self._ce["ref_freq_mhz"], name=f"pulsar {getattr(p, 'name', '?')}")
+                   for p in self.psrs]
+            self._ce_lnu = (self.d_toa_s, dv.f64(np.concatenate(lnu)))
+        return self._ce_lnu[1]
+
+    def _ce_apply(self, det, R, out, accumulate=True):
+        """out[R, n_toa] (+)= the chromatic events of every row for validated theta `det`: the [R, E, 9] label table ->
+        pta_engine_chrom_event_params (tab [R, E, 10]) -> pta_engine_chrom_event_add, in batches of max_batch()."""
+        if not self._prepared:
+            self.prepare()
+        E = self._ce["E"]
+        src = torch.stack([dv.as_f64(det[k]).reshape(R, E) for k in _chrom_event.KEYS], dim=2).contiguous()   # [R, E, 9]
+        count = self._count_device(det.get(_chrom_event.COUNT_KEY), R)
+        step = min(R, self.max_batch(), ((1 << 31) - 1) // (11 * E))
+        c = _lib.ChromEventEngine()
+        c.n_psr, c.n_ev, c.toa_s, c.lnu = self.P, E, self.d_toa_s.data_ptr(), self._ce_lnu_device().data_ptr()
+        c.tab = self._scratch("ce_tab", (step, E, 10)).data_ptr()
+        rows = [("src", src, 8 * 9 * E), ("count", count, 4)]
+        self._term_batches("pta_engine_chrom_event_params", "pta_engine_chrom_event_add", c, rows, R, step, out, accumulate)
+        self._keep["chrom_event"] = (src, count)   # the launches above read them asynchronously
         return out
 
     # ---------------------------------------------------------------- chromatic process ---------
@@ -578,9 +641,9 @@ class PerRealisationTermsMixin:
         prior, cw_prior, bwm_prior = getattr(self, "_prior", None), getattr(self, "_cw_prior", None), getattr(self, "_bwm_prior", None)
         wn_prior, chrom_prior, cp_prior = getattr(self, "_wn_prior", None), getattr(self, "_chrom_prior", None), getattr(self, "_cproc_prior", None)
         pop = getattr(self, "_pop", None)
-        burst_prior, nt_prior = getattr(self, "_burst_prior", None), getattr(self, "_nt_prior", None)
+        burst_prior, nt_prior, ce_prior = getattr(self, "_burst_prior", None), getattr(self, "_nt_prior", None), getattr(self, "_ce_prior", None)
         if (prior is None and cw_prior is None and bwm_prior is None and wn_prior is None and chrom_prior is None and cp_prior is None and pop is None
-                and burst_prior is None and nt_prior is None):
+                and burst_prior is None and nt_prior is None and ce_prior is None):
             raise ValueError("sample_theta: no prior (set_hyper_prior / set_cw_prior / set_bwm_prior first)")
         if not self._prepared:
             self.prepare()
@@ -603,6 +666,13 @@ class PerRealisationTermsMixin:
             V = self._nt["V"]
             theta.update(_burst.nt_labels(self._uniform_table("pta_transient_uniform", "nt", nt_prior, lambda: _burst.nt_prior_bounds(nt_prior, self.P),
                                                               R, r0, mid=(V, self.P), shape=(R, V, 6))))
+        if ce_prior is not None:      # stream (15, e): pair j = label column j of slot e, whatever else is sampled
+            if getattr(self, "_ce", None) is None or len(ce_prior["kind"]) != self._ce["E"]:
+                raise ValueError("sample_theta: the chromatic-event prior does not match the configured events (set_chromatic_events, "
+                                 "then set_chromatic_event_prior)")
+            E = self._ce["E"]
+            theta.update(_chrom_event.labels(self._uniform_table("pta_chrom_event_uniform", "chrom_event", ce_prior,
+                                                                 lambda: _chrom_event.prior_bounds(ce_prior), R, r0, mid=(E, self.P), shape=(R, E, 9))))
         if cw_prior is not None:    # stream (8, 0): pair j = label column j, whatever else is sampled
             S, cw_bounds = cw_prior["n_sources"], lambda: _cw.prior_bounds(cw_prior, self.P)
             table = catalog = None
